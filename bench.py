@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what its headline figure needs: build, warm up, time the K steps, write the outputs of the last timed step
+(``--dump-outputs DIR``) and print the JSON line.  Everything else the line can carry -- the roofline and per-kernel passes, the
+CPU baseline, the 50-step tolerance check, the reference GPU policy, the cache-on pass, the executed whole image and the
+data-parallel self-check -- runs with ``--full`` only.
 
 Precision of the headline (``--precision tolerance``, the default of c4 / c4full): the composition whose distance from the
 reference's CPU path after 50 + 50 steps is inside north_star's 1e-3 -- measured in the same run against the reference-generated
@@ -24,13 +29,15 @@ of each stage.  With the phase times taken at device-synchronised stamps inside 
 
     value = n_gpus / (50 * t_S1_iter + 50 * t_S2_iter + t_fixed)          [images / s, whole job]
 
-After the timed region (outside ``value``) the same process EXECUTES one whole image -- all 50 + 50 iterations, warm -- and prints it beside
-the projection (``config.whole_image_executed``: 76.56 s executed vs 76.48 s projected on the round-6 tree).  ``--workload c4full`` times
+A K (or W) above the sampler's step count (``--ddpm-steps``, 50) runs as several units of at most that many iterations each (the
+fixed part once per unit, ``t_fixed`` = its mean).  With ``--full``, after the timed region (outside ``value``) the same process EXECUTES one whole image -- all 50 + 50
+iterations, warm -- and prints it beside the projection (``config.whole_image_executed``: 76.56 s executed vs 76.48 s projected on
+the round-6 tree).  ``--workload c4full`` times
 complete images instead (one image per step).  Other workloads: ``c2`` (BASELINE configs[1],
 Stage 1 only 128->512 batch 4), ``c3`` (configs[2], Stage 2 at 2048^2 batch 8 with the per-image
 feature cache), ``s2`` (Stage 2 only, any size).
 
-The JSON line also carries
+With ``--full`` the JSON line also carries
   roofline     : the dominant kernel of the workload: algorithmic FLOPs of its launches / their summed
                  HIP-event durations (events on the launch stream, one extra instrumented pass), and the
                  HBM-side bytes per launch from the committed rocprofv3 PMC passes of this same workload;
@@ -289,6 +296,28 @@ def barrier(world):
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
+
+
+def unit_iterations(n, T):
+    """``n`` sampler iterations per stage as units of at most ``T`` (one truncated pipeline run each): [T, ..., T, rest]."""
+    return [min(T, n - i) for i in range(0, n, T)]
+
+
+DUMP_SAMPLE = 1 << 22      # elements per dumped array at most (16 MB of float32); the whole dump stays under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs DIR``: what the timed path returned in its last step, one float32 ``DIR/<name>.npy`` per array.  An array of
+    more than DUMP_SAMPLE elements is written as a fixed sample, flat: its elements at DUMP_SAMPLE flat indices drawn by a CPU
+    generator seeded with 0 and sorted (the same indices on every run with the same shapes); a smaller one whole, in its shape."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, f"{name}.npy"), t.to(torch.float32).cpu().numpy())
 
 
 def kernel_table(summ):
@@ -564,12 +593,13 @@ def bench_headline(args, dev, rank, world):
             print(json.dumps({"pmc_pass": True, "workload": args.workload}), flush=True)
         return
 
-    n_timed = None if full else K
     if full:
         for w in range(W):
             one_image(rank + world * w, cond, None, Phases())
-    elif W > 0:
-        one_image(rank, cond, W, Phases())                  # W untimed iterations of each stage (+ the fixed part once)
+    else:
+        for n_it in unit_iterations(W, T):                  # W untimed iterations of each stage (+ the fixed part once per unit)
+            one_image(rank, cond, n_it, Phases())
+    units = K if full else len(unit_iterations(K, T))       # pipeline runs in the timed region: the fixed part ran once in each
     ph = Phases()
     # one line per rank BEFORE the timed region: a hang behind it is attributable to a rank, a device and a phase
     rccl = None
@@ -588,29 +618,33 @@ def bench_headline(args, dev, rank, world):
         for k in range(K):
             out = one_image(rank + world * (W + k), cond, None, ph)
     else:
-        out = one_image(rank, cond, n_timed, ph)
+        for n_it in unit_iterations(K, T):
+            out = one_image(rank, cond, n_it, ph)
     barrier(world)
     dt = time.perf_counter() - t0
     a = ph.acc
     s1_loop, s2_loop = a["s1_loop"], a["edm_sampler_loop"]
     fixed = sum(v for k, v in a.items() if k not in ("s1_loop", "edm_sampler_loop"))
-    per_rank = dist_gather_rows([s1_loop / K * 1e3 / (T if full else 1), s2_loop / K * 1e3 / (T if full else 1), fixed * 1e3 / (K if full else 1),
-                                 a.get("caption", 0.0) * 1e3 / (K if full else 1), a.get("handoff", 0.0) * 1e3 / (K if full else 1)], dev, world)
+    per_rank = dist_gather_rows([s1_loop / K * 1e3 / (T if full else 1), s2_loop / K * 1e3 / (T if full else 1), fixed * 1e3 / units,
+                                 a.get("caption", 0.0) * 1e3 / units, a.get("handoff", 0.0) * 1e3 / units], dev, world)
     dt, s1_loop, s2_loop, fixed = dist_max([dt, s1_loop, s2_loop, fixed], dev, world)
     if full:
         value = world * BPG * K / dt
         it1, it2, fx = s1_loop / (K * T), s2_loop / (K * T), fixed / K
     else:
-        it1, it2, fx = s1_loop / K, s2_loop / K, fixed     # (per unit of BPG images)
+        it1, it2, fx = s1_loop / K, s2_loop / K, fixed / units     # (per unit of BPG images)
         value = world * BPG / (T * it1 + T * it2 + fx)
     finite = bool(torch.isfinite(out.float()).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": out})    # the finished uint8 images of every rank (after the all-gather)
 
+    # ---- everything below up to the line itself runs with --full only (a plain run stops at the headline figure)
     # ---- data-parallel self-check (outside the timed region): every rank runs ONE iteration per stage + the fixed part on
     # its image and the results are gathered; rank 0 then computes EVERY other rank's image by itself (world <= 8; else the last
     # rank's only), the way a 1-rank job would, and compares bit for bit with what that rank contributed (per-image seeds:
     # infer_dir.py:198-200 sharding must not change an image)
     dp_check = None
-    if world > 1 and not full:
+    if args.full and world > 1 and not full:
         chk = one_image(rank, cond, 1, Phases())
         if rank == 0:
             probes = list(range(1, world)) if world <= 8 else [world - 1]
@@ -623,7 +657,7 @@ def bench_headline(args, dev, rank, world):
         barrier(world)
 
     headline_prec = PRECISION
-    extras = rank == 0 and world == 1 and not full and not args.no_extras and BPG == 1
+    extras = args.full and rank == 0 and world == 1 and not full and not args.no_extras and BPG == 1
     # per-image feature-cache decisions of the timed unit (threshold > 0): hits per image over the iterations that ran
     cache_per_image = None
     if thr > 0 and getattr(one_image, "cache_traces", None):
@@ -645,7 +679,7 @@ def bench_headline(args, dev, rank, world):
     # rest of A its share of the per-image fixed part, and fixed + 50 x per-iteration its time in a WHOLE image -- the dominant kernel
     # is chosen on that (in 2 iterations + the fixed part the VAE's convolutions would outweigh the attention that is 28 % of an image).
     summ = None
-    if rank == 0:
+    if args.full and rank == 0:
         passes = []
         for n_it in (1, 3):
             prof = ops.LaunchProfiler()
@@ -747,7 +781,7 @@ def bench_headline(args, dev, rank, world):
         pmc = ({"default": "r04_c4_pmc_traffic.json", "reference-gpu": "r04_c4_pmc_traffic.json", "tolerance": tol_pmc,
                 "split": "r04_c4_split_pmc_traffic.json"}.get(PRECISION, "none (no PMC pass for this mode)")
                if is_metric_cfg else "none (PMC passes exist for the metric's configuration only)")
-        roof = roofline_of(summ, pmc)
+        roof = roofline_of(summ, pmc) if summ is not None else None
         tf_img = (S1_TF_PER_IMAGE_STEP.get(side, 0) + S2_TF_PER_IMAGE_STEP.get(latent, 0)) * T
         line = {
             "metric": METRIC if is_metric_cfg else f"two-stage SR images/sec @{T} steps, {args.lr_side}px x{args.scale} (secondary workload)",
@@ -772,8 +806,9 @@ def bench_headline(args, dev, rank, world):
                              "instead of the live LLaVA prompt; ") + "seeded random-init weights of the shipped architectures"),
                 "step_definition": ("one complete image per step" if full else
                                     f"one sampler iteration of EACH stage at the real shapes; the timed region = the per-image fixed "
-                                    f"part once + exactly {K} iterations per stage; value = n_gpus / ({T}*t_S1_iter + {T}*t_S2_iter + "
-                                    f"t_fixed)"),
+                                    f"part once{'' if units == 1 else f' in each of {units} pipeline runs of at most {T} iterations'} + "
+                                    f"exactly {K} iterations per stage; value = n_gpus / ({T}*t_S1_iter + {T}*t_S2_iter + t_fixed)"),
+                "full": bool(args.full),
                 "global_batch": world * BPG, "batch_per_gpu": BPG,
                 "sub_batches": None if BPG == 1 else {"stage1_images_per_launch": c1, "stage2_images_per_launch": c2,
                                                       "why": "images are independent units (infer_dir.py:196-201); a sub-batch keeps its 4096^2 activations resident"},
@@ -781,9 +816,9 @@ def bench_headline(args, dev, rank, world):
                 "parallelism": f"dp{world}",
                 "precision_mode": PRECISION, "precision": precision_report(net, m),
                 "t_s1_iter_ms": round(it1 * 1e3, 1), "t_s2_iter_ms": round(it2 * 1e3, 1), "t_fixed_ms": round(fx * 1e3, 1),
-                "t_caption_ms": round(a.get("caption", 0.0) / (K if full else 1) * 1e3, 1) if live else None,
+                "t_caption_ms": round(a.get("caption", 0.0) / units * 1e3, 1) if live else None,
                 "caption_overlaps_vae_front": bool(live and not args.serial_caption),
-                "t_conditioner_ms": round(a.get("conditioner", 0.0) / (K if full else 1) * 1e3, 1),
+                "t_conditioner_ms": round(a.get("conditioner", 0.0) / units * 1e3, 1),
                 "caption_new_tokens": getattr(captioner, "last_tokens", None) if live else None,
                 "caption_breakdown": getattr(captioner, "breakdown", None) if live else None,
                 "seconds_per_image": round((T * it1 + T * it2 + fx) / BPG, 2),
@@ -793,16 +828,16 @@ def bench_headline(args, dev, rank, world):
                 "phases_ms": {k: round(v * 1e3, 1) for k, v in a.items()},
                 "timed_region_s": round(dt, 2), "model_build_s": round(build_s, 1), "finite": finite,
                 "algorithmic_tflops_whole_image": round(tf_img * BPG / (T * it1 + T * it2 + fx), 1),
-                "mfma_busy_whole_image_pmc": mfma_busy_of_pass(summ, pmc),
+                "mfma_busy_whole_image_pmc": mfma_busy_of_pass(summ, pmc) if summ is not None else None,
                 "feature_cache": "off" if thr <= 0 else thr, "cache_decisions_per_image": cache_per_image, "dp_self_check": dp_check,
                 "tolerance": tolerance, "reference_gpu_policy": ref_gpu, "cache_on": cache_on,
                 "collective": {"backend": (torch.distributed.get_backend() if world > 1 else None), "world_size_reported":
                                (torch.distributed.get_world_size() if world > 1 else 1), "rccl_version": rccl,
-                               "uint8_and_all_gather_ms": round(a.get("gather", 0.0) / (K if full else 1) * 1e3, 3),
+                               "uint8_and_all_gather_ms": round(a.get("gather", 0.0) / units * 1e3, 3),
                                "payload_bytes_per_rank": int(out[0].numel()) if out.dim() == 4 else None}},
             "roofline": roof}
     if rank == 0:
-        line["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else guarded(lambda: cpu_baseline_headline(m, params, T, side, latent))
+        line["cpu_baseline"] = None if (not args.full or args.no_cpu_baseline or world > 1) else guarded(lambda: cpu_baseline_headline(m, params, T, side, latent))
         print(json.dumps(line), flush=True)
 
 
@@ -880,13 +915,17 @@ def bench_stage2(args, dev, rank, world):
         hits = round(sum(flat) / max(len(flat), 1), 3)
     if rank != 0:
         return
-    prof = ops.LaunchProfiler()
-    ops.set_profiler(prof)
-    with measure.hooks(m, max_steps=2):
-        m.just_sampling(img, [""] * args.batch, **kw)
-    torch.cuda.synchronize()
-    ops.set_profiler(None)
-    summ = prof.summary()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"images": out})     # this rank's Stage-2 output batch
+    summ = None
+    if args.full:          # the roofline's instrumented pass (2 sampler iterations)
+        prof = ops.LaunchProfiler()
+        ops.set_profiler(prof)
+        with measure.hooks(m, max_steps=2):
+            m.just_sampling(img, [""] * args.batch, **kw)
+        torch.cuda.synchronize()
+        ops.set_profiler(None)
+        summ = prof.summary()
     L = side // 8
     tf_step = S2_TF_PER_IMAGE_STEP.get(L)
     line = {"metric": "Stage-2 images/sec (secondary workload)", "value": round(args.batch * world * args.steps / dt, 4),
@@ -900,7 +939,7 @@ def bench_stage2(args, dev, rank, world):
                        "cache_hit_rate": hits,
                        "algorithmic_tflops_no_cache": None if tf_step is None else round(
                            tf_step * args.ddpm_steps * args.batch * world * args.steps / dt, 1)},
-            "roofline": roofline_of(summ, f"r02_{args.workload}_pmc_traffic.json"), "cpu_baseline": None}
+            "roofline": None if summ is None else roofline_of(summ, f"r02_{args.workload}_pmc_traffic.json"), "cpu_baseline": None}
     print(json.dumps(line), flush=True)
 
 
@@ -926,18 +965,22 @@ def bench_stage1(args, dev, rank, world):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_pass()
+        out = one_pass()
     barrier(world)
     dt = dist_max([time.perf_counter() - t0], dev, world)[0]
     if rank != 0:
         return
-    prof = ops.LaunchProfiler()
-    ops.set_profiler(prof)
-    saved, net.use_graph = net.use_graph, False
-    one_pass(gather=False)   # rank 0 only: no collective in here, the other ranks have moved on
-    torch.cuda.synchronize()
-    net.use_graph = saved
-    ops.set_profiler(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"images": out})     # the uint8 images of every rank (after the all-gather)
+    prof = None
+    if args.full:          # the roofline's instrumented pass
+        prof = ops.LaunchProfiler()
+        ops.set_profiler(prof)
+        saved, net.use_graph = net.use_graph, False
+        one_pass(gather=False)   # rank 0 only: no collective in here, the other ranks have moved on
+        torch.cuda.synchronize()
+        net.use_graph = saved
+        ops.set_profiler(None)
     step_tf = S1_TF_PER_IMAGE_STEP.get(side)
     line = {"metric": f"Stage-1 (SR3) {args.lr_side}->{side} x{args.scale} images/sec @{T} steps (BASELINE configs[1], secondary workload)",
             "value": round(args.batch * world * args.steps / dt, 4), "unit": "img/s", "n_gpus": world, "steps": args.steps,
@@ -948,8 +991,8 @@ def bench_stage1(args, dev, rank, world):
                        "global_batch": args.batch * world, "parallelism": f"dp{world}", "hipgraph": bool(net.use_graph),
                        "algorithmic_tflops_whole_step": None if step_tf is None else round(
                            step_tf * T * args.batch * world * args.steps / dt, 2)},
-            "roofline": roofline_of(prof.summary(), "r01_c2_pmc_traffic.json")}
-    if not args.no_cpu_baseline and world == 1:
+            "roofline": None if prof is None else roofline_of(prof.summary(), "r01_c2_pmc_traffic.json")}
+    if args.full and not args.no_cpu_baseline and world == 1:
         dt1, thr, sweep = cpu_baseline_s1(side, T)
         line["cpu_baseline"] = {"value": 1.0 / (dt1 * T), "unit": "img/s", "cores": thr, "kind": "port",
                                 "sample": f"2 ancestral steps of 1 image at {side}x{side} on the fp32 CPU oracle ({dt1:.2f} s/step, "
@@ -992,9 +1035,15 @@ def main():
     ap.add_argument("--s2-side", type=int, default=1024)
     ap.add_argument("--s2-threshold", type=float, default=None, help="feature-cache threshold (headline: 0 = off; c3/s2: 0.3)")
     ap.add_argument("--tile-vae", action="store_true", help="s2: VAEHook tiling (needed from 2048x2048 up)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="c4: skip the cache-on pass, the 50-step tolerance check and the reference-GPU-policy pass")
-    ap.add_argument("--no-whole-image", action="store_true", help="c4: skip the executed whole image (all 50 + 50 iterations, ~76 s) printed beside the projection")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: roofline / per-kernel "
+                                                         "passes, cpu_baseline, and on c4 the cache-on pass, the 50-step tolerance check, the "
+                                                         "reference-GPU-policy pass, the executed whole image and the data-parallel self-check "
+                                                         "(default: off, a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned as "
+                                                                          "DIR/<name>.npy (float32; arrays over 4 M elements as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="c4 --full: skip the cache-on pass, the 50-step tolerance check and the reference-GPU-policy pass")
+    ap.add_argument("--no-whole-image", action="store_true", help="c4 --full: skip the executed whole image (all 50 + 50 iterations, ~76 s) printed beside the projection")
     ap.add_argument("--cached-cond", action="store_true", help="c4 / c4full: cached text embeddings (PreparedConditioner) and no "
                                                                 "caption pass, as rounds 1-2 measured (default: live LLaVA-NeXT "
                                                                 "caption + live text towers, BASELINE configs[3])")
@@ -1034,8 +1083,6 @@ def main():
         args.batch = {"c2": 4, "c3": 8}.get(args.workload, 1)
     if args.s2_threshold is None:
         args.s2_threshold = 0.0 if headline else 0.3
-    if args.workload == "c4" and max(args.steps, args.warmup) > args.ddpm_steps:
-        raise SystemExit("--steps / --warmup must not exceed --ddpm-steps on the per-iteration workload")
 
     from rsvld_amd import devtools, ops, parallel
     if args.dev_env:

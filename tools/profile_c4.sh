@@ -13,7 +13,7 @@ tag=${tag}_c4${sfx}
 R=$(pwd)
 export TMPDIR=/tmp
 out=$R/gpurun_out
-rocprofv3 --kernel-trace --stats -d $out/${tag}_stats -o c4 --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras $extra > $out/${tag}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/${tag}_stats -o c4 --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras $extra > $out/${tag}_stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE "SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   n=$(echo $c | cut -d' ' -f1)
   # (--cached-cond: the counter passes serialise every dispatch, and the caption pass alone is ~200 k small PyTorch kernels;
