@@ -131,7 +131,13 @@ typedef struct rsvld_conv_desc {
  *     w     : [Cout][9][ fp16(w) (Ctot) | Ctot / 32 blocks likewise ], P0 = e4m3(w 2^6), P1 = e4m3((w - fp16 w) 2^18)   (rsvld_pack_weight_hq8)
  * (the 16-byte interleave lets the kernel read a block with the fragment addresses of its fp16 k-steps: lane half h gets all of P_h)
  * out fp32 (out_f32 must be 1), residual fp32, epilogue statistics as for RSVLD_SPLIT.  Measured at full network depth over 50 steps the
- * distance from the fp32 family is that of RSVLD_SPLIT (+3.5 % in the mean, profiles/r06_conv_lo8_emulation.txt). */
+ * distance from the fp32 family is that of RSVLD_SPLIT (+3.5 % in the mean, profiles/r06_conv_lo8_emulation.txt).
+ * Range: the ~22 bits hold for activations below |x| = 64.  Every writer clamps to the e4m3 range +-448 (no inf, no NaN out of a finite x):
+ *   P0 = e4m3((x - fp16 x) 2^14) saturates once |x - fp16 x| > 448 2^-14 ~ 0.027, i.e. from |x| = 64 on (half an fp16 ulp is 2^-5 there);
+ *   P1 = e4m3(x 2^2) saturates above |x| = 112 (the x_hi w_lo term then takes +-112).
+ * Beyond 64 the clamped x_lo loses at most |x - fp16 x| -- no more than the fp16-input form (RSVLD_F16W2) drops for the same element --
+ * and beyond 112 the x_hi w_lo term is short by (|x| - 112) |w - fp16 w|.  GroupNorm + SiLU outputs of the UNets sit far below both limits;
+ * tests/test_gpu_policy_routes.py pins the device's clamping to this model at |x| up to a few hundred. */
 #define RSVLD_HQ8_SX_LO 14
 #define RSVLD_HQ8_SX_HI 2
 #define RSVLD_HQ8_SW_HI 6

@@ -170,8 +170,11 @@ class SplitPolicy:
                     (2^-11 of the product) contracted in e4m3 on the block-scaled matrix instruction (dtype RSVLD_F16Q8: per 32 channels and tap
                     two fp16 MFMAs + one scaled MFMA instead of six bf16 MFMAs).  Emulated at full depth over 50 steps before the kernel was
                     written: mean distance from the fp32 family +3.5 %, maxima 5.8e-4 / 5.1e-4, every cache decision unchanged
-                    (profiles/r06_conv_lo8_emulation.txt).  Default: both groups in the shipped composition, none elsewhere (the VAE: real
-                    SDXL-VAE activations leave the fp16 range)."""
+                    (profiles/r06_conv_lo8_emulation.txt).  Default (``None``): in the product path with the four transformer groups of the
+                    shipped composition ("attn", "attn_out", "ff", "qkv") in ``f16_inputs``, every group of ``Q8_GROUPS`` that ``f16_inputs``
+                    does not already round to fp16 -- both in the shipped composition; none elsewhere (the VAE: real SDXL-VAE activations
+                    leave the fp16 range).  An explicit ``q8_convs`` that names a group of ``f16_inputs`` is an error.
+                    Range: the e4m3 cross terms saturate (include/rsvld_hip.h, RSVLD_HQ8_SX_*): x_lo from |x| ~ 64, x_hi above |x| = 112."""
 
     __slots__ = ("impl", "f16_inputs", "f16_weights", "q8_convs")
     GROUPS = ("attn", "attn_out", "ff", "qkv", "proj", "conv1", "conv2")
@@ -179,8 +182,9 @@ class SplitPolicy:
     Q8_GROUPS = ("conv1", "conv2")
 
     def __init__(self, impl="planes", f16_inputs=("attn", "attn_out", "ff", "qkv"), f16_weights=None, q8_convs=None):
-        if q8_convs is None:        # the default: both ResBlock convolutions, in the shipped composition of the UNets only
-            q8_convs = self.Q8_GROUPS if (impl == "planes" and {"attn", "attn_out", "ff", "qkv"} <= set(f16_inputs)) else ()
+        if q8_convs is None:        # the default: the ResBlock convolutions not rounded to fp16, in the shipped composition of the UNets only
+            q8_convs = (tuple(g for g in self.Q8_GROUPS if g not in f16_inputs)
+                        if (impl == "planes" and {"attn", "attn_out", "ff", "qkv"} <= set(f16_inputs)) else ())
         bad = [g for g in q8_convs if g not in self.Q8_GROUPS]
         if bad:
             raise ValueError(f"SplitPolicy.q8_convs {bad}: one of {self.Q8_GROUPS}")
@@ -735,9 +739,25 @@ def _q8_conv_eligible(B, H, W, Cc, pc, stride, pad, upsample, act, out_planes):
     return ctx.use_halo and Bp * ((H + 7) // 8) * ((W + 31) // 32) * ((pc.cout_p + 127) // 128) >= ctx.split_halo_min_wgs
 
 
+def _q8_conv_desc(B, H, W, Cc, pc, *, stride=1, pad=1, upsample=False, act=L.ACT_NONE, out_planes=False, x=None, w=None, rowvec=None,
+                  residual=None, out=None, alpha=1.0, beta=1.0, rowvec_stride=0):
+    """The rsvld_conv_desc of ``pc`` on a ``[B, H, W, Cc]`` input as RSVLD_F16Q8 (absent tensors: null pointers).  ``_conv2d_q8`` launches
+    it; with the geometry of any layer ``_q8_conv_eligible`` is asked about, it is what rsvld_conv3x3_halo_supported must accept."""
+    ctx = _CTX.get()
+    if pad is None:
+        pad = pc.kh // 2
+    pt, pl, pb, pr = (pad,) * 4 if isinstance(pad, int) else pad
+    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return L.ConvDesc(
+        x=ptr(x), x2=None, w=ptr(w), bias=ptr(pc.bias), rowvec=ptr(rowvec), residual=ptr(residual), out=ptr(out),
+        B=B, H=H, W=W, Cin=Cc, Cin2=0, Cout=pc.cout_p, KH=pc.kh, KW=pc.kw, stride=stride, pad_t=pt, pad_l=pl,
+        Ho=(Hin + pt + pb - pc.kh) // stride + 1, Wo=(Win + pl + pr - pc.kw) // stride + 1, upsample=int(upsample), dtype=L.F16Q8,
+        out_f32=int(not out_planes), act=act, alpha=alpha, beta=beta, rowvec_stride=rowvec_stride, plan_div=ctx.plan_div, tune=ctx.tune)
+
+
 def _conv2d_q8(xq, pc, *, rowvec, residual, alpha, beta, stats):
     """3x3 / stride 1 / pad 1 on Q8Rows: fp32 out (+ fp32 residual), epilogue statistics for the next GroupNorm."""
-    ctx = _CTX.get()
     B, H, W, Cc = xq.shape
     if Cc != pc.cin_p:
         raise L.RsvldError(f"conv2d (q8): input channels {Cc} != packed {pc.cin_p}")
@@ -750,12 +770,8 @@ def _conv2d_q8(xq, pc, *, rowvec, residual, alpha, beta, stats):
         if tuple(rowvec.shape) != (B, pc.cout_p) or rowvec.dtype != torch.float32 or rowvec.stride(1) != 1:
             raise L.RsvldError("conv2d: rowvec must be fp32 [B, Cout] with unit inner stride")
         rv_stride = rowvec.stride(0) if B > 1 else pc.cout_p
-    wq = _wq8(pc)
-    d = L.ConvDesc(
-        x=xq.t.data_ptr(), x2=None, w=wq.data_ptr(), bias=None if pc.bias is None else pc.bias.data_ptr(),
-        rowvec=None if rowvec is None else rowvec.data_ptr(), residual=None if residual is None else residual.data_ptr(), out=out.data_ptr(),
-        B=B, H=H, W=W, Cin=Cc, Cin2=0, Cout=pc.cout_p, KH=3, KW=3, stride=1, pad_t=1, pad_l=1, Ho=H, Wo=W, upsample=0,
-        dtype=L.F16Q8, out_f32=1, act=L.ACT_NONE, alpha=alpha, beta=beta, rowvec_stride=rv_stride, plan_div=ctx.plan_div, tune=ctx.tune)
+    d = _q8_conv_desc(B, H, W, Cc, pc, x=xq.t, w=_wq8(pc), rowvec=rowvec, residual=residual, out=out, alpha=alpha, beta=beta,
+                      rowvec_stride=rv_stride)
     lib = L.load()
     if not lib.rsvld_conv3x3_halo_supported(C.byref(d)):
         raise L.RsvldError("conv2d (q8): shape not supported by the halo kernel (checked by _q8_conv_eligible)")

@@ -74,30 +74,37 @@ def errors_after_50_steps(dev, sr3_prec, ae, diff, policy=None, sr3_policy=None)
                 "reference": "tests/golden/sr3_pipeline_t50.npz, s2_pipeline_50.npz (the reference's own CPU runs)"}
 
 
+def modes():
+    """name -> (SR3 precision, VAE, UNets, UNet policy, SR3 policy); split = the mode as shipped.  Every policy is built here, whichever
+    ``--only`` selects (tests/test_split_policy.py builds the whole table on the host)."""
+    from rsvld_amd import ops
+    P = ops.SplitPolicy
+    return {"shipped": ("fp16", "bf16", "fp16", None, None), "vae_split": ("fp16", "split", "fp16", None, None),
+            "split": ("split", "split", "split", None, None),
+            "split_s1w2": ("w2", "split", "split", None, None),                            # Stage 1: fp16 tensors x weight pairs
+            "split_r04": ("split", "split", "split", P(f16_inputs=("attn",)), P(f16_inputs=("attn",))),   # round 4's composition
+            "split_noqkv": ("split", "split", "split", P(f16_inputs=("attn", "attn_out", "ff"), f16_weights=()), None),
+            # round 5's three-MFMA ResBlock convolutions (no e4m3 cross terms)
+            "split_noconv": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv"), f16_weights=(), q8_convs=()), None),
+            "split_conv": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "conv1", "conv2"), f16_weights=()), None),
+            # conv2's input in fp16; conv1 keeps the default's e4m3 cross terms
+            "split_conv2": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "conv2"), f16_weights=()), None),
+            "split_proj": ("split", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "proj"), f16_weights=()), None),
+            "split_pairs": ("w2", "split", "split", P(f16_weights=()), None),                 # every weight of the fp16-input GEMMs as a pair (two MFMAs)
+            "split_w1_qkv": ("w2", "split", "split", P(f16_weights=("qkv",)), None),          # to_q / to_k / to_v weights rounded to fp16 (one MFMA)
+            "split_w1_geglu": ("w2", "split", "split", P(f16_weights=("geglu",)), None),      # the GEGLU projection's
+            "split_w1_all": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "attn_out", "ff_out")), None),   # + to_out and ff.net.2 (RSVLD_F16W1)
+            "split_w1_ao": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "attn_out")), None),
+            "split_w1_fo": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "ff_out")), None),
+            "split_noq8": ("w2", "split", "split", P(q8_convs=()), None),   # round 5's composition: the ResBlock convolutions as three bf16 MFMAs
+            "split_full": ("split", "split", "split", ops.ALL_SPLIT, ops.ALL_SPLIT)}
+
+
 if __name__ == "__main__":
     import json
     dev = torch.device("cuda:0")
-    from rsvld_amd import ops
-    P = ops.SplitPolicy
-    # name -> (SR3 precision, VAE, UNets, UNet policy, SR3 policy); split = the mode as shipped
-    modes = {"shipped": ("fp16", "bf16", "fp16", None, None), "vae_split": ("fp16", "split", "fp16", None, None),
-             "split": ("split", "split", "split", None, None),
-             "split_s1w2": ("w2", "split", "split", None, None),                            # Stage 1: fp16 tensors x weight pairs
-             "split_r04": ("split", "split", "split", P(f16_inputs=("attn",)), P(f16_inputs=("attn",))),   # round 4's composition
-             "split_noqkv": ("split", "split", "split", P(f16_inputs=("attn", "attn_out", "ff"), f16_weights=()), None),
-             "split_noconv": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv"), f16_weights=()), None),
-             "split_conv": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "conv1", "conv2"), f16_weights=()), None),
-             "split_conv2": ("w2", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "conv2"), f16_weights=()), None),
-             "split_proj": ("split", "split", "split", P(f16_inputs=("attn", "attn_out", "ff", "qkv", "proj"), f16_weights=()), None),
-             "split_pairs": ("w2", "split", "split", P(f16_weights=()), None),                 # every weight of the fp16-input GEMMs as a pair (two MFMAs)
-             "split_w1_qkv": ("w2", "split", "split", P(f16_weights=("qkv",)), None),          # to_q / to_k / to_v weights rounded to fp16 (one MFMA)
-             "split_w1_geglu": ("w2", "split", "split", P(f16_weights=("geglu",)), None),      # the GEGLU projection's
-             "split_w1_all": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "attn_out", "ff_out")), None),   # + to_out and ff.net.2 (RSVLD_F16W1)
-             "split_w1_ao": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "attn_out")), None),
-             "split_w1_fo": ("w2", "split", "split", P(f16_weights=("qkv", "geglu", "ff_out")), None),
-             "split_noq8": ("w2", "split", "split", P(q8_convs=()), None),   # round 5's composition: the ResBlock convolutions as three bf16 MFMAs
-             "split_full": ("split", "split", "split", ops.ALL_SPLIT, ops.ALL_SPLIT)}
+    table = modes()
     if "--only" in sys.argv:
-        modes = {k: v for k, v in modes.items() if k in sys.argv[sys.argv.index("--only") + 1].split(",")}
-    for name, (s1, ae, df, pol, pol1) in modes.items():
+        table = {k: v for k, v in table.items() if k in sys.argv[sys.argv.index("--only") + 1].split(",")}
+    for name, (s1, ae, df, pol, pol1) in table.items():
         print(name, json.dumps(errors_after_50_steps(dev, s1, ae, df, policy=pol, sr3_policy=pol1)), flush=True)
