@@ -31,6 +31,11 @@ class RsvldError(RuntimeError):
     pass
 
 
+class RsvldOperandError(RsvldError, ValueError):
+    """An operand a public wrapper (ops.py) would hand to a kernel breaks its contract -- dtype, layout or shape --
+    raised before anything is allocated or launched, and before the GPU-only check."""
+
+
 class ConvDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x2", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p),

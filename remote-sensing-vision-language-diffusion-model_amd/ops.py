@@ -46,6 +46,52 @@ def pad8(c):
     return (c + 7) // 8 * 8
 
 
+# ----------------------------------------------------------------------------- operand contracts
+# The C ABI takes raw pointers and sizes read off ONE operand, so a wrong operand would give plausible numbers or an access past
+# another operand's allocation.  Every public wrapper therefore checks each operand -- dtype, the layout the kernel reads, shape
+# agreement -- before it allocates, launches or asks for the GPU (checked before ``_need_gpu``: a CPU or meta tensor exercises the
+# contract, tests/test_ops_contracts.py) and raises ``RsvldOperandError`` naming the wrapper and the operand.
+_HALF = (torch.float16, torch.bfloat16)
+_ACT = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def _bad(fn, name, what):
+    raise L.RsvldOperandError(f"{fn}: operand '{name}' {what}")
+
+
+def _arg(fn, name, t, dtype=None, shape=None, numel=None, layout="contiguous", optional=False):
+    """Contract of operand ``name`` of wrapper ``fn``.  ``dtype``: one dtype or a tuple of the allowed ones; ``shape``: the exact shape
+    (``None`` entries: any extent); ``layout``: "contiguous" (the kernel walks the storage densely), "rows" (unit inner stride, every
+    other stride and the offset whole 16-byte units: the token-stride / channel-slice views whose strides the wrapper passes on) or
+    None (the wrapper makes its own copy)."""
+    if t is None:
+        if optional:
+            return None
+        _bad(fn, name, "is required")
+    if not isinstance(t, torch.Tensor):
+        _bad(fn, name, f"must be a tensor, got {type(t).__name__}")
+    if dtype is not None and t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+        _bad(fn, name, f"has dtype {t.dtype}, expected {dtype}")
+    if shape is not None and (t.dim() != len(shape) or any(s is not None and s != n for s, n in zip(shape, t.shape))):
+        _bad(fn, name, f"has shape {tuple(t.shape)}, expected {tuple('*' if s is None else s for s in shape)}")
+    if numel is not None and t.numel() != numel:
+        _bad(fn, name, f"has {t.numel()} elements, expected {numel}")
+    if layout == "contiguous" and not t.is_contiguous():
+        _bad(fn, name, f"must be contiguous, got strides {tuple(t.stride())}")
+    if layout == "rows" and t.dim():
+        vec = max(1, 16 // t.element_size())
+        if (t.stride(-1) != 1 and t.shape[-1] > 1) or t.storage_offset() % vec or any(
+                s % vec for s, n in zip(t.stride()[:-1], t.shape[:-1]) if n > 1):
+            _bad(fn, name, f"must have unit inner stride and 16-byte rows, got strides {tuple(t.stride())} "
+                           f"at offset {t.storage_offset()}")
+    return t
+
+
+def _same(fn, name, t, ref, optional=False):
+    """Operand ``name`` is an activation of ``ref``'s dtype and shape, contiguous."""
+    return _arg(fn, name, t, ref.dtype, shape=tuple(ref.shape), optional=optional)
+
+
 # ----------------------------------------------------------------------------- launch context
 # Everything a launch reads BESIDES its arguments lives in ONE immutable ``LaunchContext`` held in a ``contextvars.ContextVar``:
 # the launch-plan divisor, the precision policy of the network that is running, the developer A/B overrides and the profiler.
@@ -361,9 +407,10 @@ def to_planes(x):
     """fp32 ``[..., C]`` (C % 8 == 0, contiguous) -> Planes (rsvld_split_planes); a Planes passes through."""
     if isinstance(x, Planes):
         return x
+    _arg("to_planes", "x", x, torch.float32)
+    if x.dim() < 1 or x.shape[-1] % 8:
+        _bad("to_planes", "x", f"needs C % 8 == 0, got shape {tuple(x.shape)}")
     _need_gpu(x)
-    if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[-1] % 8:
-        raise L.RsvldError("to_planes: a contiguous fp32 tensor with C % 8 == 0 expected")
     Cc = x.shape[-1]
     t = torch.empty(tuple(x.shape[:-1]) + (2, Cc), device=x.device, dtype=torch.bfloat16)
     _launch("split_planes", 0.0, 8.0 * x.numel(), lambda: L.check(L.load().rsvld_split_planes(_ptr(x), _ptr(t), x.numel() // Cc, Cc, _stream()),
@@ -502,6 +549,7 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
     fp16 ``x`` with weights packed in fp32 (a network in the split precision whose policy rounds this layer's input to fp16, or SR3's
     compute dtype "w2"): dtype RSVLD_F16W2, fp16 activation x fp16 weight pair [W_lo | W_hi], two MFMAs per product; in a
     split-precision network the output is fp32 (+ fp32 residual) unless ``out_planes`` asks for the fp16 hand-over."""
+    _conv_operands("conv2d", x, pc, x2, stride, pad, upsample, rowvec, residual, out_f32, act, norm, out_planes)
     _need_gpu(x, x2, pc.w, rowvec, residual)
     ctx = _CTX.get()
     if isinstance(x, Planes) or (x.dtype == torch.float32 and _split_fast()):
@@ -628,6 +676,50 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
     return out
 
 
+def _conv_operands(fn, x, pc, x2, stride, pad, upsample, rowvec, residual, out_f32, act, norm, out_planes):
+    """The contract of every operand of conv2d / linear: NHWC ``x`` (16-bit, fp32 or contiguous planes) and ``x2`` of the same kind and
+    pixels, weights packed in ``x``'s type (or fp32: the weight-pair form under fp16, the fp32 / split families), fp32 bias and norm
+    affine of the layer's channels, fp32 ``rowvec [B, Cout]`` with unit inner stride, ``residual`` of the output's shape and type."""
+    if isinstance(x, Planes):
+        _arg(fn, "x", x.t, torch.bfloat16, shape=(None,) * 3 + (2, None))
+    else:
+        _arg(fn, "x", x, _ACT, shape=(None,) * 4)
+    f32 = isinstance(x, Planes) or x.dtype == torch.float32
+    B, H, W, Cin = x.shape
+    Cin2 = 0
+    if isinstance(x2, Planes):
+        if not f32:
+            _bad(fn, "x2", "is planes under a 16-bit x")
+        _arg(fn, "x2", x2.t, torch.bfloat16, shape=(B, H, W, 2, None))
+    elif x2 is not None:
+        _arg(fn, "x2", x2, torch.float32 if f32 else x.dtype, shape=(B, H, W, None))
+    if x2 is not None:
+        Cin2 = x2.shape[-1]
+    wdt = torch.float32 if f32 else ((torch.float16, torch.float32) if x.dtype == torch.float16 else x.dtype)
+    _arg(fn, "pc.w", pc.w, wdt, shape=(pc.cout_p, pc.kh * pc.kw * pc.cin_p))
+    _arg(fn, "pc.bias", pc.bias, torch.float32, shape=(pc.cout_p,), optional=True)
+    if Cin + Cin2 != pc.cin_p:
+        _bad(fn, "x", f"has {Cin}+{Cin2} channels, the packed weights {pc.cin_p}")
+    if norm is not None:
+        _arg(fn, "norm gamma", norm[0], torch.float32, shape=(Cin + Cin2,), optional=True)
+        _arg(fn, "norm beta", norm[1], torch.float32, shape=(Cin + Cin2,), optional=True)
+    _arg(fn, "rowvec", rowvec, torch.float32, shape=(B, pc.cout_p), layout=None, optional=True)
+    if rowvec is not None and rowvec.stride(1) != 1:
+        _bad(fn, "rowvec", f"must have unit inner stride, got strides {tuple(rowvec.stride())}")
+    if residual is not None:
+        pt, pl, pb, pr = (pc.kh // 2 if pad is None else pad,) * 4 if not isinstance(pad, (tuple, list)) else pad
+        Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
+        shape = (B, (Hin + pt + pb - pc.kh) // stride + 1, (Win + pl + pr - pc.kw) // stride + 1,
+                 pc.cout_p // 2 if act == L.ACT_GEGLU else pc.cout_p)
+        if f32:
+            rdt = torch.float32
+        elif pc.w.dtype == torch.float32 and _split_fast():   # the weight-pair form in a split-precision network
+            rdt = torch.float16 if out_planes else torch.float32
+        else:
+            rdt = torch.float32 if out_f32 else x.dtype
+        _arg(fn, "residual", residual, rdt, shape=shape)
+
+
 def _conv2d_f32(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, alpha, beta, norm):
     """fp32 NHWC convolution with fp32 packed weights (rsvld_conv2d_nhwc_f32); a ``norm=`` GroupNorm runs first, unfused."""
     if pc.w.dtype != torch.float32:
@@ -718,10 +810,11 @@ def _wq8(pc):
 
 def to_q8rows(x):
     """fp32 ``[..., C]`` (C % 32 == 0, contiguous) -> Q8Rows (rsvld_split_hq8): the activation format of RSVLD_F16Q8."""
+    _arg("to_q8rows", "x", x, torch.float32)
+    if x.dim() < 1 or x.shape[-1] % 32:
+        _bad("to_q8rows", "x", f"needs a multiple of 32 channels, got shape {tuple(x.shape)}")
     _need_gpu(x)
     Cc = x.shape[-1]
-    if x.dtype != torch.float32 or not x.is_contiguous() or Cc % 32:
-        raise L.RsvldError("to_q8rows: contiguous fp32 with a multiple of 32 channels expected")
     t = torch.empty(tuple(x.shape[:-1]) + (2, Cc), device=x.device, dtype=torch.float16)
     _launch("split_q8", 0.0, 8.0 * x.numel(), lambda: L.check(L.load().rsvld_split_hq8(_ptr(x), _ptr(t), x.numel() // Cc, Cc, _stream()),
                                                             "rsvld_split_hq8"))
@@ -953,6 +1046,14 @@ def _conv2d_split(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, al
 def linear(x, pc, *, residual=None, act=L.ACT_NONE, alpha=1.0, beta=1.0, out_planes=False, out_group=None, group=None):
     """``[..., Cin] -> [..., Cout]`` on token-major tensors (a 1x1 conv over rows).  ``group``: the layer's weight group
     (``SplitPolicy.f16_weights``) where the consumer of its output does not name it."""
+    # (contiguous rows: the reshapes below must be views -- a copy made here would hide a caller's layout mistake)
+    if isinstance(x, Planes):
+        _arg("linear", "x", x.t, torch.bfloat16)
+    else:
+        _arg("linear", "x", x, _ACT)
+    if x.dim() < 1 or x.shape[-1] == 0:
+        _bad("linear", "x", f"needs a channel dimension, got shape {tuple(x.shape)}")
+    _arg("linear", "residual", residual, shape=tuple(x.shape[:-1]) + (None,), optional=True)
     shp = x.shape
     rows = x.numel() // shp[-1]
     res = None if residual is None else residual.reshape(1, 1, rows, residual.shape[-1])
@@ -962,11 +1063,46 @@ def linear(x, pc, *, residual=None, act=L.ACT_NONE, alpha=1.0, beta=1.0, out_pla
 
 
 # ----------------------------------------------------------------------------- norms
+def _gn_operands(fn, x, x2, gamma, beta, stats=None, groups=None):
+    """GroupNorm family: NHWC ``x`` (16-bit or fp32, contiguous), ``x2`` of its type and pixels, fp32 gamma / beta of C1 + C2
+    channels, fp32 statistics ``[B, groups, 2]``."""
+    _arg(fn, "x", x, _ACT, shape=(None,) * 4)
+    _arg(fn, "x2", x2, x.dtype, shape=tuple(x.shape[:3]) + (None,), optional=True)
+    Cc = x.shape[3] + (0 if x2 is None else x2.shape[3])
+    _arg(fn, "gamma", gamma, torch.float32, shape=(Cc,), optional=True)
+    _arg(fn, "beta", beta, torch.float32, shape=(Cc,), optional=True)
+    if stats is not None or groups is not None:
+        _arg(fn, "stats", stats, torch.float32, shape=(x.shape[0], groups, 2))
+
+
+def _mod_operands(fn, x, x2, mod_scale1p, mod_shift, planes_ok=False):
+    """ZeroSFT modulation: both or neither; of ``x``'s type and ``[B, H, W, C1 + C2]`` shape, channel slices of one stacked tensor
+    (pixel-major rows of one stride, 16-byte aligned); planes where the split precision converts them."""
+    if (mod_scale1p is None) != (mod_shift is None):
+        _bad(fn, "mod_shift" if mod_shift is None else "mod_scale1p", "comes without its partner")
+    if mod_scale1p is None:
+        return
+    B, H, W = x.shape[:3]
+    Cc = x.shape[3] + (0 if x2 is None else x2.shape[3])
+    for name, m in (("mod_scale1p", mod_scale1p), ("mod_shift", mod_shift)):
+        if isinstance(m, Planes) and planes_ok:      # merged to a contiguous fp32 tensor first
+            _arg(fn, name, m.t, torch.bfloat16, shape=(B, H, W, 2, Cc), layout=None)
+            continue
+        _arg(fn, name, m, x.dtype, shape=(B, H, W, Cc), layout="rows")
+        ms = m.stride(2)
+        if any(s != e for s, e, n in zip(m.stride(), (H * W * ms, W * ms, ms, 1), m.shape) if n > 1):
+            _bad(fn, name, f"must be pixel-major rows of one stride, got strides {tuple(m.stride())}")
+    if not isinstance(mod_scale1p, Planes) and not isinstance(mod_shift, Planes) and mod_scale1p.stride(2) != mod_shift.stride(2):
+        _bad(fn, "mod_shift", "must share mod_scale1p's row stride")
+
+
 def group_norm(x, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=None, mod_shift=None, planes=False, group=None):
     """GroupNorm(+SiLU) over NHWC ``x`` (or the channel concat [x | x2]).  ``mod_scale1p`` / ``mod_shift``
     (ZeroSFT) may be channel slices of one stacked tensor: only their row stride must agree.
     ``planes=True`` (split precision only, ignored otherwise): the result only feeds a matrix product -> ``Planes``, or fp16 when
     the policy hands the inputs of that product's layer group ``group`` over in fp16."""
+    _gn_operands("group_norm", x, x2, gamma, beta)
+    _mod_operands("group_norm", x, x2, mod_scale1p, mod_shift, planes_ok=x.dtype == torch.float32 and _split_fast())
     if x.dtype == torch.float32 and _split_fast() and not isinstance(x, Planes):
         _need_gpu(x, x2, gamma, beta)
         ab = _gn_scale_shift_f32(x, x2, gamma, beta, groups, eps)
@@ -998,6 +1134,7 @@ def group_norm(x, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=
 
 def group_norm_stats(x, groups, *, x2=None):
     """-> fp32 ``[B, groups, 2]`` (mean, biased variance)."""
+    _gn_operands("group_norm_stats", x, x2, None, None)
     _need_gpu(x, x2)
     B, H, W, C1 = x.shape
     C2 = 0 if x2 is None else x2.shape[-1]
@@ -1029,6 +1166,8 @@ def group_norm_stats(x, groups, *, x2=None):
 def group_norm_apply(x, stats, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=None, mod_shift=None, planes=False):
     """``mod_*`` (ZeroSFT modulation) with supplied statistics exists in the fp32 family only.
     ``planes=True`` (split precision only): the result only feeds a matrix product -> ``Planes``."""
+    _gn_operands("group_norm_apply", x, x2, gamma, beta, stats=stats, groups=groups)
+    _mod_operands("group_norm_apply", x, x2, mod_scale1p, mod_shift)
     _need_gpu(x, x2, stats, gamma, beta)
     if x.dtype == torch.float32 and _split_fast() and not isinstance(x, Planes):
         B, H, W, C1 = x.shape
@@ -1065,8 +1204,13 @@ def group_norm_apply(x, stats, gamma, beta, groups, eps, *, x2=None, silu=False,
 def layer_norm(x, gamma, beta, eps=1e-5, planes=False, group=None):
     """``planes=True`` (split precision only, ignored otherwise): the result only feeds matrix products -> ``Planes``, or fp16 when
     the policy hands the inputs of those products' layer group ``group`` over in fp16."""
-    _need_gpu(x, gamma, beta)
+    _arg("layer_norm", "x", x, _ACT)
+    if x.dim() < 1 or x.numel() == 0:
+        _bad("layer_norm", "x", f"needs rows of channels, got shape {tuple(x.shape)}")
     Cc = x.shape[-1]
+    _arg("layer_norm", "gamma", gamma, torch.float32, shape=(Cc,), optional=True)
+    _arg("layer_norm", "beta", beta, torch.float32, shape=(Cc,), optional=True)
+    _need_gpu(x, gamma, beta)
     rows = x.numel() // Cc
     if x.dtype == torch.float32 and _split_fast():
         if not x.is_contiguous():
@@ -1102,7 +1246,19 @@ def attention(q, k, v, heads, scale=None):
     as fp16 x weight pairs) and planes otherwise.  Without "attn" (the VAE's policy: its single-head attentions are a rounding error
     of the image's time and a third of the mode's Stage-2 distance from the reference when run in fp16, 4.4e-4 -> 3.0e-4 max after
     50 steps) the fused split kernels run on planes."""
-    if any(isinstance(t, Planes) for t in (q, k, v)) or (q.dtype == torch.float32 and _split_fast()):
+    split = any(isinstance(t, Planes) for t in (q, k, v)) or (q.dtype == torch.float32 and _split_fast())
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if isinstance(t, Planes):
+            _arg("attention", name, t.t, torch.bfloat16, shape=(None, None, 2, None), layout=None)
+        else:   # token-stride views (slices of a fused q | k | v) are read in place: rows, not contiguity
+            _arg("attention", name, t, (torch.float32, torch.float16) if split else (_ACT if t is q else q.dtype), shape=(None,) * 3,
+                 layout="rows")
+    if heads <= 0 or q.shape[2] % heads:
+        _bad("attention", "q", f"has {q.shape[2]} channels, not a multiple of heads = {heads}")
+    for name, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != (q.shape[0], k.shape[1], q.shape[2]):
+            _bad("attention", name, f"has shape {tuple(t.shape)}, expected [B, Nk, H*D] = {(q.shape[0], k.shape[1], q.shape[2])}")
+    if split:
         return _attention_split(q, k, v, heads, scale)
     _need_gpu(q, k, v)
     B, Nq, HD = q.shape
@@ -1263,12 +1419,11 @@ def _attention_split_kernels(q, k, v, heads, scale):
 def gemv(w, x, bias=None):
     """``w [N, K]`` (16-bit, rows contiguous) times ONE activation row ``x [K]`` (+ ``bias [N]``) -> ``[N]``: the weight-streaming
     products of the caption pass's token loop (rsvld_gemv; HBM-bound, no tile, no MFMA)."""
-    _need_gpu(w, x, bias)
+    _arg("gemv", "w", w, _HALF, shape=(None, None))
     N, K = w.shape
-    if x.numel() != K or w.stride(1) != 1 or w.stride(0) != K or not x.is_contiguous():
-        raise L.RsvldError("gemv: w must be a contiguous [N, K] matrix and x a contiguous row of K elements")
-    if x.dtype != w.dtype or (bias is not None and bias.dtype != w.dtype):
-        raise L.RsvldError("gemv: w, x and bias must share one 16-bit dtype")
+    _arg("gemv", "x", x, w.dtype, numel=K)
+    _arg("gemv", "bias", bias, w.dtype, numel=N, optional=True)
+    _need_gpu(w, x, bias)
     y = torch.empty(N, device=w.device, dtype=w.dtype)
     lib = L.load()
     _launch("gemv", 2.0 * N * K, (N * K + K + N) * 2, lambda: L.check(
@@ -1280,16 +1435,14 @@ def gemv_fused(w, x, bias=None, *, norm=None, residual=None, glu=False):
     """``gemv`` with the element-wise neighbours of a Llama decode step folded in (rsvld_gemv_fused): ``norm=(weight, eps)``: the product runs
     on RMSNorm(x) * weight; ``glu``: x holds ``[gate | up]`` (2 K elements) and the product runs on silu(gate) * up; ``residual [N]``: the
     result is residual + (w x + bias)."""
-    _need_gpu(w, x, bias, residual)
+    _arg("gemv_fused", "w", w, _HALF, shape=(None, None))
     N, K = w.shape
-    if x.numel() != (2 * K if glu else K) or w.stride(1) != 1 or w.stride(0) != K or not x.is_contiguous():
-        raise L.RsvldError("gemv_fused: w must be a contiguous [N, K] matrix and x a contiguous row of K (glu: 2 K) elements")
     nw, eps = (None, 0.0) if norm is None else norm
-    for t in (x, bias, nw, residual):
-        if t is not None and t.dtype != w.dtype:
-            raise L.RsvldError("gemv_fused: every operand shares the weights' 16-bit dtype")
-    if residual is not None and (residual.numel() != N or not residual.is_contiguous()):
-        raise L.RsvldError("gemv_fused: residual must be a contiguous row of N elements")
+    _arg("gemv_fused", "x", x, w.dtype, numel=2 * K if glu else K)
+    _arg("gemv_fused", "bias", bias, w.dtype, numel=N, optional=True)
+    _arg("gemv_fused", "norm weight", nw, w.dtype, numel=x.numel(), optional=True)
+    _arg("gemv_fused", "residual", residual, w.dtype, numel=N, optional=True)
+    _need_gpu(w, x, bias, nw, residual)
     y = torch.empty(N, device=w.device, dtype=w.dtype)
     lib = L.load()
     _launch("gemv", 2.0 * N * K, (N * K + K + N) * 2, lambda: L.check(
@@ -1302,13 +1455,22 @@ def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale,
     """One decode step of grouped-query attention over a static cache (rsvld_llama_decode_attention): ``qkv`` = the new token's q | k | v rows,
     ``pos`` a DEVICE int64 scalar; the caches ``[n_kv, max_len, 128]`` are updated at ``pos``; ``ws`` (optional, re-usable): an fp32
     tensor of rsvld_llama_decode_attention_ws_bytes (scratch: no initial state).  A position outside ``[0, max_len)`` is clamped by the kernel.  -> ``[n_q * 128]``."""
-    _need_gpu(qkv, cos, sin, pos, kcache, vcache)
+    fn = "llama_decode_attention"
+    _arg(fn, "kcache", kcache, _HALF, shape=(n_kv, None, None))
     hd, max_len = kcache.shape[-1], kcache.shape[-2]
-    if pos.dtype != torch.int64 or not (kcache.is_contiguous() and vcache.is_contiguous() and qkv.is_contiguous()):
-        raise L.RsvldError("llama_decode_attention: contiguous caches / qkv and an int64 position on the device")
+    _arg(fn, "vcache", vcache, kcache.dtype, shape=tuple(kcache.shape))
+    _arg(fn, "qkv", qkv, kcache.dtype, numel=(n_q + 2 * n_kv) * hd)
+    _arg(fn, "cos", cos, kcache.dtype, numel=hd)
+    _arg(fn, "sin", sin, kcache.dtype, numel=hd)
+    _arg(fn, "pos", pos, torch.int64, numel=1)
+    _arg(fn, "ws", ws, torch.float32, shape=(None,), optional=True)
+    _need_gpu(qkv, cos, sin, pos, kcache, vcache, ws)
     lib = L.load()
+    ws_n = int(lib.rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len)) // 4
     if ws is None:
-        ws = torch.empty(int(lib.rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len)) // 4, device=qkv.device, dtype=torch.float32)
+        ws = torch.empty(ws_n, device=qkv.device, dtype=torch.float32)
+    elif ws.numel() < ws_n:
+        _bad(fn, "ws", f"has {ws.numel()} fp32 elements, the step needs {ws_n}")
     out = torch.empty(n_q * hd, device=qkv.device, dtype=qkv.dtype)
     _launch("llama_decode_attention", 0.0, 0.0, lambda: L.check(
         lib.rsvld_llama_decode_attention(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(ws), n_q, n_kv,
@@ -1319,9 +1481,12 @@ def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale,
 # ----------------------------------------------------------------------------- small fp32 layers
 def linear_small(x, w, b, act_in=0, act_out=0):
     """fp32 ``[rows, in] -> [rows, out]`` with torch nn.Linear weight layout."""
-    _need_gpu(x, w, b)
+    _arg("linear_small", "x", x, torch.float32, shape=(None, None))
     rows, in_f = x.shape
+    _arg("linear_small", "w", w, torch.float32, shape=(None, in_f))
     out_f = w.shape[0]
+    _arg("linear_small", "b", b, torch.float32, shape=(out_f,), optional=True)
+    _need_gpu(x, w, b)
     y = torch.empty((rows, out_f), device=x.device, dtype=torch.float32)
     L.check(L.load().rsvld_linear_small_f32(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, in_f, out_f, act_in, act_out,
                                             _stream()), "rsvld_linear_small_f32")
@@ -1329,6 +1494,9 @@ def linear_small(x, w, b, act_in=0, act_out=0):
 
 
 def sinusoidal(t, dim, kind):
+    # (any real ``t`` of any layout: converted to a contiguous fp32 copy below)
+    if not isinstance(t, torch.Tensor) or t.dtype == torch.bool or t.is_complex():
+        _bad("sinusoidal", "t", f"must be a real tensor, got {getattr(t, 'dtype', type(t).__name__)}")
     _need_gpu(t)
     t = t.reshape(-1).contiguous().float()
     out = torch.empty((t.numel(), dim), device=t.device, dtype=torch.float32)
@@ -1340,8 +1508,18 @@ def sinusoidal(t, dim, kind):
 # ----------------------------------------------------------------------------- layout / elementwise
 def nchw_to_nhwc(src, dtype, c_dst=None, c_off=0, out=None, scale=1.0):
     """fp32 NCHW (* scale) -> 16-bit (or fp32) NHWC with channels padded to ``c_dst`` (default: next multiple of 8)."""
-    _need_gpu(src)
+    # (``src`` of any floating type and layout: converted to a contiguous fp32 copy below)
+    _arg("nchw_to_nhwc", "src", src, (torch.float32, torch.float16, torch.bfloat16, torch.float64), shape=(None,) * 4, layout=None)
     B, Cc, H, W = src.shape
+    if out is not None:
+        _arg("nchw_to_nhwc", "out", out, _ACT, shape=(B, H, W, None))
+        if c_off < 0 or c_off + Cc > out.shape[-1]:
+            _bad("nchw_to_nhwc", "out", f"has {out.shape[-1]} channels, the window [{c_off}, {c_off + Cc}) does not fit")
+    elif dtype not in _ACT:
+        _bad("nchw_to_nhwc", "dtype", f"is {dtype}, expected one of {_ACT}")
+    elif c_off < 0 or c_off + Cc > (pad8(Cc) if c_dst is None else c_dst):
+        _bad("nchw_to_nhwc", "src", f"has {Cc} channels: they do not fit [{c_off}, c_dst = {c_dst})")
+    _need_gpu(src, out)
     src = src.contiguous().float()
     if out is None:
         c_dst = pad8(Cc) if c_dst is None else c_dst
@@ -1361,9 +1539,12 @@ def nchw_to_nhwc(src, dtype, c_dst=None, c_off=0, out=None, scale=1.0):
 
 def nhwc_to_nchw(src, channels=None, c_off=0):
     """NHWC (16-bit or fp32) -> fp32 NCHW, keeping channels [c_off, c_off+channels)."""
-    _need_gpu(src)
+    _arg("nhwc_to_nchw", "src", src, _ACT, shape=(None,) * 4)
     B, H, W, Cs = src.shape
     Cc = Cs - c_off if channels is None else channels
+    if c_off < 0 or Cc <= 0 or c_off + Cc > Cs:
+        _bad("nhwc_to_nchw", "src", f"has {Cs} channels: the window [{c_off}, {c_off + Cc}) does not fit")
+    _need_gpu(src)
     out = torch.empty((B, Cc, H, W), device=src.device, dtype=torch.float32)
     f32 = src.dtype == torch.float32
     L.check(L.load().rsvld_nhwc_to_nchw_f32(_ptr(src), _ptr(out), B, Cc, H, W, Cs, c_off, int(f32),
@@ -1372,11 +1553,11 @@ def nhwc_to_nchw(src, channels=None, c_off=0):
 
 
 def axpby(a, b, sa=1.0, sb=1.0):
+    _arg("axpby", "a", a, _ACT)
+    _same("axpby", "b", b, a)
     _need_gpu(a, b)
     out = torch.empty_like(a)
     if a.dtype == torch.float32:
-        if b.dtype != torch.float32 or not (a.is_contiguous() and b.is_contiguous()) or a.numel() != b.numel():
-            raise L.RsvldError("axpby (fp32): two contiguous fp32 tensors of one size expected")
         L.check(L.load().rsvld_axpby_f32(_ptr(a), _ptr(b), _ptr(out), a.numel(), sa, sb, _stream()), "rsvld_axpby_f32")
         if a.dim() == 4:
             out._nhwc = True
@@ -1386,6 +1567,10 @@ def axpby(a, b, sa=1.0, sb=1.0):
 
 
 def geglu(x):
+    # (16-bit only: the fp32 families fuse GEGLU into the projection's epilogue)
+    _arg("geglu", "x", x, _HALF)
+    if x.dim() < 1 or x.shape[-1] % 2:
+        _bad("geglu", "x", f"must hold [value | gate] rows of an even width, got shape {tuple(x.shape)}")
     _need_gpu(x)
     Cc = x.shape[-1] // 2
     rows = x.numel() // x.shape[-1]
@@ -1396,8 +1581,13 @@ def geglu(x):
 
 def ddpm_step(x, eps_nhwc, noise, c_recip, c_recipm1, coef1, coef2, sigma, clip=True):
     """SR3 ancestral step on fp32 NCHW ``x`` with the UNet's fp32 NHWC eps (diffusion.py:142-175)."""
-    _need_gpu(x, eps_nhwc, noise)
+    _arg("ddpm_step", "x", x, torch.float32, shape=(None,) * 4)
     B, Cc, H, W = x.shape
+    _arg("ddpm_step", "eps_nhwc", eps_nhwc, torch.float32, shape=(B, H, W, None))
+    if eps_nhwc.shape[-1] < Cc:
+        _bad("ddpm_step", "eps_nhwc", f"has {eps_nhwc.shape[-1]} channels, x {Cc}")
+    _same("ddpm_step", "noise", noise, x, optional=True)
+    _need_gpu(x, eps_nhwc, noise)
     out = torch.empty_like(x)
     L.check(L.load().rsvld_ddpm_step(_ptr(x), _ptr(eps_nhwc), _ptr(noise), _ptr(out), B, Cc, H, W,
                                      eps_nhwc.shape[-1], c_recip, c_recipm1, coef1, coef2, sigma, int(clip),
@@ -1408,10 +1598,12 @@ def ddpm_step(x, eps_nhwc, noise, c_recip, c_recipm1, coef1, coef2, sigma, clip=
 # ----------------------------------------------------------------------------- Stage-2 sampler / cache / VAE posterior
 def denoiser_out(net_out_nhwc, inp, c_out, c_skip):
     """fp32 NHWC network output -> fp32 NCHW ``net*c_out + input*c_skip`` (denoiser.py:77-78)."""
-    _need_gpu(net_out_nhwc, inp)
+    _arg("denoiser_out", "inp", inp, torch.float32, shape=(None,) * 4)
     B, Cc, H, W = inp.shape
-    if net_out_nhwc.dtype != torch.float32 or tuple(net_out_nhwc.shape[:3]) != (B, H, W):
-        raise L.RsvldError("denoiser_out: network output must be fp32 NHWC matching the input")
+    _arg("denoiser_out", "net_out_nhwc", net_out_nhwc, torch.float32, shape=(B, H, W, None))
+    if net_out_nhwc.shape[-1] < Cc:
+        _bad("denoiser_out", "net_out_nhwc", f"has {net_out_nhwc.shape[-1]} channels, the input {Cc}")
+    _need_gpu(net_out_nhwc, inp)
     out = torch.empty_like(inp)
     L.check(L.load().rsvld_denoiser_out(_ptr(net_out_nhwc), _ptr(inp), _ptr(out), B, Cc, H, W, net_out_nhwc.shape[-1],
                                         c_out, c_skip, _stream()), "rsvld_denoiser_out")
@@ -1419,9 +1611,9 @@ def denoiser_out(net_out_nhwc, inp, c_out, c_skip):
 
 
 def lerp_f32(a, b, w):
+    _arg("lerp_f32", "a", a, torch.float32)
+    _same("lerp_f32", "b", b, a)
     _need_gpu(a, b)
-    if not (a.is_contiguous() and b.is_contiguous()):
-        raise L.RsvldError("lerp_f32: contiguous fp32 tensors expected")
     out = torch.empty_like(a)
     L.check(L.load().rsvld_lerp_f32(_ptr(a), _ptr(b), _ptr(out), a.numel(), w, _stream()), "rsvld_lerp_f32")
     return out
@@ -1429,6 +1621,8 @@ def lerp_f32(a, b, w):
 
 def axpy_f32(x, y, s):
     """x + s*y on fp32 tensors; ``x=None`` gives s*y."""
+    _arg("axpy_f32", "y", y, torch.float32)
+    _same("axpy_f32", "x", x, y, optional=True)
     _need_gpu(x, y)
     out = torch.empty_like(y)
     L.check(L.load().rsvld_axpy_f32(_ptr(x), _ptr(y), _ptr(out), y.numel(), s, _stream()), "rsvld_axpy_f32")
@@ -1436,6 +1630,9 @@ def axpy_f32(x, y, s):
 
 
 def euler_step(x_hat, denoised, x_center, restore_w, sigma_hat, dt):
+    _arg("euler_step", "x_hat", x_hat, torch.float32)
+    _same("euler_step", "denoised", denoised, x_hat)
+    _same("euler_step", "x_center", x_center, x_hat, optional=True)
     _need_gpu(x_hat, denoised, x_center)
     out = torch.empty_like(x_hat)
     L.check(L.load().rsvld_euler_step(_ptr(x_hat), _ptr(denoised), _ptr(x_center), _ptr(out), x_hat.numel(),
@@ -1445,18 +1642,24 @@ def euler_step(x_hat, denoised, x_center, restore_w, sigma_hat, dt):
 
 def tile_blend_accumulate(acc, cnt, tile, weights, y0, x0):
     """In place: ``acc[:, :, y0:y0+th, x0:x0+tw] += tile * weights``, ``cnt[...] += weights`` (fp32 NCHW; sampling.py:733-734)."""
-    _need_gpu(acc, cnt, tile, weights)
+    fn = "tile_blend_accumulate"
+    _arg(fn, "acc", acc, torch.float32, shape=(None,) * 4)
     B, Cc, H, W = acc.shape
+    _same(fn, "cnt", cnt, acc)
+    _arg(fn, "tile", tile, torch.float32, shape=(B, Cc, None, None))
     th, tw = tile.shape[-2:]
-    if (tuple(cnt.shape) != tuple(acc.shape) or tuple(tile.shape[:2]) != (B, Cc) or tuple(weights.shape) != (th, tw)
-            or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (acc, cnt, tile, weights))):
-        raise L.RsvldError("tile_blend_accumulate: fp32 contiguous acc/cnt [B,C,H,W], tile [B,C,th,tw], weights [th,tw]")
+    _arg(fn, "weights", weights, torch.float32, shape=(th, tw))
+    if not (0 <= int(y0) and int(y0) + th <= H and 0 <= int(x0) and int(x0) + tw <= W):
+        _bad(fn, "tile", f"window [{y0}:{int(y0) + th}, {x0}:{int(x0) + tw}] lies outside the {H}x{W} latent")
+    _need_gpu(acc, cnt, tile, weights)
     L.check(L.load().rsvld_tile_blend_accumulate(_ptr(acc), _ptr(cnt), _ptr(tile), _ptr(weights), B, Cc, H, W, int(y0), int(x0),
                                                  th, tw, _stream()), "rsvld_tile_blend_accumulate")
 
 
 def tile_blend_finish(acc, cnt):
     """-> ``acc / cnt`` (sampling.py:735)."""
+    _arg("tile_blend_finish", "acc", acc, torch.float32)
+    _same("tile_blend_finish", "cnt", cnt, acc)
     _need_gpu(acc, cnt)
     out = torch.empty_like(acc)
     L.check(L.load().rsvld_tile_blend_finish(_ptr(acc), _ptr(cnt), _ptr(out), acc.numel(), _stream()), "rsvld_tile_blend_finish")
@@ -1465,14 +1668,16 @@ def tile_blend_finish(acc, cnt):
 
 def absdiff_sums(a, b):
     """Per batch row: fp32 ``[rows, 2]`` = (sum|a-b|, sum|a|)  (DFBCache.py:98-112)."""
+    _arg("absdiff_sums", "a", a, _ACT)
+    if a.dim() < 1 or a.numel() == 0:
+        _bad("absdiff_sums", "a", f"needs batch rows, got shape {tuple(a.shape)}")
+    _same("absdiff_sums", "b", b, a)
     _need_gpu(a, b)
     rows = a.shape[0]
     n = a.numel() // rows
     lib = L.load()
     out = torch.empty((rows, 2), device=a.device, dtype=torch.float32)
     if a.dtype == torch.float32:
-        if b.dtype != torch.float32 or not (a.is_contiguous() and b.is_contiguous()) or a.numel() != b.numel():
-            raise L.RsvldError("absdiff_sums (fp32): two contiguous fp32 tensors of one size expected")
         L.check(lib.rsvld_absdiff_sums_f32(_ptr(a), _ptr(b), _ptr(out), rows, n, _stream()), "rsvld_absdiff_sums_f32")
         return out
     ws = torch.empty(lib.rsvld_absdiff_ws_bytes(rows, n), device=a.device, dtype=torch.uint8)
@@ -1483,8 +1688,12 @@ def absdiff_sums(a, b):
 
 def gaussian_sample(moments, channels, noise, scale):
     """NHWC moments (16-bit or fp32) -> fp32 NCHW z; ``noise=None`` gives mode()."""
-    _need_gpu(moments, noise)
+    _arg("gaussian_sample", "moments", moments, _ACT, shape=(None,) * 4)
     B, H, W, mc = moments.shape
+    if channels <= 0 or mc < 2 * channels:
+        _bad("gaussian_sample", "moments", f"has {mc} channels, mean | logvar of {channels} need {2 * channels}")
+    _arg("gaussian_sample", "noise", noise, torch.float32, shape=(B, channels, H, W), optional=True)
+    _need_gpu(moments, noise)
     z = torch.empty((B, channels, H, W), device=moments.device, dtype=torch.float32)
     f32 = moments.dtype == torch.float32
     L.check(L.load().rsvld_gaussian_sample(_ptr(moments), _ptr(noise), _ptr(z), B, channels, H, W, mc, scale, int(f32),
@@ -1493,6 +1702,9 @@ def gaussian_sample(moments, channels, noise, scale):
 
 
 def wavelet_blur(img, radius, high_accum=None):
+    """-> the dilated 3x3 blur of fp32 NCHW ``img``; ``high_accum`` (of ``img``'s shape) accumulates ``img - blur`` in place."""
+    _arg("wavelet_blur", "img", img, torch.float32, shape=(None,) * 4)
+    _same("wavelet_blur", "high_accum", high_accum, img, optional=True)
     _need_gpu(img, high_accum)
     B, Cc, H, W = img.shape
     low = torch.empty_like(img)
@@ -1502,6 +1714,8 @@ def wavelet_blur(img, radius, high_accum=None):
 
 
 def add_f32(a, b):
+    _arg("add_f32", "a", a, torch.float32)
+    _same("add_f32", "b", b, a)
     _need_gpu(a, b)
     out = torch.empty_like(a)
     L.check(L.load().rsvld_add_f32(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "rsvld_add_f32")
@@ -1509,6 +1723,9 @@ def add_f32(a, b):
 
 
 def adain(content, style):
+    """Per (image, channel) plane: content normalised to the style's mean and (unbiased) standard deviation; fp32 NCHW of one shape."""
+    _arg("adain", "content", content, torch.float32, shape=(None,) * 4)
+    _same("adain", "style", style, content)
     _need_gpu(content, style)
     B, Cc, H, W = content.shape
     out = torch.empty_like(content)
@@ -1519,12 +1736,14 @@ def adain(content, style):
 
 
 def concat_c(a, b):
+    _arg("concat_c", "a", a, _ACT)
+    if a.dim() < 1:
+        _bad("concat_c", "a", "needs a channel dimension")
+    _arg("concat_c", "b", b, a.dtype, shape=tuple(a.shape[:-1]) + (None,))
     _need_gpu(a, b)
     rows = a.numel() // a.shape[-1]
     out = torch.empty((*a.shape[:-1], a.shape[-1] + b.shape[-1]), device=a.device, dtype=a.dtype)
     if a.dtype == torch.float32:
-        if b.dtype != torch.float32 or not (a.is_contiguous() and b.is_contiguous()):
-            raise L.RsvldError("concat_c (fp32): two contiguous fp32 tensors expected")
         L.check(L.load().rsvld_concat_c_f32(_ptr(a), _ptr(b), _ptr(out), rows, a.shape[-1], b.shape[-1], _stream()), "rsvld_concat_c_f32")
         if a.dim() == 4:
             out._nhwc = True
