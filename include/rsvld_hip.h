@@ -235,6 +235,12 @@ int rsvld_attention(const void* q, const void* k, const void* v, void* out,
 #define RSVLD_ATTN_D64_FOUR_WAVE 1
 #define RSVLD_ATTN_D64_PINGPONG 2
 #define RSVLD_ATTN_D64_PIPELINED 3
+/* d = 512 with keys = values (one tensor, the SR3 form): which of the two shared-tile kernels runs.  They agree bit for bit
+ * (tests/test_gpu_attn_d512_dsplit.py); tune = 0 runs the d-split form.
+ *   attn_d512b  every wave owns 32 query rows over the whole head dim (reads the whole key tile twice per tile);
+ *   attn_d512d  the same S and softmax, PV split by head dim: a wave owns 128 dims of all 128 rows, P exchanged through LDS. */
+#define RSVLD_ATTN_D512_ROWS 4
+#define RSVLD_ATTN_D512_DSPLIT 5
 int rsvld_attention_tuned(const void* q, const void* k, const void* v, void* out,
                           int B, int heads, int Nq, int Nk, int D,
                           int64_t q_batch_stride, int64_t q_tok_stride,

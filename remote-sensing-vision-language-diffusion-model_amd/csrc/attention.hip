@@ -458,6 +458,8 @@ __global__ __launch_bounds__(128) void attn_combine_kernel(AttnArgs p, int nspli
     *(v4*)((T*)p.out + (int64_t)b * p.o_bs + (int64_t)h * D + (int64_t)qrow * p.o_ts + threadIdx.x * 4) = o;
 }
 
+#include "attention_d512d.inc"
+
 }  // namespace
 
 namespace {
@@ -1096,6 +1098,11 @@ extern "C" int rsvld_attention_tuned(const void* q, const void* k, const void* v
             if (ns > 1) hipLaunchKernelGGL(comb, dim3((unsigned)Nq, (unsigned)(B * heads)), dim3(128), 0, s, a, ns, part_o, part_ml);
             return rsvld_check_launch();
         };
+        // shared tile: the head-dimension split of PV (attn_d512d) unless tune asks for the row-owning form; the two agree bit
+        // for bit (tests/test_gpu_attn_d512_dsplit.py)
+        if (shared && tune != RSVLD_ATTN_D512_ROWS)
+            return dtype == RSVLD_F16 ? go(attn_d512d_kernel<f16>, attn_combine_kernel<f16>, A5D_SMEM)
+                                      : go(attn_d512d_kernel<bf16>, attn_combine_kernel<bf16>, A5D_SMEM);
         if (shared)
             return dtype == RSVLD_F16 ? go(attn_d512b_kernel<f16, true>, attn_combine_kernel<f16>, A5B_SMEM_SH)
                                       : go(attn_d512b_kernel<bf16, true>, attn_combine_kernel<bf16>, A5B_SMEM_SH);

@@ -7,6 +7,7 @@ compositions are ``ops.SplitPolicy`` arguments of the owning network, launch-pla
     RSVLD_CONV_TILE / RSVLD_CONV_STAGES / RSVLD_CONV_KSPLIT / RSVLD_CONV_STAGING / RSVLD_HALO_NW /
     RSVLD_GEMM256_OFF / RSVLD_GEMM256_ONE_TILE   -> LaunchContext.tune   (rsvld_conv_desc.tune: every combination computes the same function)
     RSVLD_D64_KERNEL=b|c|p                        -> LaunchContext.d64_kernel (the three bit-identical forms of the d = 64 attention)
+    RSVLD_D512_KERNEL=rows|dsplit                 -> LaunchContext.d512_kernel (the two bit-identical shared-tile d = 512 forms)
     RSVLD_PROFILE_DETAIL=1                        -> LaunchContext.profile_detail (layer shapes in the profiler group names)
     RSVLD_HALO_MIN_WGS=n                          -> LaunchContext.halo_min_wgs
 """
@@ -39,9 +40,16 @@ def d64_kernel(name):
     ops.set_defaults(d64_kernel={"b": 1, "c": 2, "p": 3}.get(name or "", 0))
 
 
+def d512_kernel(name):
+    """"rows" (attn_d512b: a wave owns 32 query rows), "dsplit" (attn_d512d: a wave owns 128 head dims), "" = the library's
+    choice -> this thread's base LaunchContext.d512_kernel (include/rsvld_hip.h RSVLD_ATTN_D512_*; keys = values only)."""
+    ops.set_defaults(d512_kernel={"rows": 4, "dsplit": 5}.get(name or "", 0))
+
+
 def apply_env(e=None):
     e = os.environ if e is None else e
     ops.set_defaults(tune=tune_from_env(e), profile_detail=bool(e.get("RSVLD_PROFILE_DETAIL")))
     d64_kernel(e.get("RSVLD_D64_KERNEL", ""))
+    d512_kernel(e.get("RSVLD_D512_KERNEL", ""))
     if e.get("RSVLD_HALO_MIN_WGS"):
         ops.set_defaults(halo_min_wgs=int(e["RSVLD_HALO_MIN_WGS"]))

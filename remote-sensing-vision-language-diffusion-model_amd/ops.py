@@ -107,14 +107,17 @@ class LaunchContext:
     ``use_halo`` / ``halo_min_wgs`` / ``split_halo_min_wgs``   routing of eligible 3x3 convolutions through conv_halo.hip (below).
     ``split_d512_fused_min`` / ``split_attn_s_bytes``          form of the split-precision d != 64 attention (below).
     ``d64_kernel``                                             developer A/B of the d = 64 attention's three bit-identical forms.
+    ``d512_kernel``                                            developer A/B of the shared-tile d = 512 attention's two bit-identical forms.
     ``profiler`` / ``profile_detail``   per-launch HIP-event bracketing (``LaunchProfiler``) and layer shapes in its group names."""
 
     __slots__ = ("plan_div", "policy", "tune", "use_halo", "halo_min_wgs", "split_halo_min_wgs", "split_d512_fused_min",
-                 "split_attn_s_bytes", "profiler", "profile_detail", "d64_kernel")
+                 "split_attn_s_bytes", "profiler", "profile_detail", "d64_kernel", "d512_kernel")
 
     def __init__(self, plan_div=1, policy=None, tune=0, use_halo=True, halo_min_wgs=256, split_halo_min_wgs=64,
-                 split_d512_fused_min=2048, split_attn_s_bytes=32 << 30, profiler=None, profile_detail=False, d64_kernel=0):
+                 split_d512_fused_min=2048, split_attn_s_bytes=32 << 30, profiler=None, profile_detail=False, d64_kernel=0,
+                 d512_kernel=0):
         # d64_kernel: developer A/B (devtools.d64_kernel): 1 / 2 / 3 = force attn_d64b / attn_d64c / attn_d64p (bit-identical forms)
+        # d512_kernel: developer A/B (devtools.d512_kernel): 4 / 5 = force attn_d512b / attn_d512d when keys = values (bit-identical)
         # use_halo: route eligible 3x3 convs through conv_halo.hip (False: A/B against the gather kernel)
         # halo_min_wgs 256: below one workgroup per CU the 8x32-pixel halo tile under-fills the chip (measured 130 vs 334 TFLOP/s on
         #   32x32 maps): such layers use the 64x128 gather kernel with the 3-stage ring
@@ -127,7 +130,7 @@ class LaunchContext:
         for k, v in (("policy", policy), ("tune", int(tune)), ("use_halo", bool(use_halo)), ("halo_min_wgs", int(halo_min_wgs)),
                      ("split_halo_min_wgs", int(split_halo_min_wgs)), ("split_d512_fused_min", int(split_d512_fused_min)),
                      ("split_attn_s_bytes", int(split_attn_s_bytes)), ("profiler", profiler), ("profile_detail", bool(profile_detail)),
-                     ("d64_kernel", int(d64_kernel))):
+                     ("d64_kernel", int(d64_kernel)), ("d512_kernel", int(d512_kernel))):
             object.__setattr__(self, k, v)
 
     def __setattr__(self, k, v):
@@ -1284,7 +1287,7 @@ def attention(q, k, v, heads, scale=None):
         return out
     ws_bytes = lib.rsvld_attention_ws_bytes(B, heads, Nq, Nk, D, _CTX.get().plan_div)   # split-KV partials (D = 512, small grids)
     ws = torch.empty(ws_bytes, device=q.device, dtype=torch.uint8) if ws_bytes > 0 else None
-    tune = _CTX.get().d64_kernel
+    tune = _CTX.get().d64_kernel if D == 64 else _CTX.get().d512_kernel
     # (profiler group: the short cross-attention launches -- 77 text keys -- are a different kernel and a different regime than
     #  the self-attention of the same layer: kept apart so that the roofline of the dominant group describes ONE kind of launch)
     _launch(f"attention_d{D}" + ("_cross" if (D == 64 and Nk != Nq) else ""), flops, nbytes, lambda: L.check(

@@ -35,7 +35,7 @@ def short_name(n):
     m = re.search(r"gemm256_kernelI\w+?Li(\d)ELb[01]E", n)   # <T, SEG, PERSIST, PV, WIDE>
     if m:
         return "gemm256" + SEG_SFX.get(m.group(1), "")
-    m = re.search(r"attn_d(\d+)b?_kernel", n)
+    m = re.search(r"attn_d(\d+)[bd]?_kernel", n)   # attn_d512b / attn_d512d: one label (bit-identical forms)
     if m:
         return "attn_d%s" % m.group(1)
     m = re.search(r"(?:N_1\d+|::)([a-z0-9_]+)_kernel", n)
