@@ -108,10 +108,16 @@ class LaunchContext:
     ``split_d512_fused_min`` / ``split_attn_s_bytes``          form of the split-precision d != 64 attention (below).
     ``d64_kernel``                                             developer A/B of the d = 64 attention's three bit-identical forms.
     ``d512_kernel``                                            developer A/B of the shared-tile d = 512 attention's two bit-identical forms.
-    ``profiler`` / ``profile_detail``   per-launch HIP-event bracketing (``LaunchProfiler``) and layer shapes in its group names."""
+    ``profiler`` / ``profile_detail``   per-launch HIP-event bracketing (``LaunchProfiler``) and layer shapes in its group names.
+
+    A captured hipGraph (the Stage-1 sampler's UNet forward) bakes in whatever a wrapper read here when it was captured: which
+    kernel, which plan, which workspace.  ``launch_key()`` is the tuple of ALL fields that influence a launch -- every slot except
+    ``NOT_IN_LAUNCH_KEY`` (``profiler``, ``profile_detail``: they bracket and name launches, they do not choose them) -- and is part
+    of a capture's key.  A field added to ``__slots__`` is in the key unless it is listed there (tests/test_graph_key.py)."""
 
     __slots__ = ("plan_div", "policy", "tune", "use_halo", "halo_min_wgs", "split_halo_min_wgs", "split_d512_fused_min",
                  "split_attn_s_bytes", "profiler", "profile_detail", "d64_kernel", "d512_kernel")
+    NOT_IN_LAUNCH_KEY = ("profiler", "profile_detail")
 
     def __init__(self, plan_div=1, policy=None, tune=0, use_halo=True, halo_min_wgs=256, split_halo_min_wgs=64,
                  split_d512_fused_min=2048, split_attn_s_bytes=32 << 30, profiler=None, profile_detail=False, d64_kernel=0,
@@ -143,6 +149,10 @@ class LaunchContext:
             raise TypeError(f"LaunchContext has no field {bad}")
         kw.update(changes)
         return LaunchContext(**kw)
+
+    def launch_key(self):
+        """Hashable tuple of every field a launch depends on (class docstring): two contexts with equal keys issue the same launches."""
+        return tuple((k, getattr(self, k)) for k in self.__slots__ if k not in self.NOT_IN_LAUNCH_KEY)
 
 
 _CTX = contextvars.ContextVar("rsvld_launch_context", default=LaunchContext())

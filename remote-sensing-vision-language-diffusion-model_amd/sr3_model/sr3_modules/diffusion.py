@@ -137,17 +137,30 @@ class GaussianDiffusion(nn.Module):
         return ops.ddpm_step(x, eps, noise, float(h["recip"][t]), float(h["recipm1"][t]), float(h["coef1"][t]),
                              float(h["coef2"][t]), float(h["sigma"][t]) if t > 0 else 0.0, clip=clip_denoised)
 
+    def _graph_key(self, shape, dtype, device_index):
+        """Key of the capture of one UNet forward: everything the capture bakes in besides the values of its two inputs.  Needs no GPU.
+          * input shape, dtype and device: the launch geometry and the static buffers;
+          * ``pack_version``: the graph holds raw pointers into the packed weights (a reload, a move, ``invalidate_packed()`` and every
+            change of precision bump it; ``_unet_eps`` drops the captures of older versions);
+          * ``precision_key()``: compute / pack dtype and the ``SplitPolicy`` (fp32 <-> split toggles once left
+            ``pack_version`` alone and replayed the other mode's kernels).  Today every ``set_compute_dtype`` that changes anything bumps
+            ``pack_version`` too, so the precision rows of tests/test_gpu_sr3_graph.py hold with either field alone and fail only
+            without both: the two are kept because they state different things (pointers | kernels), not because one is spare;
+          * ``LaunchContext.launch_key()``: every field of the launch context a wrapper reads at launch time -- the batch-invariant
+            plan divisor, ``tune``, the halo routing, the attention forms.  (The profiler is not in it: see ``_unet_eps``.)"""
+        unet = self.denoise_fn
+        return (tuple(shape), dtype, device_index, unet.pack_version, unet.precision_key(), ops.context().launch_key())
+
     def _unet_eps(self, xin, level):
         """UNet forward; with ``use_graph`` the ~300 launches of one forward are captured once into a
         hipGraph (torch.cuda.CUDAGraph drives hipStreamBeginCapture on the launch stream) and replayed:
-        the per-step host cost drops from one ctypes call per kernel to one graph launch."""
+        the per-step host cost drops from one ctypes call per kernel to one graph launch.
+        With a ``LaunchProfiler`` in the launch context the forward runs eagerly: a capture would record the profiler's events once,
+        at capture time, and a replay none at all."""
         unet = self.denoise_fn
-        if not self.use_graph:
+        if not self.use_graph or ops.context().profiler is not None:
             return unet.forward_nhwc(xin, level)
-        # the graph holds raw pointers into the packed weights: key it on their version and drop stale captures
-        # ... and on everything else a capture bakes in: the split-operand flag and the batch-invariant plan divisor are global state
-        # read at launch time (ADVICE round 3: fp32 <-> split toggles left pack_version alone and replayed the other mode's kernels)
-        key = (tuple(xin.shape), xin.dtype, xin.device.index, unet.pack_version, unet.precision_key(), ops.context().plan_div)
+        key = self._graph_key(xin.shape, xin.dtype, xin.device.index)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs = {k: v for k, v in self._graphs.items() if k[3] == unet.pack_version}
