@@ -572,64 +572,32 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
     if x.dtype == torch.float32:
         return _conv2d_f32(x, pc, x2=x2, stride=stride, pad=pad, upsample=upsample, rowvec=rowvec, residual=residual,
                            act=act, alpha=alpha, beta=beta, norm=norm)
-    w2 = pc.w.dtype == torch.float32         # fp32 masters under a 16-bit activation: the weight-pair form
+    w2 = pc.w.dtype == torch.float32         # fp32 masters under a 16-bit activation: the weight-pair form (fp16 only: _conv_operands)
     w1res = False
-    if w2:
-        if x.dtype != torch.float16:
-            raise L.RsvldError("conv2d: fp32-packed weights take fp16 activations (RSVLD_F16W2), fp32 tensors or planes")
-        if _split_fast():
-            out_f32 = not out_planes
-            # the layer's weight group (SplitPolicy.f16_weights): named by the caller, or implied by the consumer of an fp16 output
-            wg = group if group is not None else ({"attn": "qkv", "ff": "geglu"}.get(out_group) if not out_f32 else None)
-            if wg is not None and ctx.policy is not None and wg in ctx.policy.f16_weights:
-                if out_f32:
-                    if pc.kh != 1 or pc.kw != 1 or x2 is not None:
-                        raise L.RsvldError(f"conv2d: SplitPolicy.f16_weights {wg!r} with an fp32 output is a Linear layer's form (RSVLD_F16W1)")
-                    w1res = True  # fp16 x fp16, ONE MFMA per product, fp32 out + fp32 residual (dtype RSVLD_F16W1)
-                else:
-                    w2 = False    # the plain fp16 kernels
+    if w2 and _split_fast():
+        out_f32 = not out_planes
+        # the layer's weight group (SplitPolicy.f16_weights): named by the caller, or implied by the consumer of an fp16 output
+        wg = group if group is not None else ({"attn": "qkv", "ff": "geglu"}.get(out_group) if not out_f32 else None)
+        if wg is not None and ctx.policy is not None and wg in ctx.policy.f16_weights:
+            if out_f32:
+                if pc.kh != 1 or pc.kw != 1 or x2 is not None:
+                    raise L.RsvldError(f"conv2d: SplitPolicy.f16_weights {wg!r} with an fp32 output is a Linear layer's form (RSVLD_F16W1)")
+                w1res = True  # fp16 x fp16, ONE MFMA per product, fp32 out + fp32 residual (dtype RSVLD_F16W1)
+            else:
+                w2 = False    # the plain fp16 kernels
     wt = _w1(pc) if w1res else _w2(pc) if w2 else (_w1(pc) if pc.w.dtype == torch.float32 else pc.w)
     B, H, W, Cin = x.shape
     Cin2 = 0 if x2 is None else x2.shape[-1]
-    if Cin + Cin2 != pc.cin_p:
-        raise L.RsvldError(f"conv2d: input channels {Cin}+{Cin2} != packed {pc.cin_p}")
-    if pad is None:
-        pad = pc.kh // 2
-    if isinstance(pad, int):
-        pt = pl = pb = pr = pad
-    else:
-        pt, pl, pb, pr = pad
-    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
-    Ho = (Hin + pt + pb - pc.kh) // stride + 1
-    Wo = (Win + pl + pr - pc.kw) // stride + 1
-    geglu = act == L.ACT_GEGLU
-    c_out = pc.cout_p // 2 if geglu else pc.cout_p
+    geo = _conv_geometry(x.shape, pc, stride, pad, upsample, act)
+    Ho, Wo, c_out = geo[2:]
     out = torch.empty((B, Ho, Wo, c_out), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-    if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()):
-        raise L.RsvldError("conv2d: inputs must be contiguous NHWC")
-    if residual is not None and (tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous()
-                                 or (w2 and residual.dtype != out.dtype)):
-        raise L.RsvldError("conv2d: residual must match the output shape (weight-pair form: and the output's type)")
-    rv_stride = 0
-    if rowvec is not None:
-        if tuple(rowvec.shape) != (B, pc.cout_p) or rowvec.dtype != torch.float32 or rowvec.stride(1) != 1:
-            raise L.RsvldError("conv2d: rowvec must be fp32 [B, Cout] with unit inner stride")
-        rv_stride = rowvec.stride(0) if B > 1 else pc.cout_p
-    d = L.ConvDesc(
-        x=x.data_ptr(), x2=None if x2 is None else x2.data_ptr(), w=wt.data_ptr(),
-        bias=None if pc.bias is None else pc.bias.data_ptr(),
-        rowvec=None if rowvec is None else rowvec.data_ptr(),
-        residual=None if residual is None else residual.data_ptr(), out=out.data_ptr(),
-        B=B, H=H, W=W, Cin=Cin, Cin2=Cin2, Cout=pc.cout_p, KH=pc.kh, KW=pc.kw, stride=stride,
-        pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo, upsample=int(upsample), dtype=L.F16W1 if w1res else L.F16W2 if w2 else _dt(x), out_f32=int(out_f32),
-        act=act, alpha=alpha, beta=beta, rowvec_stride=rv_stride, plan_div=ctx.plan_div, tune=ctx.tune)
+    d = _conv_desc(x.shape, Cin2, pc, geo, L.F16W1 if w1res else L.F16W2 if w2 else _dt(x), int(out_f32), stride=stride,
+                   upsample=upsample, act=act, alpha=alpha, beta=beta, x=x, x2=x2, w=wt, rowvec=rowvec, residual=residual, out=out)
     sfx = "_w1" if w1res else "_w2" if w2 else ""
     lib = L.load()
     halo = ctx.use_halo and bool(lib.rsvld_conv3x3_halo_supported(C.byref(d)))
-    Bp = -(-B // ctx.plan_div)            # batch rows of one planning unit: every plan decision below uses Bp / Mp
     if halo:
-        bn = 64 if pc.cout_p <= 64 else 128
-        halo = Bp * ((Ho + 7) // 8) * ((Wo + 31) // 32) * ((pc.cout_p + bn - 1) // bn) >= ctx.halo_min_wgs and not (upsample and norm is not None)
+        halo = _halo_wgs(B, Ho, Wo, pc.cout_p, ctx.plan_div) >= ctx.halo_min_wgs and not (upsample and norm is not None)
     if norm is not None and not halo:   # unfused: normalise into a (single) tensor, then convolve it
         gamma, nbeta, groups, eps, silu = norm
         xn = group_norm(x, gamma, nbeta, groups, eps, x2=x2, silu=silu)
@@ -641,39 +609,23 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
         + (0 if residual is None else residual.numel() * residual.element_size())
     if halo:
         ab, silu = None, 0
-        part1 = getattr(x, "_gn_part", None)
-        part2 = None if x2 is None else getattr(x2, "_gn_part", None)
-        if norm is not None and part1 is not None and (x2 is None or part2 is not None):
-            gamma, nbeta, groups, eps, silu = norm     # statistics came with the producers' epilogues
-            ab = torch.empty((B, Cin + Cin2, 2), device=x.device, dtype=torch.float32)
-            _launch("groupnorm_ab_from_partials", 0.0, 0.0, lambda: L.check(lib.rsvld_groupnorm_scale_shift_from_partials(
-                _ptr(part1[0]), part1[1], Cin, None if part2 is None else _ptr(part2[0]), 0 if part2 is None else part2[1],
-                Cin2, _ptr(gamma), _ptr(nbeta), _ptr(ab), B, H * W, groups, eps, _stream()),
-                "rsvld_groupnorm_scale_shift_from_partials"))
-        elif norm is not None:
+        if norm is not None:
             gamma, nbeta, groups, eps, silu = norm
-            ws = torch.empty(lib.rsvld_groupnorm_ws_bytes(B, H * W, Cin + Cin2, groups), device=x.device, dtype=torch.uint8)
-            ab = torch.empty((B, Cin + Cin2, 2), device=x.device, dtype=torch.float32)
-            _launch("groupnorm_stats(3 kernels)", 0.0, x.numel() * esz + (0 if x2 is None else x2.numel() * esz),
-                    lambda: L.check(lib.rsvld_groupnorm_scale_shift(_ptr(x), _ptr(x2), _ptr(gamma), _ptr(nbeta), _ptr(ab), B,
-                                                                    H * W, Cin, Cin2, groups, eps, _dt(x), _ptr(ws), _stream()),
-                                    "rsvld_groupnorm_scale_shift"))
+            ab = _gn_ab_from_partials(x, x2, gamma, nbeta, groups, eps)     # statistics came with the producers' epilogues
+            if ab is None:
+                ws = torch.empty(lib.rsvld_groupnorm_ws_bytes(B, H * W, Cin + Cin2, groups), device=x.device, dtype=torch.uint8)
+                ab = torch.empty((B, Cin + Cin2, 2), device=x.device, dtype=torch.float32)
+                _launch("groupnorm_stats(3 kernels)", 0.0, x.numel() * esz + (0 if x2 is None else x2.numel() * esz),
+                        lambda: L.check(lib.rsvld_groupnorm_scale_shift(_ptr(x), _ptr(x2), _ptr(gamma), _ptr(nbeta), _ptr(ab), B,
+                                                                        H * W, Cin, Cin2, groups, eps, _dt(x), _ptr(ws), _stream()),
+                                        "rsvld_groupnorm_scale_shift"))
         name = ("conv_halo_64" if pc.cout_p <= 64 else "conv_halo_128") + sfx
-        part_out = None
-        if stats and (w2 or not out_f32):
-            ntiles = ((Ho + 7) // 8) * ((Wo + 31) // 32)
-            part_out = torch.empty((B, ntiles, pc.cout_p, 2), device=x.device, dtype=torch.float32)
-        _launch(name + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, lambda: L.check(lib.rsvld_conv3x3_halo_nhwc(C.byref(d), _ptr(ab), int(silu), _ptr(part_out),
-                                                                                 _stream()), "rsvld_conv3x3_halo_nhwc"))
-        if part_out is not None:
-            out._gn_part = (part_out, ntiles)
+        _halo_launch(name + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, d, out, ab, silu,
+                     stats and (w2 or not out_f32))
         return out
     M = B * Ho * Wo
-    Mp = -(-M // ctx.plan_div)
-    if (pc.kh == 1 and pc.kw == 1 and stride == 1 and (pt, pl) == (0, 0) and not upsample and x2 is None and rowvec is None
-            and (w2 or not out_f32) and Cin % 32 == 0 and pc.cout_p >= 256 and Mp >= 4096
-            and ((Mp + 255) // 256) * ((pc.cout_p + 255) // 256) >= 128 and 256 * Cin * (4 if w2 else 2) < 2 ** 32
-            and not (ctx.tune & L.TUNE_NO_GEMM256)):   # mirrors rsvld_gemm256_try in csrc/gemm.hip (profiler label only)
+    Mp = -(-M // ctx.plan_div)            # output rows of one planning unit: every plan decision below uses Mp
+    if (w2 or not out_f32) and _gemm256_label(d, Mp, 4 if w2 else 2):
         variant = "gemm_256x256"
     elif pc.cout_p <= 32:
         variant = "conv_igemm_256x32"
@@ -720,10 +672,7 @@ def _conv_operands(fn, x, pc, x2, stride, pad, upsample, rowvec, residual, out_f
     if rowvec is not None and rowvec.stride(1) != 1:
         _bad(fn, "rowvec", f"must have unit inner stride, got strides {tuple(rowvec.stride())}")
     if residual is not None:
-        pt, pl, pb, pr = (pc.kh // 2 if pad is None else pad,) * 4 if not isinstance(pad, (tuple, list)) else pad
-        Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
-        shape = (B, (Hin + pt + pb - pc.kh) // stride + 1, (Win + pl + pr - pc.kw) // stride + 1,
-                 pc.cout_p // 2 if act == L.ACT_GEGLU else pc.cout_p)
+        shape = (B,) + _conv_geometry(x.shape, pc, stride, pad, upsample, act)[2:]
         if f32:
             rdt = torch.float32
         elif pc.w.dtype == torch.float32 and _split_fast():   # the weight-pair form in a split-precision network
@@ -733,49 +682,91 @@ def _conv_operands(fn, x, pc, x2, stride, pad, upsample, rowvec, residual, out_f
         _arg(fn, "residual", residual, rdt, shape=shape)
 
 
-def _conv2d_f32(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, alpha, beta, norm):
-    """fp32 NHWC convolution with fp32 packed weights (rsvld_conv2d_nhwc_f32); a ``norm=`` GroupNorm runs first, unfused."""
-    if pc.w.dtype != torch.float32:
-        raise L.RsvldError("conv2d (fp32): weights must be packed in fp32 (the owning network's compute_dtype)")
-    if norm is not None:
-        gamma, nbeta, groups, eps, silu = norm
-        x, x2 = group_norm(x, gamma, nbeta, groups, eps, x2=x2, silu=silu), None
-    B, H, W, Cin = x.shape
-    Cin2 = 0 if x2 is None else x2.shape[-1]
-    if Cin + Cin2 != pc.cin_p:
-        raise L.RsvldError(f"conv2d: input channels {Cin}+{Cin2} != packed {pc.cin_p}")
+def _conv_geometry(shape, pc, stride, pad, upsample, act):
+    """Where the output of ``pc`` over an NHWC input of ``shape`` lies -> ``(pt, pl, Ho, Wo, c_out)``: ``pad`` = None (``kh // 2``), an int
+    or (top, left, bottom, right); ``upsample`` doubles the input first; GEGLU halves the channels.  Integer arithmetic only."""
+    H, W = shape[1], shape[2]
     if pad is None:
         pad = pc.kh // 2
     pt, pl, pb, pr = (pad,) * 4 if isinstance(pad, int) else pad
     Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
     Ho = (Hin + pt + pb - pc.kh) // stride + 1
     Wo = (Win + pl + pr - pc.kw) // stride + 1
-    c_out = pc.cout_p // 2 if act == L.ACT_GEGLU else pc.cout_p
-    out = torch.empty((B, Ho, Wo, c_out), device=x.device, dtype=torch.float32)
-    if not x.is_contiguous() or (x2 is not None and (not x2.is_contiguous() or x2.dtype != torch.float32)):
-        raise L.RsvldError("conv2d (fp32): inputs must be contiguous fp32 NHWC")
-    if residual is not None and (tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous()
-                                 or residual.dtype != torch.float32):
-        raise L.RsvldError("conv2d (fp32): residual must be fp32 and match the output shape")
-    rv_stride = 0
-    if rowvec is not None:
-        if tuple(rowvec.shape) != (B, pc.cout_p) or rowvec.dtype != torch.float32 or rowvec.stride(1) != 1:
-            raise L.RsvldError("conv2d: rowvec must be fp32 [B, Cout] with unit inner stride")
-        rv_stride = rowvec.stride(0) if B > 1 else pc.cout_p
-    d = L.ConvDesc(
-        x=x.data_ptr(), x2=None if x2 is None else x2.data_ptr(), w=pc.w.data_ptr(),
-        bias=None if pc.bias is None else pc.bias.data_ptr(), rowvec=None if rowvec is None else rowvec.data_ptr(),
-        residual=None if residual is None else residual.data_ptr(), out=out.data_ptr(),
+    return pt, pl, Ho, Wo, pc.cout_p // 2 if act == L.ACT_GEGLU else pc.cout_p
+
+
+def _conv_desc(shape, Cin2, pc, geo, dtype, out_f32, *, stride=1, upsample=False, act=L.ACT_NONE, alpha=1.0, beta=1.0, x=None, x2=None,
+               w=None, rowvec=None, residual=None, out=None, plan_div=None, tune=None):
+    """The rsvld_conv_desc (include/rsvld_hip.h; field by field L.ConvDesc) of ``pc`` on an input of ``shape`` = ``[B, H, W, Cin]`` (+ ``Cin2``
+    channels of ``x2``) with the geometry ``geo`` of ``_conv_geometry``: the only place that fills one.  Absent tensors are null pointers
+    (nothing here needs a device).  ``dtype`` / ``out_f32``: RSVLD_* operand form and output code (0: the activation's type, 1: fp32,
+    2: fp16 from RSVLD_SPLIT).  ``rowvec [B, Cout]`` may be a view with a row stride (one row: the stride is never used).
+    ``plan_div`` / ``tune``: the launch context's unless the caller plans on the whole call / sets its own bits."""
+    ctx = _CTX.get()
+    B, H, W, Cin = shape
+    pt, pl, Ho, Wo, _ = geo
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return L.ConvDesc(
+        x=ptr(x), x2=ptr(x2), w=ptr(w), bias=ptr(pc.bias), rowvec=ptr(rowvec), residual=ptr(residual), out=ptr(out),
         B=B, H=H, W=W, Cin=Cin, Cin2=Cin2, Cout=pc.cout_p, KH=pc.kh, KW=pc.kw, stride=stride, pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo,
-        upsample=int(upsample), dtype=L.F32, out_f32=1, act=act, alpha=alpha, beta=beta, rowvec_stride=rv_stride, plan_div=1,
-        tune=L.TUNE_F32_SPLIT if _policy() is not None else 0)
+        upsample=int(upsample), dtype=dtype, out_f32=out_f32, act=act, alpha=alpha, beta=beta,
+        rowvec_stride=0 if rowvec is None else (rowvec.stride(0) if B > 1 else pc.cout_p),
+        plan_div=ctx.plan_div if plan_div is None else plan_div, tune=ctx.tune if tune is None else tune)
+
+
+def _halo_tiles(Ho, Wo):
+    """8 x 32-pixel output tiles of conv_halo.hip per image: also the rows of its epilogue statistics."""
+    return ((Ho + 7) // 8) * ((Wo + 31) // 32)
+
+
+def _halo_wgs(B, Ho, Wo, cout_p, plan_div):
+    """Workgroups conv_halo.hip would run for ONE planning unit (``-(-B // plan_div)`` batch rows): pixel tiles x blocks of 64
+    (Cout <= 64) or 128 output channels.  Compared with ``halo_min_wgs`` / ``split_halo_min_wgs`` (LaunchContext)."""
+    bn = 64 if cout_p <= 64 else 128
+    return -(-B // plan_div) * _halo_tiles(Ho, Wo) * ((cout_p + bn - 1) // bn)
+
+
+def _halo_launch(name, flops, nbytes, d, out, ab, silu, stats):
+    """rsvld_conv3x3_halo_nhwc on descriptor ``d`` (``ab`` / ``silu``: the fused GroupNorm of its input, or None / 0).  ``stats``: the
+    epilogue writes per-tile per-channel (sum, sumsq) of the output, attached to ``out`` as ``_gn_part`` for the consumer's ``norm=``."""
+    part_out = None
+    if stats:
+        ntiles = _halo_tiles(d.Ho, d.Wo)
+        part_out = torch.empty((d.B, ntiles, d.Cout, 2), device=out.device, dtype=torch.float32)
+    _launch(name, flops, nbytes, lambda: L.check(L.load().rsvld_conv3x3_halo_nhwc(C.byref(d), _ptr(ab), int(silu), _ptr(part_out), _stream()),
+                                                 "rsvld_conv3x3_halo_nhwc"))
+    if part_out is not None:
+        out._gn_part = (part_out, ntiles)
+
+
+def _gemm256_label(d, Mp, wbytes):
+    """Profiler label only: would rsvld_gemm256_try (csrc/gemm.hip) take the layer of descriptor ``d`` (``Mp`` output rows per planning
+    unit, ``wbytes`` per weight element and input channel: 2 plain, 4 pairs, 6 triples)?"""
+    Cin, Cout = d.Cin, d.Cout
+    return (d.KH == 1 and d.KW == 1 and d.stride == 1 and (d.pad_t, d.pad_l) == (0, 0) and not d.upsample and d.x2 is None
+            and d.rowvec is None and Cin % 32 == 0 and Cout >= 256 and Mp >= 4096 and ((Mp + 255) // 256) * ((Cout + 255) // 256) >= 128
+            and 256 * Cin * wbytes < 2 ** 32 and not (d.tune & L.TUNE_NO_GEMM256))
+
+
+def _conv2d_f32(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, alpha, beta, norm):
+    """fp32 NHWC convolution with fp32 packed weights (rsvld_conv2d_nhwc_f32); a ``norm=`` GroupNorm runs first, unfused."""
+    if norm is not None:
+        gamma, nbeta, groups, eps, silu = norm
+        x, x2 = group_norm(x, gamma, nbeta, groups, eps, x2=x2, silu=silu), None
+    B = x.shape[0]
+    geo = _conv_geometry(x.shape, pc, stride, pad, upsample, act)
+    Ho, Wo, c_out = geo[2:]
+    out = torch.empty((B, Ho, Wo, c_out), device=x.device, dtype=torch.float32)
+    split = _policy() is not None
+    d = _conv_desc(x.shape, 0 if x2 is None else x2.shape[-1], pc, geo, L.F32, 1, stride=stride, upsample=upsample, act=act, alpha=alpha,
+                   beta=beta, x=x, x2=x2, w=pc.w, rowvec=rowvec, residual=residual, out=out, plan_div=1,
+                   tune=L.TUNE_F32_SPLIT if split else 0)
     flops = 2.0 * B * Ho * Wo * pc.cout * pc.cin * pc.kh * pc.kw
     nbytes = 4.0 * (x.numel() + pc.w.numel() + out.numel() + (0 if residual is None else residual.numel()))
-    _launch("conv_f32_split" if _policy() is not None else "conv_f32", flops, nbytes, lambda: L.check(L.load().rsvld_conv2d_nhwc_f32(C.byref(d), _stream()),
-                                                       "rsvld_conv2d_nhwc_f32"))
+    _launch("conv_f32_split" if split else "conv_f32", flops, nbytes, lambda: L.check(L.load().rsvld_conv2d_nhwc_f32(C.byref(d), _stream()),
+                                                                                    "rsvld_conv2d_nhwc_f32"))
     out._nhwc = True     # an fp32 4-d tensor is otherwise taken for NCHW by the VAE's input adapter
     return out
-
 
 
 def _w3(pc):
@@ -841,75 +832,58 @@ def _q8_conv_eligible(B, H, W, Cc, pc, stride, pad, upsample, act, out_planes):
     if Cc % 64 or pc.cout_p <= 64 or pc.cout_p % 8 or W < 16 or H < 4 or pc.w.dtype != torch.float32:
         return False
     ctx = _CTX.get()
-    Bp = -(-B // ctx.plan_div)
-    return ctx.use_halo and Bp * ((H + 7) // 8) * ((W + 31) // 32) * ((pc.cout_p + 127) // 128) >= ctx.split_halo_min_wgs
+    return ctx.use_halo and _halo_wgs(B, H, W, pc.cout_p, ctx.plan_div) >= ctx.split_halo_min_wgs
 
 
-def _q8_conv_desc(B, H, W, Cc, pc, *, stride=1, pad=1, upsample=False, act=L.ACT_NONE, out_planes=False, x=None, w=None, rowvec=None,
-                  residual=None, out=None, alpha=1.0, beta=1.0, rowvec_stride=0):
-    """The rsvld_conv_desc of ``pc`` on a ``[B, H, W, Cc]`` input as RSVLD_F16Q8 (absent tensors: null pointers).  ``_conv2d_q8`` launches
-    it; with the geometry of any layer ``_q8_conv_eligible`` is asked about, it is what rsvld_conv3x3_halo_supported must accept."""
-    ctx = _CTX.get()
-    if pad is None:
-        pad = pc.kh // 2
-    pt, pl, pb, pr = (pad,) * 4 if isinstance(pad, int) else pad
-    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    return L.ConvDesc(
-        x=ptr(x), x2=None, w=ptr(w), bias=ptr(pc.bias), rowvec=ptr(rowvec), residual=ptr(residual), out=ptr(out),
-        B=B, H=H, W=W, Cin=Cc, Cin2=0, Cout=pc.cout_p, KH=pc.kh, KW=pc.kw, stride=stride, pad_t=pt, pad_l=pl,
-        Ho=(Hin + pt + pb - pc.kh) // stride + 1, Wo=(Win + pl + pr - pc.kw) // stride + 1, upsample=int(upsample), dtype=L.F16Q8,
-        out_f32=int(not out_planes), act=act, alpha=alpha, beta=beta, rowvec_stride=rowvec_stride, plan_div=ctx.plan_div, tune=ctx.tune)
+def _q8_conv_desc(B, H, W, Cc, pc, *, stride=1, pad=1, upsample=False, act=L.ACT_NONE, out_planes=False, **operands):
+    """The rsvld_conv_desc of ``pc`` on a ``[B, H, W, Cc]`` input as RSVLD_F16Q8 (``operands``: the tensors and scalars of ``_conv_desc``;
+    absent tensors: null pointers).  ``_conv2d_q8`` launches it; with the geometry of any layer ``_q8_conv_eligible`` is asked about, it
+    is what rsvld_conv3x3_halo_supported must accept."""
+    shape = (B, H, W, Cc)
+    return _conv_desc(shape, 0, pc, _conv_geometry(shape, pc, stride, pad, upsample, act), L.F16Q8, int(not out_planes), stride=stride,
+                      upsample=upsample, act=act, **operands)
 
 
 def _conv2d_q8(xq, pc, *, rowvec, residual, alpha, beta, stats):
     """3x3 / stride 1 / pad 1 on Q8Rows: fp32 out (+ fp32 residual), epilogue statistics for the next GroupNorm."""
     B, H, W, Cc = xq.shape
-    if Cc != pc.cin_p:
-        raise L.RsvldError(f"conv2d (q8): input channels {Cc} != packed {pc.cin_p}")
     out = torch.empty((B, H, W, pc.cout_p), device=xq.t.device, dtype=torch.float32)
-    if residual is not None and (isinstance(residual, Planes) or residual.dtype != torch.float32 or tuple(residual.shape) != tuple(out.shape)
-                                 or not residual.is_contiguous()):
-        raise L.RsvldError("conv2d (q8): residual must be fp32 and match the output shape")
-    rv_stride = 0
-    if rowvec is not None:
-        if tuple(rowvec.shape) != (B, pc.cout_p) or rowvec.dtype != torch.float32 or rowvec.stride(1) != 1:
-            raise L.RsvldError("conv2d: rowvec must be fp32 [B, Cout] with unit inner stride")
-        rv_stride = rowvec.stride(0) if B > 1 else pc.cout_p
-    d = _q8_conv_desc(B, H, W, Cc, pc, x=xq.t, w=_wq8(pc), rowvec=rowvec, residual=residual, out=out, alpha=alpha, beta=beta,
-                      rowvec_stride=rv_stride)
-    lib = L.load()
-    if not lib.rsvld_conv3x3_halo_supported(C.byref(d)):
+    d = _q8_conv_desc(B, H, W, Cc, pc, x=xq.t, w=_wq8(pc), rowvec=rowvec, residual=residual, out=out, alpha=alpha, beta=beta)
+    if not L.load().rsvld_conv3x3_halo_supported(C.byref(d)):
         raise L.RsvldError("conv2d (q8): shape not supported by the halo kernel (checked by _q8_conv_eligible)")
-    part_out, ntiles = None, ((H + 7) // 8) * ((W + 31) // 32)
-    if stats:
-        part_out = torch.empty((B, ntiles, pc.cout_p, 2), device=out.device, dtype=torch.float32)
     flops = 2.0 * B * H * W * pc.cout * pc.cin * 9
     nbytes = 4.0 * (B * H * W * Cc + out.numel() + (0 if residual is None else residual.numel())) + 4.0 * pc.w.numel()
-    _launch("conv_halo_128_q8" + _detail(B, H, W, Cc, 0, pc, 1, False), flops, nbytes, lambda: L.check(
-        lib.rsvld_conv3x3_halo_nhwc(C.byref(d), None, 0, _ptr(part_out), _stream()), "rsvld_conv3x3_halo_nhwc"))
-    if part_out is not None:
-        out._gn_part = (part_out, ntiles)
+    _halo_launch("conv_halo_128_q8" + _detail(B, H, W, Cc, 0, pc, 1, False), flops, nbytes, d, out, None, 0, stats)
     out._nhwc = True
     return out
+
+
+def _gn_ab_from_partials(x, x2, gamma, nbeta, groups, eps):
+    """(scale, shift) fp32 ``[B, C1+C2, 2]`` of a GroupNorm over NHWC ``[x | x2]`` from the (sum, sumsq) partials their producers'
+    epilogues attached (``_gn_part``: no pass over the tensors); None unless every source carries them."""
+    part1 = getattr(x, "_gn_part", None)
+    part2 = None if x2 is None else getattr(x2, "_gn_part", None)
+    if part1 is None or (x2 is not None and part2 is None):
+        return None
+    B, H, W, C1 = x.shape
+    C2 = 0 if x2 is None else x2.shape[-1]
+    ab = torch.empty((B, C1 + C2, 2), device=x.device, dtype=torch.float32)
+    _launch("groupnorm_ab_from_partials", 0.0, 0.0, lambda: L.check(L.load().rsvld_groupnorm_scale_shift_from_partials(
+        _ptr(part1[0]), part1[1], C1, None if part2 is None else _ptr(part2[0]), 0 if part2 is None else part2[1],
+        C2, _ptr(gamma), _ptr(nbeta), _ptr(ab), B, H * W, groups, eps, _stream()), "rsvld_groupnorm_scale_shift_from_partials"))
+    return ab
 
 
 def _gn_scale_shift_f32(x, x2, gamma, nbeta, groups, eps):
     """(scale, shift) fp32 ``[B, C1+C2, 2]`` of a GroupNorm over fp32 NHWC ``[x | x2]``: from the producers' epilogue partials when
     every source carries them (no pass over the tensors), else one statistics pass."""
+    ab = _gn_ab_from_partials(x, x2, gamma, nbeta, groups, eps)
+    if ab is not None:
+        return ab
     B, H, W, C1 = x.shape
     C2 = 0 if x2 is None else x2.shape[-1]
     lib = L.load()
     ab = torch.empty((B, C1 + C2, 2), device=x.device, dtype=torch.float32)
-    part1 = getattr(x, "_gn_part", None)
-    part2 = None if x2 is None else getattr(x2, "_gn_part", None)
-    if part1 is not None and (x2 is None or part2 is not None):
-        _launch("groupnorm_ab_from_partials", 0.0, 0.0, lambda: L.check(lib.rsvld_groupnorm_scale_shift_from_partials(
-            _ptr(part1[0]), part1[1], C1, None if part2 is None else _ptr(part2[0]), 0 if part2 is None else part2[1],
-            C2, _ptr(gamma), _ptr(nbeta), _ptr(ab), B, H * W, groups, eps, _stream()), "rsvld_groupnorm_scale_shift_from_partials"))
-        return ab
-    if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()):
-        raise L.RsvldError("group_norm (split): contiguous fp32 NHWC inputs expected")
     ws = torch.empty(lib.rsvld_groupnorm_ws_bytes(B, H * W, C1 + C2, groups), device=x.device, dtype=torch.uint8)
     _launch("groupnorm_stats_split", 0.0, 4.0 * (x.numel() + (0 if x2 is None else x2.numel())), lambda: L.check(
         lib.rsvld_groupnorm_scale_shift_f32(_ptr(x), _ptr(x2), _ptr(gamma), _ptr(nbeta), _ptr(ab), B, H * W, C1, C2, groups, eps,
@@ -921,12 +895,12 @@ def _gn_apply_split(x, x2, ab, silu, planes, mod_scale1p=None, mod_shift=None, f
     B, H, W, C1 = x.shape
     C2 = 0 if x2 is None else x2.shape[-1]
     Cc = C1 + C2
-    mod_stride = 0
-    if mod_scale1p is not None:
-        mod_stride = mod_scale1p.stride(-2)
-        if (mod_shift.stride(-2) != mod_stride or mod_scale1p.stride(-1) != 1 or mod_shift.stride(-1) != 1
-                or mod_scale1p.dtype != torch.float32 or mod_shift.dtype != torch.float32):
-            raise L.RsvldError("group_norm: modulation tensors must be fp32, share a row stride and be channel-contiguous")
+    mod_stride = _mod_stride(mod_scale1p)
+    # (_mod_operands saw the tensors as the caller passed them: group_norm has since merged a Planes one into a contiguous fp32 tensor,
+    #  which its plain partner -- a channel slice with another row stride, say -- must still agree with)
+    if mod_scale1p is not None and (mod_shift.stride(-2) != mod_stride or mod_scale1p.stride(-1) != 1 or mod_shift.stride(-1) != 1
+                                    or mod_scale1p.dtype != torch.float32 or mod_shift.dtype != torch.float32):
+        raise L.RsvldError("group_norm: modulation tensors must be fp32, share a row stride and be channel-contiguous")
     f16 = f16 and planes          # the fp16 hand-over replaces a planes output only
     if q8:                        # RSVLD_F16Q8 rows (the input of a convolution with e4m3 cross terms)
         out = torch.empty((B, H, W, 2, Cc), device=x.device, dtype=torch.float16)
@@ -983,24 +957,10 @@ def _conv2d_split(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, al
     x2 = None if x2 is None else to_planes(x2)
     B, H, W, Cin = x.shape
     Cin2 = 0 if x2 is None else x2.shape[-1]
-    if Cin + Cin2 != pc.cin_p:
-        raise L.RsvldError(f"conv2d: input channels {Cin}+{Cin2} != packed {pc.cin_p}")
-    if pad is None:
-        pad = pc.kh // 2
-    pt, pl, pb, pr = (pad,) * 4 if isinstance(pad, int) else pad
-    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
-    Ho = (Hin + pt + pb - pc.kh) // stride + 1
-    Wo = (Win + pl + pr - pc.kw) // stride + 1
-    geglu = act == L.ACT_GEGLU
-    c_out = pc.cout_p // 2 if geglu else pc.cout_p
-    if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()):
-        raise L.RsvldError("conv2d (split): inputs must be contiguous planes")
-    if residual is not None:
-        if out_planes:
-            raise L.RsvldError("conv2d (split): a planes output takes no residual (the residual stream stays fp32)")
-        if isinstance(residual, Planes) or residual.dtype != torch.float32 or tuple(residual.shape) != (B, Ho, Wo, c_out) \
-                or not residual.is_contiguous():
-            raise L.RsvldError("conv2d (split): residual must be fp32 and match the output shape")
+    geo = _conv_geometry(x.shape, pc, stride, pad, upsample, act)
+    Ho, Wo, c_out = geo[2:]
+    if residual is not None and out_planes:
+        raise L.RsvldError("conv2d (split): a planes output takes no residual (the residual stream stays fp32)")
     # fp16 hand-over: a Linear / 1x1 layer (the implicit-GEMM kernels write it) whose consumer's layer group takes fp16 inputs
     out_f16 = bool(out_planes and f16_group(out_group) and pc.kh == 1 and pc.kw == 1 and stride == 1 and x2 is None and not upsample)
     if out_f16:
@@ -1009,45 +969,23 @@ def _conv2d_split(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, al
         out = torch.empty((B, Ho, Wo, 2, c_out), device=x.device, dtype=torch.bfloat16)
     else:
         out = torch.empty((B, Ho, Wo, c_out), device=x.device, dtype=torch.float32)
-    rv_stride = 0
-    if rowvec is not None:
-        if tuple(rowvec.shape) != (B, pc.cout_p) or rowvec.dtype != torch.float32 or rowvec.stride(1) != 1:
-            raise L.RsvldError("conv2d: rowvec must be fp32 [B, Cout] with unit inner stride")
-        rv_stride = rowvec.stride(0) if B > 1 else pc.cout_p
-    w3 = _w3(pc)
-    d = L.ConvDesc(
-        x=x.t.data_ptr(), x2=None if x2 is None else x2.t.data_ptr(), w=w3.data_ptr(),
-        bias=None if pc.bias is None else pc.bias.data_ptr(), rowvec=None if rowvec is None else rowvec.data_ptr(),
-        residual=None if residual is None else residual.data_ptr(), out=out.data_ptr(),
-        B=B, H=H, W=W, Cin=Cin, Cin2=Cin2, Cout=pc.cout_p, KH=pc.kh, KW=pc.kw, stride=stride, pad_t=pt, pad_l=pl, Ho=Ho, Wo=Wo,
-        upsample=int(upsample), dtype=L.SPLIT, out_f32=2 if out_f16 else int(not out_planes), act=act, alpha=alpha, beta=beta,
-        rowvec_stride=rv_stride, plan_div=ctx.plan_div, tune=ctx.tune)
+    d = _conv_desc(x.shape, Cin2, pc, geo, L.SPLIT, 2 if out_f16 else int(not out_planes), stride=stride, upsample=upsample, act=act,
+                   alpha=alpha, beta=beta, x=x.t, x2=None if x2 is None else x2.t, w=_w3(pc), rowvec=rowvec, residual=residual, out=out)
     lib = L.load()
     flops = 2.0 * B * Ho * Wo * pc.cout * pc.cin * pc.kh * pc.kw
     nbytes = 4.0 * (x.numel() + (0 if x2 is None else x2.numel()) + out.numel() / (2 if (out_planes or out_f16) else 1)
                     + (0 if residual is None else residual.numel())) + 6.0 * pc.w.numel()
-    Bp = -(-B // ctx.plan_div)
     halo = ctx.use_halo and bool(lib.rsvld_conv3x3_halo_supported(C.byref(d)))
     if halo:
-        bn = 64 if pc.cout_p <= 64 else 128
-        halo = Bp * ((Ho + 7) // 8) * ((Wo + 31) // 32) * ((pc.cout_p + bn - 1) // bn) >= ctx.split_halo_min_wgs
+        halo = _halo_wgs(B, Ho, Wo, pc.cout_p, ctx.plan_div) >= ctx.split_halo_min_wgs
     if halo:
-        part_out = None
-        if stats and not out_planes:
-            ntiles = ((Ho + 7) // 8) * ((Wo + 31) // 32)
-            part_out = torch.empty((B, ntiles, pc.cout_p, 2), device=x.device, dtype=torch.float32)
-        _launch(("conv_halo_64_split" if pc.cout_p <= 64 else "conv_halo_128_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, lambda: L.check(
-            lib.rsvld_conv3x3_halo_nhwc(C.byref(d), None, 0, _ptr(part_out), _stream()), "rsvld_conv3x3_halo_nhwc"))
-        if part_out is not None:
-            out._gn_part = (part_out, ntiles)
+        _halo_launch(("conv_halo_64_split" if pc.cout_p <= 64 else "conv_halo_128_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
+                     flops, nbytes, d, out, None, 0, stats and not out_planes)
     else:
         M = B * Ho * Wo
         Mp = -(-M // ctx.plan_div)
-        g256 = (pc.kh == 1 and pc.kw == 1 and stride == 1 and (pt, pl) == (0, 0) and not upsample and x2 is None and rowvec is None
-                and Cin % 32 == 0 and pc.cout_p >= 256 and Mp >= 4096 and ((Mp + 255) // 256) * ((pc.cout_p + 255) // 256) >= 128
-                and 256 * Cin * 6 < 2 ** 32 and not (ctx.tune & L.TUNE_NO_GEMM256))   # mirrors rsvld_gemm256_try
-        _launch(("gemm_256x256_split" if g256 else "conv_igemm_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes,
-                lambda: L.check(lib.rsvld_conv2d_nhwc(C.byref(d), _stream()), "rsvld_conv2d_nhwc"))
+        _launch(("gemm_256x256_split" if _gemm256_label(d, Mp, 6) else "conv_igemm_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
+                flops, nbytes, lambda: L.check(lib.rsvld_conv2d_nhwc(C.byref(d), _stream()), "rsvld_conv2d_nhwc"))
     if out_f16:
         return out
     if out_planes:
@@ -1109,6 +1047,11 @@ def _mod_operands(fn, x, x2, mod_scale1p, mod_shift, planes_ok=False):
         _bad(fn, "mod_shift", "must share mod_scale1p's row stride")
 
 
+def _mod_stride(mod_scale1p):
+    """Row (pixel) stride in elements that both ZeroSFT modulation tensors share (``_mod_operands``); 0 without modulation."""
+    return 0 if mod_scale1p is None else mod_scale1p.stride(-2)
+
+
 def group_norm(x, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=None, mod_shift=None, planes=False, group=None):
     """GroupNorm(+SiLU) over NHWC ``x`` (or the channel concat [x | x2]).  ``mod_scale1p`` / ``mod_shift``
     (ZeroSFT) may be channel slices of one stacked tensor: only their row stride must agree.
@@ -1121,11 +1064,6 @@ def group_norm(x, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=
         ab = _gn_scale_shift_f32(x, x2, gamma, beta, groups, eps)
         return _gn_apply_split(x, x2, ab, silu, planes, as_f32(mod_scale1p) if mod_scale1p is not None else None,
                                as_f32(mod_shift) if mod_shift is not None else None, f16=f16_group(group))
-    mod_stride = 0
-    if mod_scale1p is not None:
-        mod_stride = mod_scale1p.stride(-2)
-        if mod_shift.stride(-2) != mod_stride or mod_scale1p.stride(-1) != 1 or mod_shift.stride(-1) != 1:
-            raise L.RsvldError("group_norm: modulation tensors must share a row stride and be channel-contiguous")
     _need_gpu(x, x2, gamma, beta)
     if x.dtype == torch.float32:       # fp32 family: the two-source form concatenates first; statistics, then apply (+ modulation)
         if x2 is not None:
@@ -1140,7 +1078,7 @@ def group_norm(x, gamma, beta, groups, eps, *, x2=None, silu=False, mod_scale1p=
     nbytes = 3 * y.numel() * y.element_size()  # stats read + apply read + write
     _launch("groupnorm(3 kernels)", 0.0, nbytes, lambda: L.check(
         lib.rsvld_groupnorm_nhwc(_ptr(x), _ptr(x2), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(mod_scale1p),
-                                 _ptr(mod_shift), mod_stride, B, H * W, C1, C2, groups, eps, int(silu), _dt(x),
+                                 _ptr(mod_shift), _mod_stride(mod_scale1p), B, H * W, C1, C2, groups, eps, int(silu), _dt(x),
                                  _ptr(ws), _stream()), "rsvld_groupnorm_nhwc"))
     return y
 
@@ -1197,14 +1135,8 @@ def group_norm_apply(x, stats, gamma, beta, groups, eps, *, x2=None, silu=False,
     if x.dtype == torch.float32:
         if x2 is not None or not x.is_contiguous():
             raise L.RsvldError("group_norm_apply (fp32): one contiguous NHWC tensor expected")
-        mod_stride = 0
-        if mod_scale1p is not None:
-            mod_stride = mod_scale1p.stride(-2)
-            if (mod_shift.stride(-2) != mod_stride or mod_scale1p.stride(-1) != 1 or mod_shift.stride(-1) != 1
-                    or mod_scale1p.dtype != torch.float32 or mod_shift.dtype != torch.float32):
-                raise L.RsvldError("group_norm: modulation tensors must be fp32, share a row stride and be channel-contiguous")
         _launch("groupnorm_apply_f32", 0.0, 8.0 * x.numel(), lambda: L.check(L.load().rsvld_groupnorm_apply_f32(
-            _ptr(x), _ptr(y), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(mod_scale1p), _ptr(mod_shift), mod_stride,
+            _ptr(x), _ptr(y), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(mod_scale1p), _ptr(mod_shift), _mod_stride(mod_scale1p),
             B, H * W, C1, groups, eps, int(silu), _stream()), "rsvld_groupnorm_apply_f32"))
         y._nhwc = True
         return y
@@ -1313,9 +1245,8 @@ def attention(q, k, v, heads, scale=None):
 def _split_gemm(xt, w3, out, M, K, N, out_f32, name):
     """``out[M, N] = x[M, K] w[N, K]^T`` in the split precision: ``xt`` contiguous planes ``[M, 2, K]``, ``w3`` triples ``[N, 3K]``,
     ``out`` fp32 ``[M, N]`` or planes ``[M, 2, N]`` (rsvld_conv2d_nhwc as a 1x1 layer; plans on the whole call)."""
-    d = L.ConvDesc(x=xt.data_ptr(), x2=None, w=w3.data_ptr(), bias=None, rowvec=None, residual=None, out=out.data_ptr(),
-                   B=1, H=1, W=M, Cin=K, Cin2=0, Cout=N, KH=1, KW=1, stride=1, pad_t=0, pad_l=0, Ho=1, Wo=M, upsample=0,
-                   dtype=L.SPLIT, out_f32=int(out_f32), act=L.ACT_NONE, alpha=1.0, beta=1.0, rowvec_stride=0, plan_div=1, tune=_CTX.get().tune)
+    d = _conv_desc((1, 1, M, K), 0, PackedConv(w3, None, K, N, K, N, 1, 1), (0, 0, 1, M, N), L.SPLIT, int(out_f32), x=xt, w=w3, out=out,
+                   plan_div=1)
     _launch(name, 2.0 * M * K * N, 4.0 * M * K + 6.0 * N * K + 4.0 * M * N,
             lambda: L.check(L.load().rsvld_conv2d_nhwc(C.byref(d), _stream()), "rsvld_conv2d_nhwc"))
 
