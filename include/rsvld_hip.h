@@ -226,15 +226,13 @@ int rsvld_attention(const void* q, const void* k, const void* v, void* out,
                     int64_t v_batch_stride, int64_t v_tok_stride,
                     int64_t o_batch_stride, int64_t o_tok_stride,
                     float scale, int dtype, int plan_div, void* ws, void* stream);
-/* The same call with a developer A/B override (tests, tools): which of the three d = 64 kernels runs.  They agree bit for
+/* The same call with a developer A/B override (tests, tools): which of the two d = 64 kernels runs.  They agree bit for
  * bit on every shape (tests/test_gpu_kernels.py), so the library's own choice (tune = 0: by grid size) is a speed decision only:
  *   attn_d64b  four waves per SIMD, 128 / 256 query rows per workgroup (short sequences, small grids);
  *   attn_d64c  "ping-pong": 8 waves x 64 query rows, matrix and vector segments of the two waves of a SIMD in anti-phase
- *              (grids of >= 1024 workgroups: the Stage-2 self-attention of the headline, +2-5 %);
- *   attn_d64p  "pipelined": every wave mixes its MFMAs with chunks of the next tile's softmax (experiment, 12 % slower). */
+ *              (grids of >= 1024 workgroups: the Stage-2 self-attention of the headline, +2-5 %). */
 #define RSVLD_ATTN_D64_FOUR_WAVE 1
 #define RSVLD_ATTN_D64_PINGPONG 2
-#define RSVLD_ATTN_D64_PIPELINED 3
 /* d = 512 with keys = values (one tensor, the SR3 form): which of the two shared-tile kernels runs.  They agree bit for bit
  * (tests/test_gpu_attn_d512_dsplit.py); tune = 0 runs the d-split form.
  *   attn_d512b  every wave owns 32 query rows over the whole head dim (reads the whole key tile twice per tile);
@@ -467,8 +465,7 @@ int rsvld_layernorm_split(const float* x, void* out, const float* gamma, const f
 /* Flash attention on planes, D = 64 (sgm CrossAttention at sgm/modules/attention.py:357-359 under diffusion_dtype "split"):
  * q / k / v point at the LO plane of element (b, n, h, d) = base + b*batch_stride + n*tok_stride + h*64 + d, the HI plane sits
  * *_plane elements further; three bf16 MFMAs per product in both contractions, fp32 softmax.  out: planes (o_plane = distance of
- * its hi plane, out_f32 = 0) or fp32 (out_f32 = 1).  out_f32 bit 2 (value 4, developer override like rsvld_attention_tuned): run the
- * ping-pong form of the kernel (an experiment: bit-identical, 10-13 % slower). */
+ * its hi plane, out_f32 = 0) or fp32 (out_f32 = 1; only bit 0 is read). */
 int rsvld_attention_split_d64(const void* q, const void* k, const void* v, void* out, int B, int heads, int Nq, int Nk,
                               int64_t q_batch_stride, int64_t q_tok_stride, int64_t q_plane,
                               int64_t k_batch_stride, int64_t k_tok_stride, int64_t k_plane,

@@ -66,66 +66,11 @@
         };
         // (each part ends with an empty volatile asm naming what it produced: volatile asms keep their order, so the part
         // is computed at its hook; without the pins hipcc sinks the whole softmax behind the chain)
-        // the same softmax in 32 parts (A5B_FINE): 0..7 max of two scores each, 8 half-wave exchange + scale, 9 the deferred-max
-        // decision, 10..25 one exponential each (fma + exp2 + row-sum add), 26 the row sum, 27..30 four conversions each
-        auto sm32 = [&](int part) {
-            if (A5B_ABL & 1) {
-                if (part == 30) sm(6);
-                return;
-            }
-            if (part < 8) {
-                if (!A5B_STEADY && part == 0 && k_begin + (t + 1) * 32 > k_end) {   // ragged last tile (uniform branch)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int kv = k_begin + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (kv >= k_end) S_CUR[r] = -INFINITY;
-                    }
-                }
-                mx = fmaxf(mx, fmaxf(S_CUR[2 * part], S_CUR[2 * part + 1]));
-                asm volatile("" : "+v"(mx));
-            } else if (part == 8) {
-                mx = a5b_halfwave_max(mx) * p.scale_log2e;
-                asm volatile("" : "+v"(mx));
-            } else if (part == 9) {
-                need = mx > m_run + A5_DEFER_LOG2;   // true on the first tile (m_run = -inf)
-                if (need) {
-                    alpha = __builtin_amdgcn_exp2f(m_run - mx);
-                    m_run = mx;
-                }
-                asm volatile("" : "+v"(alpha), "+v"(m_run));
-            } else if (part <= 25) {
-                const int r = part - 10;
-                S_CUR[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(S_CUR[r], p.scale_log2e, -m_run));
-                rs += S_CUR[r];
-                asm volatile("" : "+v"(S_CUR[r]), "+v"(rs));
-            } else if (part == 26) {
-                l_run = l_run * alpha + rs;
-                asm volatile("" : "+v"(l_run));
-            } else if (part <= 30) {
-                const int q4 = part - 27;   // scores 4 q4 .. 4 q4 + 3 -> pf[q4 >> 1][4 (q4 & 1) ..]
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pf[q4 >> 1][4 * (q4 & 1) + j] = (T)S_CUR[4 * q4 + j];
-                if (q4 & 1) asm volatile("" : "+v"(pf[q4 >> 1]));
-            }
-        };
 
 #if !A5B_PAIR
         f32x16 snext;
 #endif
         if (more) {
-#if A5B_FINE
-#define A5B_HOOK(k)                                                   \
-    if constexpr (((k) & 3) == 3) {                                   \
-        if constexpr (SH) {                                           \
-            if (more2) dma_kb_s(t + 2, b_dma, (k) >> 2);                \
-        } else {                                                      \
-            if (more2) dma_k_s(t + 2, (k) >> 2);                        \
-            dma_v_s(t + 1, (k) >> 2);                                   \
-        }                                                             \
-    }                                                                 \
-    sm32(k);                                                          \
-    __builtin_amdgcn_sched_barrier(0)
-#else
 #define A5B_HOOK(i)                                                   \
     if constexpr (SH) {                                               \
         if (more2) dma_kb_s(t + 2, b_dma, i);                           \
@@ -135,16 +80,12 @@
     }                                                                 \
     sm(i);                                                            \
     __builtin_amdgcn_sched_barrier(0)
-#endif
             if constexpr (__is_same(T, f16)) {
                 A5B_CHAIN("v_mfma_f32_32x32x16_f16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
             } else {
                 A5B_CHAIN("v_mfma_f32_32x32x16_bf16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
             }
 #undef A5B_HOOK
-        } else if (A5B_FINE) {
-#pragma unroll
-            for (int i = 0; i < 32; ++i) sm32(i);
         } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) sm(i);

@@ -1,6 +1,6 @@
 // Included by attention.hip inside its anonymous namespace (uses AttnArgs, Mfma<T>, A6B_TILE, a6b_add, s16x4).
 // ---------------------------------------------------------------------------------------
-// D = 64, third generation ("ping-pong", round 3).  attn_d64b runs four waves per SIMD whose phases are left to chance: the
+// D = 64, the "ping-pong" form.  attn_d64b runs four waves per SIMD whose phases are left to chance: the
 // matrix pipe is busy 61 % of the time (PMC) although the kernel's vector issue (exp 8, add 4, cvt 4 cycles per instruction;
 // MI355X_MICROARCH.md) would allow ~0.9.  Here the overlap is by construction:
 //   * one workgroup of 8 waves per CU (two per SIMD, up to 256 registers); a wave owns 64 query rows (two 32-row sub-tiles
@@ -21,52 +21,13 @@
 #define A6C_ABL 0   // diagnostic builds (results WRONG, timing only): 1 no in-loop LDS-DMA request, 2 no exponentials, 4 no row sums,
                     // 8 no softmax at all (V segment = V reads only), 16 no MFMAs in the M segment
 #endif
-#ifndef A6C_M0_CLOBBER
-#define A6C_M0_CLOBBER 1   // M0 declared clobbered by the LDS-DMA statements (see A5B_M0_CLOBBER; audited by tools/audit_m0.py): +1.1-1.2 % here
-#endif                     // (1 000.8 / 1 103.6 -> 1 013.1 / 1 115.9 TFLOP/s, profiles/r03_attn_d64_ab.txt run 16); attn_d64b lost 12 % with it
-#ifndef A6C_DMA_IN_V
-#define A6C_DMA_IN_V 0   // experiment: the LDS-DMA request of tile i + 3 in the vector segment instead of the matrix segment (+0.3 %; -0.4 % together with the M0 form: off)
-#endif
-#ifndef A6C_XCD_ORDER
-#define A6C_XCD_ORDER 1
-#endif
-#ifndef A6C_STEADY_LOOP
-#define A6C_STEADY_LOOP 1
-#endif
-#ifndef A6C_PRIO
-#define A6C_PRIO 1   // s_setprio 1 around: 1 the matrix segment, 2 the vector segment, 0 neither
-#endif
-#ifndef A6C_JOINT
-#define A6C_JOINT 1
-#endif
-#ifndef A6C_ONEPATH
-#define A6C_ONEPATH 0
-#endif
-#ifndef A6C_NOREDO
-#define A6C_NOREDO 0   // diagnostic (results wrong): no redo path
-#endif
-#ifndef A6C_QREG
-#define A6C_QREG 0   // experiment (round 5): the Q fragments in registers (+32) instead of re-read from the wave's LDS image in every S chain (8 of the 16 ds_read_b128 per tile)
-#endif
-#ifndef A6C_AHEAD
-#define A6C_AHEAD 1   // experiment (round 5): the K (and Q) fragments of an S chain are read this many k-steps ahead of their MFMAs (1 or 2)
-#endif
-#ifndef A6C_VEARLY
-#define A6C_VEARLY 0   // experiment (round 5): the V-fragment reads of a tile between the two P conversions of its softmax instead of behind them (their LDS latency behind 16 v_cvt_pk instead of in front of the late half's first PV MFMA)
-#endif
-#ifndef A6C_VINM
-#define A6C_VINM 0   // experiment (round 5): the V-fragment reads of tile t + 1 ride in the issue slots of M(t)'s S chains (behind PV(t), which frees the registers) instead of closing the vector segment
-#endif
-#ifndef A6C_BIASREG
-#define A6C_BIASREG 1   // experiment (round 5): the three operand tuples of the bias steps live in 12 registers (zeros written once) instead of being rebuilt per tile (10 v_mov_b32 in the matrix segment)
-#endif
-#ifndef A6C_MIN_KEYS
-#define A6C_MIN_KEYS 512   // ... and at least this many keys: on the 77-key cross-attention of the same token counts attn_d64b is faster
-#endif                     // (70 vs 89 us at 2 x 20 x 16 384 queries, 158 vs 178 at 2 x 10 x 65 536: prologue and tail are all there is)
 #ifndef A6C_MIN_WG
 #define A6C_MIN_WG 1024   // the ping-pong kernel is used when its grid (512 query rows per workgroup, one workgroup per CU) has at
 #endif                    // least this many workgroups (4 rounds of the 256 CUs): measured +2.3 % at 2 x 20 heads x 16 384 tokens (1 280
                           // workgroups), +4.5 % at 2 x 10 x 65 536 (2 560); 25 % SLOWER at 2 x 10 x 4 096 (160 workgroups)
+#ifndef A6C_MIN_KEYS
+#define A6C_MIN_KEYS 512   // ... and at least this many keys: on the 77-key cross-attention of the same token counts attn_d64b is faster
+#endif                     // (70 vs 89 us at 2 x 20 x 16 384 queries, 158 vs 178 at 2 x 10 x 65 536: prologue and tail are all there is)
 // MODE 0: C = 0 (first step of a chain, behind a VALU write), 1: accumulate, 2: accumulate behind a VALU write
 template <typename T, int MODE>
 __device__ __forceinline__ void a6c_mma(f32x16& acc, const typename Mfma<T>::v8& a, const typename Mfma<T>::v8& b) {
@@ -86,19 +47,18 @@ template <typename T>
 __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     constexpr int D = 64, NB = 4;
     typedef typename Mfma<T>::v8 v8;
-    typedef typename Mfma<T>::v4 v4;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // K[4] | V[4] | Q (8 waves x 64 rows): A6C_SMEM bytes
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int l31 = lane & 31, lh = lane >> 5;
     const int wu = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool late = A6C_ONEPATH ? (A6C_ONEPATH == 2) : wu >= 4;   // the second wave of its SIMD (A6C_ONEPATH: register-pressure diagnostics)
-    // XCD-aware work order (A6C_XCD_ORDER): workgroups are dealt to the 8 XCDs round-robin by their linear id, so with the plain
+    const bool late = wu >= 4;   // the second wave of its SIMD
+    // XCD-aware work order: workgroups are dealt to the 8 XCDs round-robin by their linear id, so with the plain
     // (query block, head, batch) grid the 256 concurrent workgroups spread EVERY head over all 8 L2s (at 2 x 20 heads x 16 384
     // tokens: 8 heads x 4 MB of K / V per 4 MiB L2, four CUs per stream).  Here each XCD walks a contiguous run of (head, query
     // block) items (the scheme of the conv / GEMM kernels): its 32 CUs work on the same head's K / V stream in step.
-    int qblk = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    if (A6C_XCD_ORDER) {
+    int qblk, h, b;
+    {
         const int nqb = gridDim.x, nwg = gridDim.x * gridDim.y * gridDim.z;
         const int lid = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
         const int q = nwg >> 3, r = nwg & 7, xcd = lid & 7, slot = lid >> 3;
@@ -121,13 +81,9 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     const uint32_t kswz = (uint32_t)(((lane & 7) ^ ((r16 >> 1) & 7)) << 4), vswz = (uint32_t)(((lane & 7) ^ (((r16 >> 1) & 1) << 2)) << 4);
     const uint32_t kvo = (uint32_t)(drow * k_rowb) + kswz, vvo = (uint32_t)(drow * v_rowb) + vswz;
     auto dma_fast = [&](const char* base, uint32_t voff, uint32_t dst) __attribute__((always_inline)) {
-#if A6C_M0_CLOBBER   // M0 declared clobbered instead of saved / restored (see A5B_M0_CLOBBER)
+        // M0 declared clobbered instead of saved / restored (the note on M0 in attention.hip; audited by tools/audit_m0.py): +1.1-1.2 %
+        // here (profiles/r03_attn_d64_ab.txt run 16), where attn_d64b lost 12 % with it
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
-#else
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-#endif
     };
     const char* k_next = (const char*)(Kb + (int64_t)(wu * 8) * p.k_ts);   // requests come in tile order: two pointer adds each
     const char* v_next = (const char*)(Vb + (int64_t)(wu * 8) * p.v_ts);
@@ -151,13 +107,12 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     if (nt > 1) dma_tile(1);
     if (nt > 2) dma_tile(2);
 
-    // ---- Q, pre-scaled by scale * log2(e) (bias step, see A6B_BIAS), parked in LDS: every lane stores the eight fragments it
+    // ---- Q, pre-scaled by scale * log2(e) (bias step, see attn_d64b), parked in LDS: every lane stores the eight fragments it
     // will need (B operand: col = query row on the lane, k = d) at the address it reads them back from in every S chain, in the
     // K-tile image (conflict-free ds_read_b128).  Held in registers the fragments cost 32 of the 256 for the whole kernel, and
     // hipcc spilled them to scratch around the early half's loop -- scratch reloads share vmcnt with the LDS-DMA prefetch.
     char* const Qs = smem + 2 * NB * A6B_TILE + wu * A6B_TILE;   // this wave's 64 rows x 128 B
     int koff[4];
-    v8 qf[2][4];   // (A6C_QREG only)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) koff[ks] = l31 * 128 + (((2 * ks + lh) ^ ((l31 >> 1) & 7)) << 4);
 #pragma unroll
@@ -170,8 +125,7 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
             v8 f = __builtin_bit_cast(v8, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = (T)((float)f[e] * p.scale_log2e);
-            if (A6C_QREG) qf[j][ks] = f;
-            else *(v8*)(Qs + j * 4096 + koff[ks]) = f;
+            *(v8*)(Qs + j * 4096 + koff[ks]) = f;
         }
     }
     f32x16 oacc[2][2];
@@ -212,13 +166,8 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
         KStep f;
         f.k0 = *(const v8*)(Ks + koff[ks]);
         f.k1 = *(const v8*)(Ks + 4096 + koff[ks]);
-        if (A6C_QREG) {
-            f.q0 = qf[0][ks];
-            f.q1 = qf[1][ks];
-        } else {
-            f.q0 = *(const v8*)(Qs + koff[ks]);
-            f.q1 = *(const v8*)(Qs + 4096 + koff[ks]);
-        }
+        f.q0 = *(const v8*)(Qs + koff[ks]);
+        f.q1 = *(const v8*)(Qs + 4096 + koff[ks]);
         return f;
     };
     auto read_v = [&](int t) __attribute__((always_inline)) {
@@ -234,39 +183,18 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
                 vf[dt][s4] = __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
             }
     };
-    auto read_v_part = [&](int t, int n) __attribute__((always_inline)) {   // fragments 2n, 2n + 1 of the eight (A6C_VINM)
-        const int vb = (t & (NB - 1)) * A6B_TILE;
-#pragma unroll
-        for (int e = 2 * n; e < 2 * n + 2; ++e) {
-            const int dt = e >> 2, s4 = e & 3;
-            const int off = vb + voff[dt] + s4 * 2048;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off + 1024));
-            typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-            vf[dt][s4] = __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-    };
-    u32x4 ones_t = {one_lo, 0u, 0u, 0u}, bias_t[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};   // (A6C_BIASREG only)
-    if (A6C_BIASREG) asm volatile("" : "+v"(ones_t), "+v"(bias_t[0]), "+v"(bias_t[1]));
-    auto bias_operands = [&](int j, v8& onesf, v8& biasf) __attribute__((always_inline)) {   // see A6B_BIAS: A = 1 in k-slot 0, B = -m of the lane's query there
-        if (A6C_BIASREG) {
-            T pair[2] = {(T)(-m_run[j]), (T)0.f};
-            uint32_t b0;
-            __builtin_memcpy(&b0, pair, 4);
-            bias_t[j][0] = b0;
-            asm volatile("" : "+v"(ones_t), "+v"(bias_t[j]));   // the tuples stay where they are: no copies
-            onesf = __builtin_bit_cast(v8, ones_t);
-            biasf = __builtin_bit_cast(v8, bias_t[j]);
-            return;
-        }
-        uint32_t zr;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(zr));
+    // the three operand tuples of the bias steps live in 12 registers, zeros written once (rebuilt per tile: 10 v_mov_b32 in the matrix segment)
+    u32x4 ones_t = {one_lo, 0u, 0u, 0u}, bias_t[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    asm volatile("" : "+v"(ones_t), "+v"(bias_t[0]), "+v"(bias_t[1]));
+    auto bias_operands = [&](int j, v8& onesf, v8& biasf) __attribute__((always_inline)) {   // A = 1 in k-slot 0, B = -m of the lane's query there
         T pair[2] = {(T)(-m_run[j]), (T)0.f};
         uint32_t b0;
         __builtin_memcpy(&b0, pair, 4);
-        const u32x4 av = {one_lo, zr, zr, zr}, bv = {b0, zr, zr, zr};
-        onesf = __builtin_bit_cast(v8, av);
-        biasf = __builtin_bit_cast(v8, bv);
+        bias_t[j][0] = b0;
+        asm volatile("" : "+v"(ones_t), "+v"(bias_t[j]));   // the tuples stay where they are: no copies
+        onesf = __builtin_bit_cast(v8, ones_t);
+        biasf = __builtin_bit_cast(v8, bias_t[j]);
+        (void)one_lo;   // keeps one_lo in this closure: without the capture hipcc swaps two score register ranges (same instructions, other register numbers)
     };
     auto mask_tail = [&](int t, int j) __attribute__((always_inline)) {
         if ((t + 1) * 64 > p.Nk) {   // ragged last tile only (uniform branch)
@@ -282,7 +210,7 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     // S^T of tile t for BOTH query sub-tiles: four independent chains (j, half) of bias step + 4 k-steps, issued step-major so
     // that an MFMA never waits for the one before it; ``f0`` = the operands of k-step 0 (read by the caller, earlier), the
     // following steps' operands are read one step ahead
-    auto s_chains = [&](int t, KStep f0, bool not_last = false, bool vin = false) __attribute__((always_inline)) {
+    auto s_chains = [&](int t, KStep f0, bool not_last = false) __attribute__((always_inline)) {
         v8 onesf, b0f, b1f;
         bias_operands(0, onesf, b0f);
         bias_operands(1, onesf, b1f);
@@ -293,11 +221,9 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
         a6c_mma<T, 0>(sacc[1][1], onesf, b1f);
         KStep f[4];
         f[0] = f0;
-        if (A6C_AHEAD == 2) f[1] = read_step(t, 1);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (ks + A6C_AHEAD < 4) f[ks + A6C_AHEAD] = read_step(t, ks + A6C_AHEAD);
-            if (A6C_VINM && vin) read_v_part(t, ks);
+            if (ks + 1 < 4) f[ks + 1] = read_step(t, ks + 1);
             __builtin_amdgcn_sched_barrier(0);
             a6c_mma<T, 1>(sacc[0][0], f[ks].k0, f[ks].q0);
             a6c_mma<T, 1>(sacc[1][0], f[ks].k0, f[ks].q1);
@@ -376,38 +302,21 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) asm volatile("" : "+v"(pf[j][s4]));   // converted HERE (hipcc otherwise sinks the 32 cvt_pk into the next matrix segment)
     };
-    // sum-checked softmax of tile t (see A6B_SUMCHK), -> pf.  A6C_JOINT: the exponentials and row sums of BOTH sub-tiles first,
-    // then ONE wave-uniform branch for the rare redo (the decision per sub-tile is unchanged): one reduction tail + compare +
-    // scalar branch per tile instead of two, in a segment with nobody to hide them behind.
+    // sum-checked softmax of tile t (see attn_d64b's loop), -> pf.  The exponentials and row sums of BOTH sub-tiles first, then ONE
+    // wave-uniform branch for the rare redo (the decision per sub-tile is unchanged): one reduction tail + compare + scalar branch
+    // per tile instead of two, in a segment with nobody to hide them behind.
     auto softmax = [&](int t) __attribute__((always_inline)) {
-        if (A6C_JOINT) {
-            float alpha0 = 1.0f, alpha1 = 1.0f;
-            float rs0 = exp_and_sum(0), rs1 = exp_and_sum(1);
-            const bool need0 = (t == 0) || !(rs0 <= 16384.0f), need1 = (t == 0) || !(rs1 <= 16384.0f);
-            if (!A6C_NOREDO && __builtin_expect(__any(need0 || need1), 0)) {   // (cold: laid out behind the loop, the hot path falls through)
-                if (__any(need0)) redo(t, 0, rs0, alpha0);
-                if (__any(need1)) redo(t, 1, rs1, alpha1);
-            }
-            l_run[0] = l_run[0] * alpha0 + rs0;
-            l_run[1] = l_run[1] * alpha1 + rs1;
-            to_p(0);
-            if (A6C_VEARLY) {
-                __builtin_amdgcn_sched_barrier(0);
-                read_v(t);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            to_p(1);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float alpha = 1.0f;
-                float rs = exp_and_sum(j);
-                const bool need = (t == 0) || !(rs <= 16384.0f);
-                if (!A6C_NOREDO && __builtin_expect(__any(need), 0)) redo(t, j, rs, alpha);
-                l_run[j] = l_run[j] * alpha + rs;
-                to_p(j);
-            }
+        float alpha0 = 1.0f, alpha1 = 1.0f;
+        float rs0 = exp_and_sum(0), rs1 = exp_and_sum(1);
+        const bool need0 = (t == 0) || !(rs0 <= 16384.0f), need1 = (t == 0) || !(rs1 <= 16384.0f);
+        if (__builtin_expect(__any(need0 || need1), 0)) {   // (cold: laid out behind the loop, the hot path falls through)
+            if (__any(need0)) redo(t, 0, rs0, alpha0);
+            if (__any(need1)) redo(t, 1, rs1, alpha1);
         }
+        l_run[0] = l_run[0] * alpha0 + rs0;
+        l_run[1] = l_run[1] * alpha1 + rs1;
+        to_p(0);
+        to_p(1);
     };
     // O^T[d][q] += V^T P^T, one 16-key step for both sub-tiles and both d halves (four independent accumulators)
     auto pv_first = [&]() __attribute__((always_inline)) {
@@ -427,13 +336,13 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
 #define A6C_MARK(i) do { if (A6B_STAMP) { const unsigned long long now_ = a6b_stamp(); st_sum[i] += now_ - st_t; st_t = now_; } } while (0)
     // M(i): PV(i), S(i + 1); the K fragments of tile i + 1 and the request of tile i + 3 go into the gaps behind the first MFMAs
     auto m_part = [&](int i, bool req, bool steady = false) __attribute__((always_inline)) {   // steady (a literal): tile i + 3 exists and is full, tile i + 1 is not the last
-        if (A6C_PRIO == 1) asm volatile("s_setprio 1");
+        asm volatile("s_setprio 1");   // around the matrix segment only
         __builtin_amdgcn_sched_barrier(0);
         if (!(A6C_ABL & 16)) pv_first();
         __builtin_amdgcn_sched_barrier(0);
         if (!(A6C_ABL & 16)) pv_step(1);
         __builtin_amdgcn_sched_barrier(0);
-        if ((steady || req) && !(A6C_ABL & 1) && !A6C_DMA_IN_V) dma_tile(i + 3, steady);
+        if ((steady || req) && !(A6C_ABL & 1)) dma_tile(i + 3, steady);
         __builtin_amdgcn_sched_barrier(0);
         if (!(A6C_ABL & 16)) pv_step(2);
         __builtin_amdgcn_sched_barrier(0);
@@ -441,21 +350,15 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
         __builtin_amdgcn_sched_barrier(0);
         if (!(A6C_ABL & 16)) pv_step(3);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(A6C_ABL & 16)) s_chains(i + 1, f0, steady, true);
-        if (A6C_PRIO == 1) asm volatile("s_setprio 0");
+        if (!(A6C_ABL & 16)) s_chains(i + 1, f0, steady);
+        asm volatile("s_setprio 0");
         A6C_MARK(0);
     };
     // V(t): softmax of tile t -> P, then the V fragments of tile t for the PV that follows in this wave's next M
     auto v_part = [&](int t) __attribute__((always_inline)) {
-        if (A6C_DMA_IN_V && !(A6C_ABL & 1)) {   // experiment: this period's request here (tile t + 2 for the early half, whose M(t - 1) opened the period)
-            const int rt = late ? t + 3 : t + 2;
-            if (rt < nt) dma_tile(rt);
-        }
-        if (A6C_PRIO == 2) asm volatile("s_setprio 1");
         if (!(A6C_ABL & 8)) softmax(t);
-        __builtin_amdgcn_sched_barrier(0);   // (V reads hoisted above the softmax would hold 32 more registers through it)
-        if (!(A6C_VEARLY && A6C_JOINT) && !A6C_VINM) read_v(t);
-        if (A6C_PRIO == 2) asm volatile("s_setprio 0");
+        __builtin_amdgcn_sched_barrier(0);   // (V reads hoisted above the softmax would hold 32 more registers through it; between the two P
+        read_v(t);                           //  conversions they lost 7.5 %, in the matrix segment's issue slots they gained nothing: profiles/r05_attn_d64_ab.txt)
         __builtin_amdgcn_sched_barrier(0);
         A6C_MARK(1);
     };
@@ -480,19 +383,14 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     int t = 0;
     if (!late) {
         softmax(0);
-        if (!(A6C_VEARLY && A6C_JOINT)) read_v(0);
+        read_v(0);
         seg_barrier();   // the early half enters period 0 one softmax ahead
         m_part(0, 3 < nt);
         t = 1;
     } else {
-        if (A6C_VINM) read_v(0);
         seg_barrier();
     }
-    // (the late half's prologue reloads four spilled score registers behind its barrier: waited for HERE, or hipcc keeps their vmcnt waits
-    //  inside the loop body, where they would count the LDS-DMA requests in flight)
-    if (A6C_VINM) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     if (A6B_STAMP) st_t = a6b_stamp();
-#if A6C_STEADY_LOOP
     // steady state (tile t + 3 exists and is full): the same body with its five uniform branches per tile folded away -- around
     // the request, its fast / ragged forms, the two ragged-tile masks and the two forms of the counted wait
     for (; t + 4 < nt; ++t) {
@@ -501,7 +399,6 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
         m_part(t, true, true);
         if (late) period_end(true);
     }
-#endif
     for (; t + 1 < nt; ++t) {
         v_part(t);
         if (!late) period_end(t + 2 < nt);    // closes the period of M(t - 1) (request of tile t + 2), V(t)
@@ -516,7 +413,7 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
         d[5] = (unsigned long long)(nt - 1);
     }
     softmax(nt - 1);
-    if (!(A6C_VEARLY && A6C_JOINT) && !A6C_VINM) read_v(nt - 1);
+    read_v(nt - 1);
     if (!late) seg_barrier();   // the early half's barrier count: 1 + (nt - 2) + this one = the late half's 1 + (nt - 1)
     pv_first();   // PV of the last tile
     pv_step(1);

@@ -6,7 +6,7 @@ compositions are ``ops.SplitPolicy`` arguments of the owning network, launch-pla
 
     RSVLD_CONV_TILE / RSVLD_CONV_STAGES / RSVLD_CONV_KSPLIT / RSVLD_CONV_STAGING / RSVLD_HALO_NW /
     RSVLD_GEMM256_OFF / RSVLD_GEMM256_ONE_TILE   -> LaunchContext.tune   (rsvld_conv_desc.tune: every combination computes the same function)
-    RSVLD_D64_KERNEL=b|c|p                        -> LaunchContext.d64_kernel (the three bit-identical forms of the d = 64 attention)
+    RSVLD_D64_KERNEL=b|c                          -> LaunchContext.d64_kernel (the two bit-identical forms of the d = 64 attention)
     RSVLD_D512_KERNEL=rows|dsplit                 -> LaunchContext.d512_kernel (the two bit-identical shared-tile d = 512 forms)
     RSVLD_PROFILE_DETAIL=1                        -> LaunchContext.profile_detail (layer shapes in the profiler group names)
     RSVLD_HALO_MIN_WGS=n                          -> LaunchContext.halo_min_wgs
@@ -36,8 +36,8 @@ def tune_from_env(e=None):
 
 
 def d64_kernel(name):
-    """"b" (four-wave), "c" (ping-pong), "p" (pipelined), "" = the library's choice -> this thread's base LaunchContext.d64_kernel."""
-    ops.set_defaults(d64_kernel={"b": 1, "c": 2, "p": 3}.get(name or "", 0))
+    """"b" (four-wave), "c" (ping-pong), "" = the library's choice -> this thread's base LaunchContext.d64_kernel."""
+    ops.set_defaults(d64_kernel={"b": 1, "c": 2}.get(name or "", 0))
 
 
 def d512_kernel(name):

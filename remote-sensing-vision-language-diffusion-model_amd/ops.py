@@ -106,7 +106,7 @@ class LaunchContext:
     ``tune``      developer A/B overrides -> rsvld_conv_desc.tune (every combination computes the same function); 0 = the library's choice.
     ``use_halo`` / ``halo_min_wgs`` / ``split_halo_min_wgs``   routing of eligible 3x3 convolutions through conv_halo.hip (below).
     ``split_d512_fused_min`` / ``split_attn_s_bytes``          form of the split-precision d != 64 attention (below).
-    ``d64_kernel``                                             developer A/B of the d = 64 attention's three bit-identical forms.
+    ``d64_kernel``                                             developer A/B of the d = 64 attention's two bit-identical forms.
     ``d512_kernel``                                            developer A/B of the shared-tile d = 512 attention's two bit-identical forms.
     ``profiler`` / ``profile_detail``   per-launch HIP-event bracketing (``LaunchProfiler``) and layer shapes in its group names.
 
@@ -122,7 +122,7 @@ class LaunchContext:
     def __init__(self, plan_div=1, policy=None, tune=0, use_halo=True, halo_min_wgs=256, split_halo_min_wgs=64,
                  split_d512_fused_min=2048, split_attn_s_bytes=32 << 30, profiler=None, profile_detail=False, d64_kernel=0,
                  d512_kernel=0):
-        # d64_kernel: developer A/B (devtools.d64_kernel): 1 / 2 / 3 = force attn_d64b / attn_d64c / attn_d64p (bit-identical forms)
+        # d64_kernel: developer A/B (devtools.d64_kernel): 1 / 2 = force attn_d64b / attn_d64c (bit-identical forms)
         # d512_kernel: developer A/B (devtools.d512_kernel): 4 / 5 = force attn_d512b / attn_d512d when keys = values (bit-identical)
         # use_halo: route eligible 3x3 convs through conv_halo.hip (False: A/B against the gather kernel)
         # halo_min_wgs 256: below one workgroup per CU the 8x32-pixel halo tile under-fills the chip (measured 130 vs 334 TFLOP/s on

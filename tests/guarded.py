@@ -15,7 +15,7 @@ lives in a buffer of its own,
 * guard size = max(1 MiB, ``TILE_ROWS`` row pitches of the placed tensor), rounded up to 256 bytes.  A missing clamp lets a lane
   read or write up to one workgroup's rows past the end of an operand, so the poison must reach that far.  ``TILE_ROWS`` = 512:
   the tile edges of the kernels are 256 rows (gemm256, conv_igemm_256x32), 128 / 64 (the other implicit-GEMM tiles), 8 x 32 and
-  16 x 32 pixels (conv_halo), 128 / 256 query rows and 64 keys (attn_d64b / d64p, the d = 512 kernels, split.hip), and -- the
+  16 x 32 pixels (conv_halo), 128 / 256 query rows and 64 keys (attn_d64b, the d = 512 kernels, split.hip), and -- the
   largest -- the 512 query rows one workgroup of attn_d64c walks (csrc/attention_d64c.inc, A6C_MIN_WG).
 
 ``Arena.place`` moves an operand in, ``torch_proxy`` makes ``rsvld_amd.ops`` allocate its outputs and workspaces in the arena

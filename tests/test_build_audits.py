@@ -27,6 +27,8 @@ def test_lds_dma_kernels_use_no_scratch(unit):
     from a runtime flag in its source selection).  No MFMA kernel of these units may contain a scratch instruction."""
     import audit_scratch
     res = audit_scratch.audit(unit)
-    assert len(res) >= 3, res
+    assert len(res) >= 3 or unit == "split.hip", res   # the MFMA kernels are really there
+    if unit == "split.hip":   # its two: the split attention kernels
+        assert len(res) == 2 and any("attn_split_d64_kernel" in k for k in res) and any("attn_split_d512_kernel" in k for k in res), res
     bad = {k: v for k, v in res.items() if v > 0}
     assert not bad, bad

@@ -341,7 +341,7 @@ def _attn64(form, shape, dtypes=(F16,)):
         return dict(fn=_attn_fn(heads, lambda: _d64(form)), operands=_attn_operands(dev, dt, B, heads, Nq, Nk, 64), prefix="attention_d64")
 
 
-for _form in ("b", "c", "p"):       # the three bit-identical d = 64 forms: each has its own K / V tile loads and its own store guard
+for _form in ("b", "c"):       # the two bit-identical d = 64 forms: each has its own K / V tile loads and its own store guard
     _attn64(_form, (1, 20, 64, 77), (F16, BF16))   # Nk = 77: 13 real keys in the second tile: "rows past Nk re-read the last key and are masked in the softmax"
     _attn64(_form, (2, 5, 100, 333))               # Nq and Nk ragged, batch 2
     _attn64(_form, (3, 2, 1, 1))                   # one query, one key

@@ -16,7 +16,7 @@ for rep in 1 2 3; do
     HEADLINE=1 ONLY64=1 REPS=20 RSVLD_LIB=$R/tools/ablate/librsvld_$v.so timeout -k 10 300 python3 tools/bench_attn.py >> "$log" 2>&1 || { echo "BENCH FAILED ($v)" >> "$log"; exit 1; }
   done
 done
-for v in d64c_stamp d64c_vinm_stamp; do
+for v in d64c_stamp; do
   [ -f tools/ablate/librsvld_$v.so ] || continue
   echo "== stamps: $v" >> "$log"
   RSVLD_D64_KERNEL=c RSVLD_LIB=$R/tools/ablate/librsvld_$v.so timeout -k 10 300 python3 tools/stamp_attn.py >> "$log" 2>&1 || echo "STAMPS FAILED" >> "$log"
