@@ -51,6 +51,7 @@ struct GemmArgs {
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
+template <int MASK> using Pieces = std::integral_constant<int, MASK>;   // (mma_tile: which LDS-DMA pieces a multiply slot issues)
 
 constexpr int G_STAGE = 32 * 1024;   // X: 256 rows x 64 B | W: 256 rows x 64 B
 #ifndef G_ABL
@@ -58,56 +59,14 @@ constexpr int G_STAGE = 32 * 1024;   // X: 256 rows x 64 B | W: 256 rows x 64 B
                   // 8 the LDS-DMA source cycles over four K tiles (operands L2-resident: the K loop without memory latency),
                   // 16 no LDS-DMA pieces in the steady-state multiply slots beyond K tile 5 (the K loop without their issue cost; waits pass at once)
 #endif
-// G_ONEBAR = 1 (experiment, round 3): ONE barrier per K tile instead of two (see the loop).  Correct (kernel tests green) and within
-// +-1 % of the two-barrier form on all nine headline shapes at 20 repetitions each (profiles/r03_gemm_onebar_ab.txt): the mid-tile
-// barrier is not what the K loop loses.  On the K-dominated shape (32 768 x 5 120 -> 1 280) the kernel is level with the vendor GEMM
-// (862-891 vs 876-912 TFLOP/s); the gap is the unhidden epilogue at K <= 2 048 and the 20 % padding of N = 640 to three 256-wide tiles.  Off.
-#ifndef G_ONEBAR
-#define G_ONEBAR 0
-#endif
-#ifndef G_EPI_SPECIALISED
-#define G_EPI_SPECIALISED 1
-#endif
-#ifndef G_ASMDMA
-#define G_ASMDMA 1   // 1: LDS-DMA pieces as inline asm in the scalar-base form, steady-state loop without the "is there a tile to
-#endif               // request" branches (see dma_piece / the slot loops); 0: the round-2 form (builtin, per-lane 64-bit addresses)
-#ifndef G_STAGGER
-#define G_STAGGER 0   // experiment: first-round workgroups on every other CU start half a K loop late (s_sleep units per K tile),
-#endif                // so that the CUs' output bursts stop coinciding; 0 = off
-#ifndef G_ORDER2D
-#define G_ORDER2D 1   // tile order inside an XCD's run: 1 = blocks of 8 x 4 tiles (see the index computation), 0 = m fastest (rounds 2-3)
-#endif
-#ifndef G_DMA_SPLIT
-#define G_DMA_SPLIT 0     // experiment (round 4), persistent form: activation pieces of tile kt + 3 in the read slot of tile kt, weight pieces between
-                          // the MFMAs of its multiply slot (two and two instead of four in one slot).  Correct, and level with 0: see G_DMA_IN_READ.
-#endif
-#ifndef G_DMA_IN_READ
-#define G_DMA_IN_READ 0   // experiment (round 4), persistent form: the LDS-DMA pieces of tile kt + 3 in the READ slot of tile kt (1) instead of between the
-                          // MFMAs of its multiply slot (0).  Correct (kernel tests green) and level with 0 on all nine headline shapes, and so is
-                          // G_DMA_SPLIT (two and two): WHERE the pieces are issued does not matter.  Without them the K loop runs at the matrix pipe's
-                          // rate (-DG_ABL=16: 31.3 -> 26.6 us per tile at K = 1 280 = 1 026 cycles per K tile); a half tile's slots with 8 MFMAs and 3
-                          // pieces take as long as a whole tile's with 16 and 4.  What the pieces cost is LDS time: per K tile the CU reads 96 KiB of
-                          // fragments (<= 256 B/clk) and the pieces write 32 KiB (~64 B/clk): ~900 of the 1 024 cycles its 128 MFMAs take.
-                          // profiles/r04_gemm_dma_issue.txt.  Off.
-#endif
-#ifndef G_PAIR_XREAD
-#define G_PAIR_XREAD 1    // PAIRED K loop (round 5): the two ACTIVATION pieces of an even K' tile are issued in the read slot of the odd tile three
-                          // tiles before it (four fragment reads instead of twelve: the one slot with issue time to spare) and only its two weight
-                          // pieces between the MFMAs, so that EVERY multiply slot carries two pieces (0: four / two alternating).  An LDS-DMA piece
-                          // costs its wave 60-180 issue cycles; 16 MFMAs + four pieces overran the 512 cycles the partner's slot takes.
-#endif
-#ifndef G_RES_AHEAD
-#define G_RES_AHEAD 1     // persistent fp32 + residual epilogue: the residual pieces of this many 32 x 32 half-blocks are in flight ahead of the one being
-                          // stored.  2 and 3 measured (round 5, tools/bench_linear_w2.py, A-B-A-B): no change on any of the four to_out / ff.net.2 shapes
-                          // (157.9 / 157.7 / 157.8 us at 32 768 x 1 280 -> 1 280) -- with fp16 weights these GEMMs move 8 bytes per output element beside
-                          // 2 K FLOP and run at 3.8-4.3 TB/s of HBM traffic: bound by the bytes, not by the latency of the request rounds
-#endif
-#ifndef G_HALF_TILES
-#define G_HALF_TILES 1    // persistent form: the last partial round of an XCD's run as 128-row half tiles (see the tile enumeration); 0 = whole tiles
-#endif
-#ifndef G_GELU_PACKED
-#define G_GELU_PACKED 1   // persistent GEGLU epilogue: the pairwise GELU in packed fp32 arithmetic (gelu_erf2_f); 0 = the scalar form
-#endif
+// Settled experiments (rounds 2-5; their switches and alternative code are gone, the findings stay):
+//   * ONE barrier per K tile instead of two: within +-1 % on all nine headline shapes -- the mid-tile barrier is not what the K loop
+//     loses (profiles/r03_gemm_onebar_ab.txt).
+//   * Persistent form, the LDS-DMA pieces of tile kt + 3 in the read slot of tile kt, or two and two over both slots: level with the
+//     shipped placement between the MFMAs.  WHERE the pieces are issued does not matter; the 17 % the K loop loses to them
+//     (-DG_ABL=16 runs at the matrix pipe's rate) is their LDS time: per K tile the CU reads 96 KiB of fragments and the pieces
+//     write 32 KiB, ~900 of the 1 024 cycles its 128 MFMAs take (profiles/r04_gemm_dma_issue.txt).
+//   * First-round workgroups on every other CU starting half a K loop late: a null result (profiles/r03_gemm_stagger_ab.txt).
 #ifndef G_STAMP
 #define G_STAMP 0     // diagnostic build: thread 0 of every workgroup records s_memrealtime (100 MHz) at its phase boundaries + HW_ID into
 #endif                // g_stamp_buf (read back by rsvld_debug_gemm_stamps; tools/gemm_stamps.py) -- where a tile's time goes, and the gap
@@ -156,6 +115,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     typedef typename Mfma<T>::v8 v8;
     typedef typename std::conditional<SEG == 1, T, f16>::type TO;
     typedef typename Mfma<TO>::v4 v4;
+    typedef std::integral_constant<int, 4> Whole;   // 32-row blocks per group of a tile, as a tag: 256 rows,
+    typedef std::integral_constant<int, 2> Half;    // or the upper / lower 128 rows of a tile (PERSIST, see the tile enumeration)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -181,7 +142,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         if constexpr (PERSIST) {
             const int c = lid >> 3, qx = t_end - ts;
             const int fr = qx / t_step, rem = qx - fr * t_step;
-            const bool halves = G_HALF_TILES && !PAIRED && rem > 0 && 2 * rem <= t_step;   // (the paired K loop exists for whole tiles)
+            const bool halves = !PAIRED && rem > 0 && 2 * rem <= t_step;   // (the paired K loop exists for whole tiles)
             n_full = fr + ((!halves && c < rem) ? 1 : 0);
             if (halves && c < 2 * rem) {
                 t_half = ts + fr * t_step + (c >> 1);
@@ -191,7 +152,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         }
     }
     auto tile_of = [&](int t, int& tile_m, int& tile_n) {
-#if G_ORDER2D
         // the 32 workgroups an XCD runs at a time form a block of 8 (m) x up to 4 (n) tiles: an activation tile is fetched into that
         // L2 once per <= 4 workgroups and a weight tile once per 8, instead of 32 different activation tiles beside ONE weight tile
         // (1-D order: every activation byte crossed the fabric once per 256 output columns).  Column blocks of balanced width.
@@ -205,10 +165,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         const int dn = rr / h;
         tile_n = nfirst + dn;
         tile_m = 8 * mb + (rr - dn * h);
-#else
-        tile_n = t / nmt;
-        tile_m = t - tile_n * nmt;
-#endif
     };
     if (PERSIST && t_half >= 0) {   // a lower half that starts beyond M (the last row of tiles holds <= 128 rows) does not exist: its row offsets
         int tm, tn;                 // relative to the tile's first row would be negative, i.e. huge as the 32-bit unsigned offsets of the LDS-DMA pieces
@@ -230,12 +186,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     // wave pair instead of 24: this K loop is bound by LDS time (7 of the 8 cycles an MFMA takes), not by the matrix pipe.
     auto xk = [&](int kt) { return PAIRED ? (kt >> 1) : SEG == 3 ? (kt >= 2 * nk0 ? kt - nk0 : kt) : SEG == 2 ? (kt >= nk0 ? kt - nk0 : kt) : kt; };
     auto wk = [&](int kt) { return PAIRED ? (kt & 1) * nk0 + (kt >> 1) : kt; };   // weight row = [W_lo(K) | W_hi(K)]
-    if (G_STAGGER > 0 && !PERSIST) {
-        const int lid = blockIdx.x + blockIdx.y * gridDim.x;
-        if (lid < 256 && ((lid >> 3) & 1))
-            for (int i = 0; i < nk; ++i) __builtin_amdgcn_s_sleep(G_STAGGER);
-    }
-
     // ---- per tile: DMA roles.  Wave w fills rows 32w .. 32w+31 of X and of W: two wave-instructions of 16 rows x 64 B each.
     // lane -> (row = lane>>2, position = lane&3) holds source chunk position ^ ((row>>2)&3); rows past the end of the
     // tensor re-read its last row (their outputs are never stored)
@@ -307,11 +257,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
 #endif
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
     // j = 0..3: (X, W) x (rows 0..15, 16..31) of this wave's share of tile kt.
-    // G_ASMDMA: the builtin made hipcc form a per-lane 64-bit address for every piece -- a v_lshl_add_u64 INTO the fragment
-    // registers the four MFMAs in front of it had just read (a write-after-read wait on the matrix pipe in the middle of the
-    // MFMA slot) -- and a branch around every piece.  Here the tile's row base is a scalar (SGPR pair), the lane's row / swizzle
-    // offset a 32-bit VGPR that lives across the loop, and M0 (the LDS destination) is written inside the statement and
-    // declared clobbered: nothing else in this file uses M0 (tools/audit_m0.py checks the assembly).
+    // Inline asm in the scalar-base form: the builtin made hipcc form a per-lane 64-bit address for every piece -- a v_lshl_add_u64
+    // INTO the fragment registers the four MFMAs in front of it had just read (a write-after-read wait on the matrix pipe in the
+    // middle of the MFMA slot) -- and a branch around every piece (profiles/r03_gemm_asmdma_ab.txt).  Here the tile's row base is a
+    // scalar (SGPR pair), the lane's row / swizzle offset a 32-bit VGPR that lives across the loop, and M0 (the LDS destination) is
+    // written inside the statement and declared clobbered: nothing else in this file uses M0 (tools/audit_m0.py checks the assembly).
     // (the tile's row bases are wave-uniform by construction; behind the per-lane store guards of the persistent fp32 epilogue hipcc's
     //  uniformity analysis gave up on them and handed the asm statements VGPR pairs: readfirstlane states the fact -- in THAT instantiation
     //  only: it does not fold away where the value already lives in SGPRs (+59 instructions per kernel when applied everywhere))
@@ -321,24 +271,38 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
         return (const char*)(uintptr_t)(((uint64_t)hi << 32) | lo);
     };
-    auto dma_piece = [&](int kt, int j) {
-#if G_ASMDMA
-        const uint32_t dst = lds0 + (uint32_t)((kt & (G_NST - 1)) * G_STAGE + wave * 2048 + (j & 1) * 16384 + (j >> 1) * 1024);
+    // RB, the first argument of every tile helper = the 32-row blocks per group: Whole, or Half (PERSIST): 128 rows x 256 columns on
+    // the same eight waves: group g owns rows 64 g .. + 64 (two accumulators per column block: acc[ni][0..1]), 8 MFMAs per slot and
+    // wave, three pieces per K tile and wave: j = 0 (its 16 X rows), 1 and 3 (its W rows as in a whole tile).
+    // (dst: one sum per form, each in this order -- with the common terms factored out hipcc reassociates the scalar adds and every
+    //  kernel of the file moves by -3 .. +12 instruction lines)
+    auto dma_piece = [&](auto RB, int kt, int j) {
+        constexpr bool half = decltype(RB)::value == 2;
+        const uint32_t dst = lds0 + (uint32_t)(half ? (kt & (G_NST - 1)) * G_STAGE + ((j & 1) ? wave * 2048 + 16384 + (j >> 1) * 1024 : wave * 1024)
+                                                    : (kt & (G_NST - 1)) * G_STAGE + wave * 2048 + (j & 1) * 16384 + (j >> 1) * 1024);
         const int ktx = (G_ABL & 8) ? (kt & 3) : xk(kt);
         const char* base = uni((j & 1) ? Wb + ((G_ABL & 8) ? (kt & 3) : wk(kt)) * 64 : Xb + ktx * 64);
         const uint32_t voff = (j & 1) ? wvo[j >> 1] : xvo[j >> 1];
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
-#else
-        char* st = smem + (kt & (G_NST - 1)) * G_STAGE + wave * 2048 + (j & 1) * 16384 + (j >> 1) * 1024;
-        const int ktx = xk(kt);
-        const char* src = (j & 1) ? Wb + kt * 64 : Xb + ktx * 64;
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + ((j & 1) ? wvo[j >> 1] : xvo[j >> 1])), (lptr_t)st, 16, 0, 0);
-#endif
     };
-    auto dma_tile = [&](int kt) {
+    auto dma_tile = [&](auto RB, int kt) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (!PAIRED || !(kt & 1) || (j & 1)) dma_piece(kt, j);      // PAIRED: an odd tile is its two weight pieces
+            if ((decltype(RB)::value == 4 || j != 2) && (!PAIRED || !(kt & 1) || (j & 1))) dma_piece(RB, kt, j);   // PAIRED: an odd tile is its two weight pieces
+    };
+    // the first requests of tile t (hsel as in setup_tile): its bias row, then its K tiles 0..2 (PERSIST: nk >= 4)
+    auto request_tile = [&](int t, int hsel) {
+        setup_tile(t, hsel);
+        dma_bias(n0);
+        if (hsel < 0) {
+            dma_tile(Whole{}, 0);
+            dma_tile(Whole{}, 1);
+            dma_tile(Whole{}, 2);
+        } else {
+            dma_tile(Half{}, 0);
+            dma_tile(Half{}, 1);
+            dma_tile(Half{}, 2);
+        }
     };
 
     f32x16 acc[2][4];   // [n tile][m tile]
@@ -351,42 +315,38 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 for (int r = 0; r < 16; ++r) acc[ni][mi][r] = 0.f;
     }
 
-    int fa_off[2], fb_off[2];
+    int fa_off[2], fb_off[2], fbh_off[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
         fa_off[ks] = 16384 + g_off(wn * 64 + l31, 2 * ks + lh);     // weights: + ni * 2048
         fb_off[ks] = g_off(grp * 128 + l31, 2 * ks + lh);           // activations: + mi * 2048
     }
+    // activations of a half tile (a loop of its own: computed in the loop above, registers are numbered differently in the ten
+    // one-tile kernels and two of the paired ones, which never use it)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) fbh_off[ks] = g_off(grp * 64 + l31, 2 * ks + lh);
 
     v8 fa[2][2], fb[2][4];   // [k-step][tile]
-    auto read_tile = [&](int kt) {
+    auto read_tile = [&](auto RB, int kt) {
+        constexpr int MI = decltype(RB)::value;
         const char* st = smem + (kt & (G_NST - 1)) * G_STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) fa[ks][ni] = *(const v8*)(st + fa_off[ks] + ni * 2048);
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) fb[ks][mi] = *(const v8*)(st + fb_off[ks] + mi * 2048);
+            for (int mi = 0; mi < MI; ++mi) fb[ks][mi] = *(const v8*)(st + (MI == 2 ? fbh_off[ks] : fb_off[ks]) + mi * 2048);
         }
     };
-    // 16 MFMAs of the fragments in registers; the 4 LDS-DMAs of tile `next` (if >= 0) are issued between them: an
-    // LDS-DMA costs its wave 60-180 issue cycles, which the matrix pipe covers here and which would lengthen the
-    // partner group's critical read slot otherwise (measured: all four in the read slot -4 %, two and two -5 % at
-    // K >= 2560 against this placement)
-    auto mma_tile = [&](int next) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], acc[ni][mi]);
-                if (next >= 0) dma_piece(next, 2 * ks + ni);
-            }
-        __builtin_amdgcn_s_setprio(0);
-    };
-    // FIRST (PERSIST, K tile 0): the first k-step takes the bias registers as its C operand
-    auto mma_tile_dma = [&](int next, auto FIRST) {   // steady state: the tile to request always exists, no branch around the pieces
+    // A multiply slot: the 16 MFMAs (half tile: 8) of the fragments in registers, with LDS-DMA pieces of tile `next` between them:
+    // bit j of PIECES = piece j is issued behind the j-th group of MFMAs.  0xF a whole tile, 0xB a half tile, 0xA the two weight
+    // pieces (PAIRED), 0 none: the tail of every K loop (kt >= nk - 3: tile kt + 3 does not exist).  An LDS-DMA costs its wave 60-180
+    // issue cycles, which the matrix pipe covers here and which would lengthen the partner group's critical read slot otherwise
+    // (measured: all four in the read slot -4 %, two and two -5 % at K >= 2560 against this placement).  Steady state: the tile to
+    // request always exists, no branch around the pieces.  FIRST (PERSIST, K tile 0): the first k-step takes the bias registers as
+    // its C operand
+    auto mma_tile = [&](auto RB, auto PIECES, auto FIRST, int next = -1) {
+        constexpr int MI = decltype(RB)::value, pieces = decltype(PIECES)::value;
         constexpr bool first = decltype(FIRST)::value;
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -394,17 +354,20 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], (first && ks == 0) ? bC[ni] : acc[ni][mi]);
-                __builtin_amdgcn_sched_barrier(0);   // one piece after every fourth MFMA (hipcc otherwise moves the asm
-                if (!(G_ABL & 16) || next < 6) dma_piece(next, 2 * ks + ni);   // statements to the head of the slot, three of them behind the first MFMA)
-                __builtin_amdgcn_sched_barrier(0);
+                for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], (first && ks == 0) ? bC[ni] : acc[ni][mi]);
+                if ((pieces >> (2 * ks + ni)) & 1) {
+                    __builtin_amdgcn_sched_barrier(0);   // behind its group of MFMAs (hipcc otherwise moves the asm statements to the
+                    if (!(G_ABL & 16) || next < 6) dma_piece(RB, next, 2 * ks + ni);   // head of the slot, three of them behind the first MFMA)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
         __builtin_amdgcn_s_setprio(0);
     };
-    // own DMAs of tile kt+1 have landed; `ahead` later tiles of this wave may stay in flight (4 instructions per tile)
-    auto wait_ahead = [&](int ahead) {
-        if (ahead >= 2) g_wait_vm<8>();
-        else if (ahead == 1) g_wait_vm<4>();
+    // own DMAs of tile kt+1 have landed; `ahead` later tiles of this wave may stay in flight (4 instructions per tile, a half tile 3)
+    auto wait_ahead = [&](auto RB, int ahead) {
+        constexpr int PCS = decltype(RB)::value == 2 ? 3 : 4;   // a wave's pieces per K tile
+        if (ahead >= 2) g_wait_vm<2 * PCS>();
+        else if (ahead == 1) g_wait_vm<PCS>();
         else g_wait_vm<0>();
     };
     auto slot_end = [&]() {
@@ -413,67 +376,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // ---- HALF tiles (PERSIST): 128 rows x 256 columns on the same eight waves: group g owns rows 64 g .. + 64 (two 32-row accumulators
-    // per column block: acc[ni][0..1]), 8 MFMAs per slot and wave, three LDS-DMA pieces per K tile and wave (X: 16 rows, W: 2 x 16)
-    int fbh_off[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) fbh_off[ks] = g_off(grp * 64 + l31, 2 * ks + lh);
-    auto dma_piece_h = [&](int kt, int j) {   // j = 0: the wave's X rows; 1, 3: its W rows as in a whole tile
-        const uint32_t dst = lds0 + (uint32_t)((kt & (G_NST - 1)) * G_STAGE + ((j & 1) ? wave * 2048 + 16384 + (j >> 1) * 1024 : wave * 1024));
-        const char* base = uni((j & 1) ? Wb + kt * 64 : Xb + xk(kt) * 64);
-        const uint32_t voff = (j & 1) ? wvo[j >> 1] : xvo[0];
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
-    };
-    auto dma_tile_h = [&](int kt) {
-        dma_piece_h(kt, 0);
-        dma_piece_h(kt, 1);
-        dma_piece_h(kt, 3);
-    };
-    auto read_tile_h = [&](int kt) {
-        const char* st = smem + (kt & (G_NST - 1)) * G_STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) fa[ks][ni] = *(const v8*)(st + fa_off[ks] + ni * 2048);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) fb[ks][mi] = *(const v8*)(st + fbh_off[ks] + mi * 2048);
-        }
-    };
-    auto mma_tile_h = [&]() {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], acc[ni][mi]);
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto mma_tile_dma_h = [&](int next, auto FIRST) {
-        constexpr bool first = decltype(FIRST)::value;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], (first && ks == 0) ? bC[ni] : acc[ni][mi]);
-                if (2 * ks + ni != 2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    dma_piece_h(next, 2 * ks + ni);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto wait_ahead_h = [&](int ahead) {   // three instructions per K tile
-        if (ahead >= 2) g_wait_vm<6>();
-        else if (ahead == 1) g_wait_vm<3>();
-        else g_wait_vm<0>();
-    };
-
     // ---- prologue: three tiles in flight; the one-tile form keeps the tile's bias row in LDS beside the ring (the
-    // epilogue read it from global memory once per accumulator quad: a dependent L2 round trip at the head of every output burst)
+    // epilogue read it from global memory once per accumulator quad: a dependent L2 round trip at the head of every output burst).
+    // (PERSIST: request_tile's sequence, written out.  The call in its place -- with setup_tile moved here, or with only the requests
+    //  shared -- drops the two nk tests no persistent launch needs and moves all 31 persistent kernels: the 5 paired ones by -12 .. -15
+    //  instruction lines, the others by -219 .. +117 depending on where setup_tile lands)
     if (!PERSIST && tid < 64) {
         f32x4 bv = {0.f, 0.f, 0.f, 0.f};
         const int n = n0 + tid * 4;
@@ -482,13 +389,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     }
     if constexpr (PERSIST) dma_bias(n0);
     if (PERSIST && n_full == 0) {
-        dma_tile_h(0);
-        dma_tile_h(1);
-        dma_tile_h(2);
+        dma_tile(Half{}, 0);
+        dma_tile(Half{}, 1);
+        dma_tile(Half{}, 2);
     } else {
-        dma_tile(0);
-        if (nk > 1) dma_tile(1);
-        if (nk > 2) dma_tile(2);
+        dma_tile(Whole{}, 0);
+        if (nk > 1) dma_tile(Whole{}, 1);
+        if (nk > 2) dma_tile(Whole{}, 2);
     }
 
     if constexpr (PERSIST) {
@@ -509,11 +416,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         const int rbase = (lane >> 3) * 128 + (((lane & 7) ^ (lane >> 3)) << 4);            // block read: + i * 1024 (rows lane/8 + 8 i)
         const int gwbase = l31 * 64 + lh * 4, gx3 = (l31 & 3) << 4;                         // GEGLU: 32 rows x 64 B
         const int grbase = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 2) & 3)) << 4);      // GEGLU read: + i * 1024 (rows lane/4 + 16 i)
-        // One tile: HALF = false: a whole tile; true: a half tile (the helpers with the _h suffix, MI = 2 row blocks per group).
+        // One tile: RB = Whole or Half (MI = 4 or 2 row blocks per group).
         // t_next / h_next (< 0: whole) = the tile whose first pieces this tile's epilogue requests; has_next false: none.
-        auto run_tile = [&](auto HALF, const bool has_next, const int t_next, const int h_next) {
-            constexpr bool half = decltype(HALF)::value;
-            constexpr int MI = half ? 2 : 4;
+        auto run_tile = [&](auto RB, const bool has_next, const int t_next, const int h_next) {
+            constexpr int MI = decltype(RB)::value;
+            constexpr bool half = MI == 2;
+            constexpr int ALL = half ? 0xB : 0xF;   // a K tile's pieces (mma_tile)
             // own pieces of K tile 0 (tiles 1, 2 and, from the second tile on, the last stores may stay in flight)
             if constexpr (half || PAIRED) g_wait_vm<6>();      // (PAIRED: K tile 1 is two pieces per wave, K tile 2 four)
             else g_wait_vm<8>();
@@ -526,184 +434,22 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
             G_STAMP_AT(1);
             const unsigned long long stamp_c0 = __builtin_readcyclecounter();
 #endif
-            auto rd = [&](int kt) { if constexpr (half) read_tile_h(kt); else read_tile(kt); };
-            auto mm = [&]() { if constexpr (half) mma_tile_h(); else mma_tile(-1); };
-            auto mmd = [&](int next, auto FIRST) { if constexpr (half) mma_tile_dma_h(next, FIRST); else mma_tile_dma(next, FIRST); };
-            auto wa = [&](int ahead) { if constexpr (half) wait_ahead_h(ahead); else wait_ahead(ahead); };
-#if G_DMA_SPLIT
-            // The pieces of K tile kt + 3 in BOTH slots of tile kt: the activation pieces behind the fragment reads of the read slot, the
-            // weight pieces between the MFMAs of the multiply slot.  A piece costs its wave ~130 issue cycles: four of them beside 16 MFMAs
-            // (128 issue cycles) or beside 12 fragment reads overrun the 512 cycles the partner's MFMAs take; two and two stay inside.
-            // Exception: group 0's first read slot of a tile issues nothing (group 1 still fetches its bias rows from stage 3): all four
-            // pieces of K tile 3 in its first multiply slot.
-            auto dmx = [&](int kt) {
-                if constexpr (half) dma_piece_h(kt, 0);
-                else { dma_piece(kt, 0); dma_piece(kt, 2); }
-            };
-            auto mmw = [&](int next, auto FIRST, auto ALL) {   // the MFMAs of a tile with the weight pieces (ALL: every piece) of tile `next` between them
-                constexpr bool first = decltype(FIRST)::value, all = decltype(ALL)::value;
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-#pragma unroll
-                        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], (first && ks == 0) ? bC[ni] : acc[ni][mi]);
-                        const int j = 2 * ks + ni;
-                        if ((j & 1) || (all && !(half && j == 2))) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if constexpr (half) dma_piece_h(next, j); else dma_piece(next, j);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                __builtin_amdgcn_s_setprio(0);
-            };
-            constexpr int PX = half ? 1 : 2, PT = half ? 3 : 4;   // activation pieces / all pieces per wave and K tile
-            if (grp == 0) {
-                rd(0);
-                read_bias();
-                slot_end();
-                mmw(3, std::true_type{}, std::true_type{});
-                wa(2);
-                slot_end();
-                for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
-                    dmx(kt + 3);
-                    slot_end();
-                    mmw(kt + 3, std::false_type{}, std::false_type{});
-                    wa(2);
-                    slot_end();
-                }
-                for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
-                    slot_end();
-                    mm();
-                    wa(max(nk - 2 - kt, 0));
-                    slot_end();
-                }
-            } else {
-                read_bias();
-                slot_end();
-                rd(0);
-                dmx(3);
-                g_wait_vm<PT + PX>();      // K tile 1 has landed; tile 2 and the activation pieces of tile 3 may stay in flight
-                slot_end();
-                mmw(3, std::true_type{}, std::false_type{});
-                slot_end();
-                for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
-                    dmx(kt + 3);
-                    g_wait_vm<PT + PX>();
-                    slot_end();
-                    mmw(kt + 3, std::false_type{}, std::false_type{});
-                    slot_end();
-                }
-                for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
-                    wa(max(nk - 2 - kt, 0));
-                    slot_end();
-                    mm();
-                    if (kt != nk - 1) slot_end();
-                }
-            }
-#elif G_DMA_IN_READ
-            // The LDS-DMA pieces of K tile kt + 3 are issued in the READ slot of tile kt, behind the fragment reads (their issue -- 60-180
-            // cycles each -- then runs under the LDS latency the reading wave waits for anyway, and the multiply slot is 16 bare MFMAs):
-            // with the pieces between the MFMAs the K loop ran at 83 % of the matrix pipe's rate and at 100 % without them
-            // (-DG_ABL=16, tools/gemm_stamps.py).  The stage of tile kt + 3 held tile kt - 1, whose last fragment reads (group 1's,
-            // in the slot before) returned before the barrier that opened this slot.  Exception: group 0 requests K tile 3 at the head
-            // of its first MULTIPLY slot -- in its first read slot group 1 still fetches its bias rows from that stage.
-            auto dm = [&](int kt) { if constexpr (half) dma_tile_h(kt); else dma_tile(kt); };
-            auto mmf = [&]() {   // K tile 0: the bias rows as C operand of the first k-step
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], ks == 0 ? bC[ni] : acc[ni][mi]);
-                __builtin_amdgcn_s_setprio(0);
-            };
-            if (grp == 0) {
-                rd(0);
-                read_bias();
-                slot_end();
-                dm(3);
-                mmf();
-                wa(2);
-                slot_end();
-                for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
-                    dm(kt + 3);
-                    slot_end();
-                    mm();
-                    wa(2);
-                    slot_end();
-                }
-                for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
-                    slot_end();
-                    mm();
-                    wa(max(nk - 2 - kt, 0));
-                    slot_end();
-                }
-            } else {
-                read_bias();
-                slot_end();
-                rd(0);
-                dm(3);
-                wa(2);
-                slot_end();
-                mmf();
-                slot_end();
-                for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
-                    dm(kt + 3);
-                    wa(2);
-                    slot_end();
-                    mm();
-                    slot_end();
-                }
-                for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
-                    wa(max(nk - 2 - kt, 0));
-                    slot_end();
-                    mm();
-                    if (kt != nk - 1) slot_end();
-                }
-            }
-#else
             if constexpr (PAIRED) {
                 // ---- PAIRED K loop (see PAIRED above).  Same slots, same barriers, same ring as the loop below; K' tile kt = 2 p + o:
                 //   o = 0: four pieces (X(p) | W_lo(p)), 12 fragment reads;   o = 1: two pieces (W_hi(p)), 4 fragment reads, fb kept from tile 2 p.
                 // Pieces in flight behind tile kt + 1: tiles kt + 2, kt + 3 = 6 pieces whatever the parity (group 0: vmcnt(6)); tile kt + 2
                 // alone = 4 behind an even kt, 2 behind an odd one (group 1, compile-time by a loop unrolled over the pair).  nk is even and
                 // >= 4, nk_main = nk - 3 is odd: the steady-state trips kt = 1 .. nk - 4 are whole (odd, even) pairs.
+                // The two ACTIVATION pieces of an even tile are issued in the read slot of the odd tile three tiles before it (four fragment
+                // reads instead of twelve: the one slot with issue time to spare) and only its two weight pieces between the MFMAs, so that
+                // EVERY multiply slot carries two pieces: a piece costs its wave 60-180 issue cycles, and 16 MFMAs + four pieces overran the
+                // 512 cycles the partner's slot takes (+1.2-1.6 % against four / two alternating, profiles/r05_gemm_w2_stamps.txt).
                 auto rd_w = [&](int kt) {           // an odd tile: its weight fragments only
                     const char* st = smem + (kt & (G_NST - 1)) * G_STAGE;
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                         for (int ni = 0; ni < 2; ++ni) fa[ks][ni] = *(const v8*)(st + fa_off[ks] + ni * 2048);
-                };
-                // the 16 MFMAs of the tile in registers with the pieces of tile `next` between them: all four (NEXT_W = false: an even
-                // tile) or its two weight pieces (an odd one)
-                auto mmp = [&](int next, auto FIRST, auto NEXT_W) {
-                    constexpr bool first = decltype(FIRST)::value, next_w = decltype(NEXT_W)::value;
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                        for (int ni = 0; ni < 2; ++ni) {
-#pragma unroll
-                            for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = Mfma<T>::mma(fa[ks][ni], fb[ks][mi], (first && ks == 0) ? bC[ni] : acc[ni][mi]);
-                            if (!next_w || ((2 * ks + ni) & 1)) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                dma_piece(next, 2 * ks + ni);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
-                    __builtin_amdgcn_s_setprio(0);
                 };
                 auto wait_pieces = [&](int n) {     // tail only: n in {0, 2, 4, 6}
                     if (n >= 6) g_wait_vm<6>();
@@ -713,115 +459,108 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 };
                 auto pcs = [&](int kt) { return kt >= nk ? 0 : ((kt & 1) ? 2 : 4); };   // pieces of tile kt per wave
                 if (grp == 0) {
-                    read_tile(0);
+                    read_tile(Whole{}, 0);
                     read_bias();
                     slot_end();
-                    mmp(3, std::true_type{}, std::true_type{});
+                    mma_tile(Whole{}, Pieces<0xA>{}, std::true_type{}, 3);
                     g_wait_vm<6>();
                     slot_end();
                     for (int kt = 1; kt < nk_main; kt += 2) {
                         rd_w(kt);
-                        if (G_PAIR_XREAD) {
-                            dma_piece(kt + 3, 0);
-                            dma_piece(kt + 3, 2);
-                        }
+                        dma_piece(Whole{}, kt + 3, 0);
+                        dma_piece(Whole{}, kt + 3, 2);
                         slot_end();
-                        mmp(kt + 3, std::false_type{}, std::integral_constant<bool, G_PAIR_XREAD != 0>{});
+                        mma_tile(Whole{}, Pieces<0xA>{}, std::false_type{}, kt + 3);
                         g_wait_vm<6>();
                         slot_end();
-                        read_tile(kt + 1);
+                        read_tile(Whole{}, kt + 1);
                         slot_end();
-                        mmp(kt + 4, std::false_type{}, std::true_type{});
+                        mma_tile(Whole{}, Pieces<0xA>{}, std::false_type{}, kt + 4);
                         g_wait_vm<6>();
                         slot_end();
                     }
                     for (int kt = nk_main; kt < nk; ++kt) {
-                        if (kt & 1) rd_w(kt); else read_tile(kt);
+                        if (kt & 1) rd_w(kt); else read_tile(Whole{}, kt);
                         slot_end();
-                        mma_tile(-1);
+                        mma_tile(Whole{}, Pieces<0>{}, std::false_type{});
                         wait_pieces(pcs(kt + 2) + pcs(kt + 3));     // tile kt + 1 landed (nothing beyond nk - 1 was requested)
                         slot_end();
                     }
                 } else {
                     read_bias();
                     slot_end();
-                    read_tile(0);
+                    read_tile(Whole{}, 0);
                     g_wait_vm<4>();                                  // tile 1 landed; tile 2 (four pieces) may stay in flight
                     slot_end();
-                    mmp(3, std::true_type{}, std::true_type{});
+                    mma_tile(Whole{}, Pieces<0xA>{}, std::true_type{}, 3);
                     slot_end();
                     for (int kt = 1; kt < nk_main; kt += 2) {
                         rd_w(kt);
-                        if (G_PAIR_XREAD) {
-                            dma_piece(kt + 3, 0);
-                            dma_piece(kt + 3, 2);
-                            g_wait_vm<4>();                          // tile kt + 1 landed; tile kt + 2 (odd: two pieces) and these two in flight
-                        } else {
-                            g_wait_vm<2>();                          // tile kt + 1 landed; tile kt + 2 (odd: two pieces) in flight
-                        }
+                        dma_piece(Whole{}, kt + 3, 0);
+                        dma_piece(Whole{}, kt + 3, 2);
+                        g_wait_vm<4>();                          // tile kt + 1 landed; tile kt + 2 (odd: two pieces) and these two in flight
                         slot_end();
-                        mmp(kt + 3, std::false_type{}, std::integral_constant<bool, G_PAIR_XREAD != 0>{});
+                        mma_tile(Whole{}, Pieces<0xA>{}, std::false_type{}, kt + 3);
                         slot_end();
-                        read_tile(kt + 1);
+                        read_tile(Whole{}, kt + 1);
                         g_wait_vm<4>();                              // tile kt + 2 landed; tile kt + 3 (even: four pieces) in flight
                         slot_end();
-                        mmp(kt + 4, std::false_type{}, std::true_type{});
+                        mma_tile(Whole{}, Pieces<0xA>{}, std::false_type{}, kt + 4);
                         slot_end();
                     }
                     for (int kt = nk_main; kt < nk; ++kt) {
-                        if (kt & 1) rd_w(kt); else read_tile(kt);
+                        if (kt & 1) rd_w(kt); else read_tile(Whole{}, kt);
                         wait_pieces(pcs(kt + 2));                    // this group has requested up to tile min(kt + 2, nk - 1)
                         slot_end();
-                        mma_tile(-1);
+                        mma_tile(Whole{}, Pieces<0>{}, std::false_type{});
                         if (kt != nk - 1) slot_end();
                     }
                 }
             } else
             if (grp == 0) {
-                rd(0);
+                read_tile(RB, 0);
                 read_bias();
                 slot_end();
-                mmd(3, std::true_type{});
-                wa(2);
+                mma_tile(RB, Pieces<ALL>{}, std::true_type{}, 3);
+                wait_ahead(RB, 2);
                 slot_end();
                 for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
+                    read_tile(RB, kt);
                     slot_end();
-                    mmd(kt + 3, std::false_type{});
-                    wa(2);
+                    mma_tile(RB, Pieces<ALL>{}, std::false_type{}, kt + 3);
+                    wait_ahead(RB, 2);
                     slot_end();
                 }
                 for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
+                    read_tile(RB, kt);
                     slot_end();
-                    mm();
-                    wa(min(nk - 1, kt + 3) - (kt + 1));
+                    mma_tile(RB, Pieces<0>{}, std::false_type{});
+                    wait_ahead(RB, min(nk - 1, kt + 3) - (kt + 1));
                     slot_end();
                 }
             } else {
                 read_bias();     // (before group 0's first multiply slot, which requests K tile 3 into the stage that holds the bias rows)
                 slot_end();
-                rd(0);
-                wa(1);
+                read_tile(RB, 0);
+                wait_ahead(RB, 1);
                 slot_end();
-                mmd(3, std::true_type{});
+                mma_tile(RB, Pieces<ALL>{}, std::true_type{}, 3);
                 slot_end();
                 for (int kt = 1; kt < nk_main; ++kt) {
-                    rd(kt);
-                    wa(1);
+                    read_tile(RB, kt);
+                    wait_ahead(RB, 1);
                     slot_end();
-                    mmd(kt + 3, std::false_type{});
+                    mma_tile(RB, Pieces<ALL>{}, std::false_type{}, kt + 3);
                     slot_end();
                 }
                 for (int kt = nk_main; kt < nk; ++kt) {
-                    rd(kt);
-                    wa(min(nk - 1, kt + 2) - (kt + 1));
+                    read_tile(RB, kt);
+                    wait_ahead(RB, min(nk - 1, kt + 2) - (kt + 1));
                     slot_end();
-                    mm();
+                    mma_tile(RB, Pieces<0>{}, std::false_type{});
                     if (kt != nk - 1) slot_end();
                 }
             }
-#endif
             G_STAMP_AT(2);
 #if G_STAMP
             if (threadIdx.x == 0 && stamp_lid < 16384) g_stamp_buf[stamp_lid * 8 + 6] = __builtin_readcyclecounter() - stamp_c0;
@@ -839,18 +578,18 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 // pieces of half-block hb + 1 are requested before half-block hb is read back.  The next tile's ring pieces are requested
                 // FIRST: every later wait for a residual piece (a load the compiler sees and counts) then covers them -- vmcnt retires
                 // in order -- and they have the whole epilogue to land in.
-                if (has_next) {
-                    setup_tile(t_next, h_next);
-                    dma_bias(n0);
-                    if (h_next < 0) { dma_tile(0); dma_tile(1); dma_tile(2); }
-                    else { dma_tile_h(0); dma_tile_h(1); dma_tile_h(2); }
-                }
+                if (has_next) request_tile(t_next, h_next);
                 const int rrow = lane >> 3, rchunk = lane & 7;
                 const int wb32 = l31 * 128, x7w = l31 & 7;
                 const int rb32 = rrow * 128 + ((rchunk ^ (rrow & 7)) << 4);        // + i * 1024: rows rrow + 8 i (same row & 7)
                 const int ncol = n0e + wn * 64 + 4 * rchunk;                        // + 32 ni
                 const int mrow = m0e + grp * (32 * MI) + rrow;                      // + 32 mi + 8 i
-                f32x4 rvp[G_RES_AHEAD + 1][4];
+                // The residual pieces of RES_AHEAD 32 x 32 half-blocks are in flight ahead of the one being stored.  2 and 3 measured (round 5,
+                // tools/bench_linear_w2.py, A-B-A-B): no change on any of the four to_out / ff.net.2 shapes (157.9 / 157.7 / 157.8 us at
+                // 32 768 x 1 280 -> 1 280) -- with fp16 weights these GEMMs move 8 bytes per output element beside 2 K FLOP and run at
+                // 3.8-4.3 TB/s of HBM traffic: bound by the bytes, not by the latency of the request rounds
+                constexpr int RES_AHEAD = 1;
+                f32x4 rvp[RES_AHEAD + 1][4];
                 auto load_res = [&](int hb, f32x4 (&r)[4]) {
                     const int n = ncol + (hb & 1) * 32;
 #pragma unroll
@@ -860,7 +599,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                     }
                 };
 #pragma unroll
-                for (int a = 0; a < G_RES_AHEAD; ++a) load_res(a, rvp[a]);
+                for (int a = 0; a < RES_AHEAD; ++a) load_res(a, rvp[a]);
 #pragma unroll
                 for (int hb = 0; hb < 2 * MI; ++hb) {
                     const int mi = hb >> 1, ni = hb & 1;
@@ -871,14 +610,14 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                         for (int e = 0; e < 4; ++e) v[e] = acc[ni][mi][4 * g + e] * p.alpha;
                         *(f32x4*)(P + wb32 + (((2 * g + lh) ^ x7w) << 4)) = v;
                     }
-                    if (hb + G_RES_AHEAD < 2 * MI) load_res(hb + G_RES_AHEAD, rvp[(hb + G_RES_AHEAD) % (G_RES_AHEAD + 1)]);
+                    if (hb + RES_AHEAD < 2 * MI) load_res(hb + RES_AHEAD, rvp[(hb + RES_AHEAD) % (RES_AHEAD + 1)]);
                     const int n = ncol + ni * 32;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         f32x4 o = *(const f32x4*)(P + rb32 + i * 1024);
                         const int m = mrow + mi * 32 + 8 * i;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] += p.beta * rvp[hb % (G_RES_AHEAD + 1)][i][e];
+                        for (int e = 0; e < 4; ++e) o[e] += p.beta * rvp[hb % (RES_AHEAD + 1)][i][e];
                         if (m < p.M && n < p.N_out && !((G_ABL & 1) && p.M > 0)) *(f32x4*)((float*)p.out + (int64_t)m * p.N_out + n) = o;
                     }
                 }
@@ -902,19 +641,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                     }
                 };
                 auto prefetch_next = [&]() {
-                    if (has_next) {
-                        setup_tile(t_next, h_next);
-                        dma_bias(n0);
-                        if (h_next < 0) {
-                            dma_tile(0);
-                            dma_tile(1);
-                            dma_tile(2);
-                        } else {
-                            dma_tile_h(0);
-                            dma_tile_h(1);
-                            dma_tile_h(2);
-                        }
-                    }
+                    if (has_next) request_tile(t_next, h_next);
                 };
                 if constexpr (res) load_res(0);
                 else prefetch_next();
@@ -955,13 +682,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] = acc[ni][mi][4 * g + e];
                             if constexpr (act == 2) {   // channels are (value, gate) interleaved: 2 outputs per quad
-#if G_GELU_PACKED
                                 const f32x2_t gl = gelu_erf2_f((f32x2_t){v[1], v[3]});
                                 const f32x2_t pr = ((f32x2_t){v[0], v[2]} * p.alpha) * gl;
                                 TO o2[2] = {(TO)pr[0], (TO)pr[1]};
-#else
-                                TO o2[2] = {(TO)(p.alpha * v[0] * gelu_erf_f(v[1])), (TO)(p.alpha * v[2] * gelu_erf_f(v[3]))};
-#endif
                                 uint32_t packed;
                                 __builtin_memcpy(&packed, o2, 4);
                                 *(uint32_t*)(P + gwbase + (((ni * 2 + (g >> 1)) << 4) ^ gx3) + (g & 1) * 8) = packed;
@@ -1019,12 +742,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         // this workgroup's list: n_full whole tiles, then (last round of the XCD's run) possibly one half tile
         for (int i = 0; i < n_full; ++i) {
             const bool more = i + 1 < n_full;
-            run_tile(std::false_type{}, more || t_half >= 0, more ? t_cur + t_step : t_half, more ? -1 : h_half);
+            run_tile(Whole{}, more || t_half >= 0, more ? t_cur + t_step : t_half, more ? -1 : h_half);
             t_cur += t_step;
         }
         if (t_half >= 0) {
             t_cur = t_half;
-            run_tile(std::true_type{}, false, 0, -1);
+            run_tile(Half{}, false, 0, -1);
         }
         return;
     }
@@ -1045,76 +768,40 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     // before the barrier that opened the slot).  Before the barrier that precedes anybody's read of tile kt+1 every
     // wave has waited for its own pieces of it: group 0 at the end of its multiply slot (tiles kt+2, kt+3 behind it),
     // group 1 at the end of its read slot (only tile kt+2 behind it: it requests kt+3 one slot later).
-    const int nk_main = G_ASMDMA ? max(nk - 3, 0) : 0;   // tiles whose multiply slot requests tile kt + 3
-#if G_ONEBAR
-    // ONE barrier per K tile (experiment; the scheme of attn_d64c): between two barriers a wave reads the fragments of one tile (R)
-    // and multiplies one tile (M); group 0 runs  M(kt) R(kt+1) | barrier,  group 1  R(kt) M(kt) | barrier,  so the two waves of a
-    // SIMD still alternate on the matrix pipe, but without the mid-tile barrier whose release latency was a bubble of the pipe
-    // twice per tile, and a wave stalled on the issue of its LDS-DMA pieces no longer idles the pipe when its partner is
-    // multiplying.  Both groups run the same loop body  R(kt) [barrier if group 0] M(kt) [barrier if group 1]  (group 0's loop
-    // is rotated by one segment).  Barrier #kt: tile kt + 1 has landed in every wave's view (group 0 then has requested up to
-    // tile kt + 2, group 1 up to tile kt + 3); the stage tile kt + 3 overwrites held tile kt - 1, whose reads returned before
-    // barrier #(kt - 1).
-    for (int kt = 0; kt < nk_main; ++kt) {
-        read_tile(kt);
-        if (grp == 0) {
-            g_wait_vm<4>();
-            slot_end();
-        }
-        mma_tile_dma(kt + 3, std::false_type{});
-        if (grp == 1) {
-            g_wait_vm<8>();
-            slot_end();
-        }
-    }
-    for (int kt = nk_main; kt < nk; ++kt) {
-        read_tile(kt);
-        if (grp == 0) {
-            wait_ahead(min(nk - 1, kt + 2) - (kt + 1));
-            slot_end();
-        }
-        mma_tile(kt + 3 < nk ? kt + 3 : -1);
-        if (grp == 1) {
-            wait_ahead(min(nk - 1, kt + 3) - (kt + 1));
-            slot_end();
-        }
-    }
-#else
+    const int nk_main = max(nk - 3, 0);   // tiles whose multiply slot requests tile kt + 3
     if (grp == 0) {
         for (int kt = 0; kt < nk_main; ++kt) {              // steady state: two tiles stay in flight behind tile kt + 1
-            read_tile(kt);
+            read_tile(Whole{}, kt);
             slot_end();
-            mma_tile_dma(kt + 3, std::false_type{});
+            mma_tile(Whole{}, Pieces<0xF>{}, std::false_type{}, kt + 3);
             g_wait_vm<8>();
             slot_end();
         }
         for (int kt = nk_main; kt < nk; ++kt) {
-            read_tile(kt);
+            read_tile(Whole{}, kt);
             slot_end();
-            mma_tile(kt + 3 < nk ? kt + 3 : -1);
-            wait_ahead(min(nk - 1, kt + 3) - (kt + 1));
+            mma_tile(Whole{}, Pieces<0>{}, std::false_type{});
+            wait_ahead(Whole{}, min(nk - 1, kt + 3) - (kt + 1));
             slot_end();
         }
         slot_end();
     } else {
         slot_end();
         for (int kt = 0; kt < nk_main; ++kt) {              // steady state: one tile stays in flight behind tile kt + 1
-            read_tile(kt);
+            read_tile(Whole{}, kt);
             g_wait_vm<4>();
             slot_end();
-            mma_tile_dma(kt + 3, std::false_type{});
+            mma_tile(Whole{}, Pieces<0xF>{}, std::false_type{}, kt + 3);
             slot_end();
         }
         for (int kt = nk_main; kt < nk; ++kt) {
-            read_tile(kt);
-            wait_ahead(min(nk - 1, kt + 2) - (kt + 1));
+            read_tile(Whole{}, kt);
+            wait_ahead(Whole{}, min(nk - 1, kt + 2) - (kt + 1));
             slot_end();
-            mma_tile(kt + 3 < nk ? kt + 3 : -1);
+            mma_tile(Whole{}, Pieces<0>{}, std::false_type{});
             slot_end();
         }
     }
-
-#endif
 
     G_STAMP_AT(2);
 #if G_STAMP
@@ -1270,7 +957,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     // the compiler) and recomputed its swizzled address.  The bias quad and the staging offset of a quad depend on (ni, g) only
     // (the row enters the swizzle as row & 31 = l31 for every mi): loops reordered, mi innermost.  Same operations on the same
     // values: bit-identical.
-#if G_EPI_SPECIALISED
     {
         auto pass = [&](auto ACT, auto ALPHA1) {
             constexpr int act = decltype(ACT)::value;
@@ -1315,44 +1001,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         else if (p.alpha == 1.0f) pass(A0{}, std::true_type{});
         else pass(A0{}, std::false_type{});
     }
-#else
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-        const int row = grp * 128 + mi * 32 + l31;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int col = wn * 64 + ni * 32 + 8 * g + 4 * lh;   // tile column of the quad
-                float v[4] = {acc[ni][mi][4 * g], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]};
-                {
-                    const f32x4 bv = *(const f32x4*)(smem + G_RING + col * 4);   // zeros without a bias / past N
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += bv[e];
-                }
-                if (geglu) {   // channels are (value, gate) interleaved: 2 outputs per quad
-                    TO o2[2] = {(TO)(p.alpha * v[0] * gelu_erf_f(v[1])), (TO)(p.alpha * v[2] * gelu_erf_f(v[3]))};
-                    uint32_t packed;
-                    __builtin_memcpy(&packed, o2, 4);
-                    const int oc = col >> 1;   // output column inside the 128-wide tile
-                    *(uint32_t*)(smem + c_off(row, oc >> 3) + (oc & 7) * 2) = packed;
-                } else {
-                    if (p.act == RSVLD_ACT_SILU) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-                    }
-                    v4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (TO)(v[e] * p.alpha);
-                    *(v4*)(smem + c_off(row, col >> 3) + (col & 7) * 2) = o;
-                }
-            }
-    }
-#endif
     __syncthreads();
     G_STAMP_AT(3);
     {
-        const int n_tile_out = geglu ? 128 : 256;                         // channels of the stored tile
         const int n_out0 = geglu ? (n0 >> 1) : n0;
         const int chunk = tid & (row_chunks - 1);
         const int rows_per_pass = 512 / row_chunks;
@@ -1372,7 +1023,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 }
             }
         } else if (nn < p.N_out) {
-            if (G_EPI_SPECIALISED && !geglu && m0 + 256 <= p.M && !(G_ABL & 1)) {
+            if (!geglu && m0 + 256 <= p.M && !(G_ABL & 1)) {
                 // full tile, 32 chunks per row: thread -> (row r0 + 16 i, chunk): one output pointer advanced by a constant, the
                 // staging offset alternates between two precomputed values (row & 31 = (r0 & 15) | 16 (i & 1)): 16 x (read, store,
                 // pointer add) instead of 16 x (bounds test, 64-bit multiply-add, swizzle)
@@ -1392,7 +1043,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 }
             }
         }
-        (void)n_tile_out;
     }
 #if G_STAMP
     G_STAMP_AT(4);

@@ -3,9 +3,11 @@ same shapes as a calibration of what the hardware allows (not used by the produc
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from rsvld_amd import ops
+from rsvld_amd import devtools, ops
 from rsvld_amd import _lib as L
 
+devtools.apply_env()   # RSVLD_GEMM256_ONE_TILE / RSVLD_GEMM256_OFF / ... -> this process's LaunchContext.tune (tools/gemm_ab.sh, tools/ab.sh -e)
+print(f"tune 0x{ops.context().tune:x} (RSVLD_TUNE_* of include/rsvld_hip.h; 0 = the library's choice), library: {os.environ.get('RSVLD_LIB', '')}", flush=True)
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 SHAPES = [(8192, 1280, 1280, 0), (8192, 1280, 3840, 0), (8192, 1280, 10240, 2), (8192, 5120, 1280, 0),
