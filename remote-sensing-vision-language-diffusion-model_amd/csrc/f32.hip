@@ -20,20 +20,7 @@
 
 namespace {
 
-// split-operand helpers: x = hi + lo in bf16 (round to nearest even both times)
-__device__ __forceinline__ void split2(float x, bf16& hi, bf16& lo) {
-    hi = (bf16)x;
-    lo = (bf16)(x - (float)hi);
-}
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        bf16 h, l;
-        split2(x[e], h, l);
-        hi[e] = h;
-        lo[e] = l;
-    }
-}
+// split-operand helpers (split2 / split8: rsvld_common.h)
 // acc += a b with a = ah + al, b = bh + bl (three 16-bit products, small terms first)
 __device__ __forceinline__ f32x16 mfma_split(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);

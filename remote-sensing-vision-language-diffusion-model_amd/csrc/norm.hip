@@ -1,70 +1,196 @@
-// norm.hip — GroupNorm (+SiLU, +ZeroSFT modulation) and LayerNorm over NHWC / token-major
-// 16-bit tensors.  HBM-bound: every pass moves 16 B per lane, statistics in fp32 with a
-// deterministic two-level reduction (per-block partials -> fp64 finalize), no atomics.
+// norm.hip — GroupNorm (+SiLU, +ZeroSFT modulation) and LayerNorm over NHWC / token-major tensors, for both the 16-bit
+// networks (f16 / bf16 in and out) and the fp32-input networks of the "split" precision (round 4; RSVLD_SPLIT): there the residual
+// stream is fp32 NHWC, and every tensor that only feeds a matrix product leaves its producer as two bf16 planes per row,
+// [lo(C) | hi(C)] with hi = bf16(v), lo = bf16(v - hi).  The two families share the partial pass (one template over an input
+// trait), the geometry, the source selection, the reduction tails, the output-form store and the host side; the apply pass and
+// LayerNorm stay one kernel per family (see there).
+// HBM-bound: every pass moves 16 B (fp32 input: 32 B) per lane and row, statistics in fp32 with a deterministic two-level
+// reduction (per-block partials -> fp64 finalize), no atomics.
 #include "rsvld_common.h"
+#include <type_traits>
 
 namespace {
+
+// ---------------------------------------------------------------------------------------
+// input/output traits: element types, the in-register raw piece of 8 channels, load, cvt to 8 floats, store of 8 channels
+// at channel c of row `row`, U, the rows a GroupNorm thread keeps in flight, and LayerNorm's rows per wave and block cap
+// ---------------------------------------------------------------------------------------
+template <typename T>
+struct Io16 {   // f16 / bf16 rows in and out: 16 B per piece
+    typedef T in;
+    typedef T out;
+    typedef u32x4 raw;
+    static constexpr int U = 4;   // 4 independent 16-B loads in flight
+    static constexpr int ln_rows(int maxc) { return maxc <= 2 ? 4 : maxc == 3 ? 3 : maxc == 4 ? 2 : 1; }   // LayerNorm rows per wave
+    // at most 4096 blocks: waves keep gamma / beta in registers over their rows
+    static constexpr int LN_MAX_BLOCKS = 4096;
+    static __device__ __forceinline__ void load(const T* p, raw& r) { r = *(const u32x4*)p; }
+    static __device__ __forceinline__ void cvt(const raw& r, float (&f)[8]) { unpack8<T>(r, f); }
+    static __device__ __forceinline__ void store(T* y, int64_t row, int C, int c, const float (&f)[8]) {
+        *(u32x4*)(y + row * C + c) = pack8<T>(f);
+    }
+};
+
+// the output forms of the fp32-input entry points (their `out_f32` argument)
+enum { OUT_PLANES = 0, OUT_F32 = 1, OUT_F16 = 2, OUT_HQ8 = 3 };   // bf16 planes, fp32, fp16, RSVLD_F16Q8 rows
+
+// planes row: lo at [c], hi at [C + c].  (split8 of rsvld_common.h in this file's own words: built on split8 the same values
+// come out, but gn_apply_split_kernel<planes> reorders its conversions, same instruction count)
+__device__ __forceinline__ void st_planes8(bf16* row, int C, int c, const float (&f)[8]) {
+    bf16x8 hv;
+    float lo[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { hv[e] = (bf16)f[e]; lo[e] = f[e] - (float)hv[e]; }
+    *(u32x4*)(row + c) = pack8<bf16>(lo);
+    *(u32x4*)(row + C + c) = __builtin_bit_cast(u32x4, hv);
+}
+template <int OUT>
+struct IoF32 {   // fp32 rows in (32 B per piece), OUT rows out
+    typedef float in;
+    typedef void out;
+    typedef float raw[8];
+    static constexpr int out_form = OUT;
+    static constexpr int U = 2;   // two rows (4 x 16 B) in flight
+    static constexpr int ln_rows(int maxc) { return maxc <= 3 ? 2 : 1; }
+    // at most ~3 resident workgroups per CU of a 256-CU chip: a wave then walks several row groups and its gamma / beta rows (as many
+    // bytes as two rows of x at C = 1 280) are loaded once per wave instead of once per two rows (round 5: 4 096 workgroups of one row
+    // group each ran the 32 768 x 1 280 LayerNorms of Stage 2 at 2.5 TB/s)
+    static constexpr int LN_MAX_BLOCKS = 768;
+    static __device__ __forceinline__ void load(const float* p, raw& r) { ld8f(p, r); }
+    static __device__ __forceinline__ void cvt(const raw& r, float (&f)[8]) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = r[e];
+    }
+    static __device__ __forceinline__ void store(void* y, int64_t row, int C, int c, const float (&f)[8]) {
+        if (OUT == OUT_F32) st8f((float*)y + row * C + c, f);
+        else if (OUT == OUT_F16) *(u32x4*)((f16*)y + row * C + c) = pack8<f16>(f);
+        else if (OUT == OUT_HQ8) st_hq8<true, RSVLD_HQ8_SX_LO, RSVLD_HQ8_SX_HI>((f16*)y + row * (2 * (int64_t)C), C, c, f);
+        else st_planes8((bf16*)y + row * (2 * (int64_t)C), C, c, f);
+    }
+};
+typedef IoF32<OUT_F32> InF32;   // for the passes that only read
+
+// ---------------------------------------------------------------------------------------
+// chunk geometry of the row-streaming GroupNorm passes (host and device): a thread owns the 8-channel chunks tc, tc + TPR, ...
+// of the rows rsub, rsub + rif, ... of its block
+// ---------------------------------------------------------------------------------------
+struct GnGeom {
+    int C, C8, C1_8;
+    int TPR;   // threads per row
+    int rif;   // rows in flight
+    __host__ __device__ GnGeom(int C1, int C2) {
+        C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
+        TPR = C8 < 256 ? C8 : 256;
+        rif = 256 / TPR;
+    }
+    size_t lds_bytes() const { return (size_t)rif * C * 2 * sizeof(float); }   // gn_partial_kernel's [rif][C][2]
+};
+
+// chunk cc of image b of the channel concatenation [x1 (C1) | x2 (C2)]: declares src (its source's first row), cstride (that
+// source's row stride) and coff (the chunk's channel offset there).  A macro: as a function or a small struct it reorders
+// gn_partial_kernel's selects.
+#define GN_SOURCE(T, x1, x2, b, HW, C1, C2, C1_8, cc)                                           \
+    const T* src;                                                                               \
+    int64_t cstride;                                                                            \
+    int coff;                                                                                   \
+    if (cc < C1_8) { src = x1 + (int64_t)b * HW * C1; cstride = C1; coff = cc * 8; }            \
+    else { src = x2 + (int64_t)b * HW * C2; cstride = C2; coff = (cc - C1_8) * 8; }
+
+// ---------------------------------------------------------------------------------------
+// reduction tails, one copy each
+// ---------------------------------------------------------------------------------------
+// Sums of s and ss (doubles) over the 256 threads of a block: GN_BLOCK_PUT2 in every thread (wave shuffles, then the four wave
+// partials into red[2][4] in LDS, and a barrier), GN_BLOCK_GET2 in the one thread that goes on with the sums (a fixed order).
+// Macros: as a function (sums by reference or by value, red passed or declared inside, thread 0's part as a continuation, a second
+// helper or an `if` of its own) the block reduction reorders gn_ab_kernel and adds a line to every gn_small_kernel.
+#define GN_WAVE_SUM2(s, ss) \
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+#define GN_BLOCK_PUT2(s, ss, red, tid)                                                \
+    GN_WAVE_SUM2(s, ss)                                                               \
+    if (((tid) & 63) == 0) { red[0][(tid) >> 6] = s; red[1][(tid) >> 6] = ss; }       \
+    __syncthreads()
+#define GN_BLOCK_GET2(s, ss, red)                                \
+    s = red[0][0] + red[0][1] + red[0][2] + red[0][3];           \
+    ss = red[1][0] + red[1][1] + red[1][2] + red[1][3]
+// fp64 sums -> mean and biased variance, clamped at 0
+__device__ __forceinline__ void gn_moments(double s, double ss, double inv_count, double& mean, double& var) {
+    mean = s * inv_count;
+    var = ss * inv_count - mean * mean;
+    if (var < 0.0) var = 0.0;
+}
+// per-channel affine (a, s) = (gamma rstd, beta - mean gamma rstd).  gn_apply_kernel forms a = gamma / sqrtf(var + eps), every
+// other site a = gamma * (1 / sqrtf(var + eps)); the two round differently and both stay.  (The scale term as a function
+// reorders gn_small_kernel<T, false>: two macros.)
+#define GN_AFFINE_A_MUL(gamma, c, rstd) ((gamma ? gamma[c] : 1.f) * (rstd))
+#define GN_AFFINE_A_DIV(gamma, c, sd) ((gamma ? gamma[c] : 1.f) / (sd))
+__device__ __forceinline__ float gn_affine_s(const float* beta, int c, float mean, float a) { return (beta ? beta[c] : 0.f) - mean * a; }
 
 // ---------------------------------------------------------------------------------------
 // pass 1: per (image, row-chunk) partial sums  part[b][chunk][g] = (sum, sumsq)
 // thread -> fixed 8-channel chunk, strided over rows; per-channel sums go through LDS so
 // that any group size (2 .. C/groups, not necessarily a multiple of 8) is handled.
 // ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x1, const T* __restrict__ x2,
-                                                         float* __restrict__ part, int HW, int C1, int C2,
-                                                         int groups, int rows_per_chunk, int nchunks) {
+template <typename In>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* __restrict__ x1,
+                                                         const typename In::in* __restrict__ x2, float* __restrict__ part,
+                                                         int HW, int C1, int C2, int groups, int rows_per_chunk, int nchunks) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* sm = (float*)smem_raw;  // [rif][C][2]
-    const int C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
-    const int TPR = C8 < 256 ? C8 : 256;  // threads per row
-    const int rif = 256 / TPR;            // rows in flight
+    const GnGeom geo(C1, C2);
     const int tid = threadIdx.x;
     const int chunk = blockIdx.x, b = blockIdx.y;
     const int row_lo = chunk * rows_per_chunk;
     const int row_hi = min(HW, row_lo + rows_per_chunk);
-    const int tc = tid % TPR, rsub = tid / TPR;
-    if (rsub < rif) {
-        for (int cc = tc; cc < C8; cc += TPR) {
+    const int tc = tid % geo.TPR, rsub = tid / geo.TPR;
+    if (rsub < geo.rif) {
+        for (int cc = tc; cc < geo.C8; cc += geo.TPR) {
             float s[8], ss[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
-            const T* src;
-            int64_t cstride;
-            int coff;
-            if (cc < C1_8) { src = x1 + (int64_t)b * HW * C1; cstride = C1; coff = cc * 8; }
-            else { src = x2 + (int64_t)b * HW * C2; cstride = C2; coff = (cc - C1_8) * 8; }
+            GN_SOURCE(typename In::in, x1, x2, b, HW, C1, C2, geo.C1_8, cc)
             int r = row_lo + rsub;
-            for (; r + 3 * rif < row_hi; r += 4 * rif) {  // 4 independent 16-B loads in flight
-                u32x4 v[4];
+            if constexpr (In::U == 2) {   // (fp32 input in its own words: through the generic loop below it compiles 13 lines shorter)
+                for (; r + geo.rif < row_hi; r += 2 * geo.rif) {
+                    float f0[8], f1[8];
+                    ld8f(src + (int64_t)r * cstride + coff, f0);
+                    ld8f(src + (int64_t)(r + geo.rif) * cstride + coff, f1);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = *(const u32x4*)(src + (int64_t)(r + u * rif) * cstride + coff);
+                    for (int e = 0; e < 8; ++e) { s[e] += f0[e]; ss[e] += f0[e] * f0[e]; }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
+                    for (int e = 0; e < 8; ++e) { s[e] += f1[e]; ss[e] += f1[e] * f1[e]; }
+                }
+            } else
+            for (; r + (In::U - 1) * geo.rif < row_hi; r += In::U * geo.rif) {  // U independent rows in flight
+                typename In::raw v[In::U];
+#pragma unroll
+                for (int u = 0; u < In::U; ++u) In::load(src + (int64_t)(r + u * geo.rif) * cstride + coff, v[u]);
+#pragma unroll
+                for (int u = 0; u < In::U; ++u) {
                     float f[8];
-                    unpack8<T>(v[u], f);
+                    In::cvt(v[u], f);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
                 }
             }
-            for (; r < row_hi; r += rif) {
-                const u32x4 v = *(const u32x4*)(src + (int64_t)r * cstride + coff);
+            for (; r < row_hi; r += geo.rif) {
+                typename In::raw v;
+                In::load(src + (int64_t)r * cstride + coff, v);
                 float f[8];
-                unpack8<T>(v, f);
+                In::cvt(v, f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
             }
-            float* dst = sm + ((int64_t)rsub * C + cc * 8) * 2;
+            float* dst = sm + ((int64_t)rsub * geo.C + cc * 8) * 2;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { dst[2 * e] = s[e]; dst[2 * e + 1] = ss[e]; }
         }
     }
     __syncthreads();
-    const int gs = C / groups;
+    const int gs = geo.C / groups;
     for (int g = tid; g < groups; g += 256) {
         float s = 0.f, ss = 0.f;
-        for (int r = 0; r < rif; ++r) {
-            const float* src = sm + ((int64_t)r * C + g * gs) * 2;
+        for (int r = 0; r < geo.rif; ++r) {
+            const float* src = sm + ((int64_t)r * geo.C + g * gs) * 2;
             for (int e = 0; e < gs; ++e) { s += src[2 * e]; ss += src[2 * e + 1]; }
         }
         float* o = part + (((int64_t)b * nchunks + chunk) * groups + g) * 2;
@@ -87,15 +213,10 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
         s += (double)p[0];
         ss += (double)p[1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o);
-        ss += __shfl_xor(ss, o);
-    }
+    GN_WAVE_SUM2(s, ss)
     if (lane == 0) {
-        const double mean = s * inv_count;
-        double var = ss * inv_count - mean * mean;
-        if (var < 0.0) var = 0.0;
+        double mean, var;
+        gn_moments(s, ss, inv_count, mean, var);
         stats[2 * i] = (float)mean;
         stats[2 * i + 1] = (float)var;
     }
@@ -135,16 +256,11 @@ __global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ pa
             ss += (double)q[1];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = s; red[1][tid >> 6] = ss; }
-    __syncthreads();
+    GN_BLOCK_PUT2(s, ss, red, tid);
     if (tid == 0) {
-        s = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        ss = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        const double mean = s * inv_count;
-        double var = ss * inv_count - mean * mean;
-        if (var < 0.0) var = 0.0;
+        GN_BLOCK_GET2(s, ss, red);
+        double mean, var;
+        gn_moments(s, ss, inv_count, mean, var);
         mr[0] = (float)mean;
         mr[1] = (float)var;
         if (stats_out != nullptr) {
@@ -156,9 +272,9 @@ __global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ pa
     if (ab != nullptr) {
         const float mean = mr[0], rstd = 1.0f / sqrtf(mr[1] + eps);
         for (int c = g * gs + tid; c < (g + 1) * gs; c += 256) {
-            const float a = (gamma ? gamma[c] : 1.f) * rstd;
+            const float a = GN_AFFINE_A_MUL(gamma, c, rstd);
             ab[((int64_t)b * C + c) * 2] = a;
-            ab[((int64_t)b * C + c) * 2 + 1] = (beta ? beta[c] : 0.f) - mean * a;
+            ab[((int64_t)b * C + c) * 2 + 1] = gn_affine_s(beta, c, mean, a);
         }
     }
 }
@@ -167,6 +283,10 @@ __global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ pa
 // grid (row-chunks, B).  Same thread <-> channel-chunk mapping as pass 1: a thread keeps ONE
 // 8-channel chunk, so its 8 (scale, shift) pairs live in registers and the row loop is pure
 // 16-byte streaming with 4 loads in flight.
+// The 16-bit and the fp32-input apply pass stay two kernels in their own words.  One kernel over both argument lists moves
+// every instantiation's argument offsets; two kernels around a shared emit body and row loops (over the traits above, the
+// preamble called back or kept in each kernel) move the 16-bit kernels by +58 .. +66 instruction lines and the four fp32-input
+// ones by -74 .. +11.  They share the geometry, the source selection and the affine.
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1, const T* __restrict__ x2,
                                                        T* __restrict__ y, const float* __restrict__ stats,
@@ -174,17 +294,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
                                                        const T* __restrict__ mod_scale, const T* __restrict__ mod_shift,
                                                        int HW, int C1, int C2, int groups, float eps, int silu,
                                                        int rows_per_block, int mod_stride) {
-    const int C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
-    const int TPR = C8 < 256 ? C8 : 256;
-    const int rif = 256 / TPR;
+    const GnGeom geo(C1, C2);
     const int tid = threadIdx.x;
-    const int tc = tid % TPR, rsub = tid / TPR;
-    if (rsub >= rif) return;
+    const int tc = tid % geo.TPR, rsub = tid / geo.TPR;
+    if (rsub >= geo.rif) return;
     const int b = blockIdx.y;
-    const int gs = C / groups;
+    const int gs = geo.C / groups;
     const int row_lo = blockIdx.x * rows_per_block;
     const int row_hi = min(HW, row_lo + rows_per_block);
-    for (int cc = tc; cc < C8; cc += TPR) {
+    for (int cc = tc; cc < geo.C8; cc += geo.TPR) {
         float sa[8], sb[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -192,16 +310,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
             const int g = ch / gs;
             const float mean = stats[((int64_t)b * groups + g) * 2];
             const float var = stats[((int64_t)b * groups + g) * 2 + 1];
-            const float a = (gamma ? gamma[ch] : 1.f) / sqrtf(var + eps);
+            const float a = GN_AFFINE_A_DIV(gamma, ch, sqrtf(var + eps));
             sa[e] = a;
-            sb[e] = (beta ? beta[ch] : 0.f) - mean * a;
+            sb[e] = gn_affine_s(beta, ch, mean, a);
         }
-        const T* src;
-        int64_t cstride;
-        int coff;
-        if (cc < C1_8) { src = x1 + (int64_t)b * HW * C1; cstride = C1; coff = cc * 8; }
-        else { src = x2 + (int64_t)b * HW * C2; cstride = C2; coff = (cc - C1_8) * 8; }
-        T* dst = y + (int64_t)b * HW * C + cc * 8;
+        GN_SOURCE(T, x1, x2, b, HW, C1, C2, geo.C1_8, cc)
+        T* dst = y + (int64_t)b * HW * geo.C + cc * 8;
         auto emit = [&](int r, const u32x4& v) {
             float f[8];
             unpack8<T>(v, f);
@@ -211,7 +325,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
                 if (silu) t = silu_f(t);
                 f[e] = t;
             }
-            const int64_t o = (int64_t)r * C;
+            const int64_t o = (int64_t)r * geo.C;
             if (mod_scale != nullptr) {
                 const int64_t mo = ((int64_t)b * HW + r) * mod_stride + cc * 8;
                 float ms[8], mh[8];
@@ -223,14 +337,68 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x1,
             *(u32x4*)(dst + o) = pack8<T>(f);
         };
         int r = row_lo + rsub;
-        for (; r + 3 * rif < row_hi; r += 4 * rif) {
+        for (; r + 3 * geo.rif < row_hi; r += 4 * geo.rif) {
             u32x4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *(const u32x4*)(src + (int64_t)(r + u * rif) * cstride + coff);
+            for (int u = 0; u < 4; ++u) v[u] = *(const u32x4*)(src + (int64_t)(r + u * geo.rif) * cstride + coff);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) emit(r + u * rif, v[u]);
+            for (int u = 0; u < 4; ++u) emit(r + u * geo.rif, v[u]);
         }
-        for (; r < row_hi; r += rif) emit(r, *(const u32x4*)(src + (int64_t)r * cstride + coff));
+        for (; r < row_hi; r += geo.rif) emit(r, *(const u32x4*)(src + (int64_t)r * cstride + coff));
+    }
+}
+
+// y = act(a[b,c] * v + s[b,c]) [* (1 + mod_scale) + mod_shift]; fp32 in (one or two sources), the pairs from a ready ab row, OUT rows out
+template <int OUT>
+__global__ __launch_bounds__(256) void gn_apply_split_kernel(const float* __restrict__ x1, const float* __restrict__ x2, void* __restrict__ y,
+                                                             const float* __restrict__ ab, const float* __restrict__ mod_scale,
+                                                             const float* __restrict__ mod_shift, int HW, int C1, int C2, int silu,
+                                                             int rows_per_block, int mod_stride) {
+    const GnGeom geo(C1, C2);
+    const int tid = threadIdx.x, tc = tid % geo.TPR, rsub = tid / geo.TPR;
+    if (rsub >= geo.rif) return;
+    const int b = blockIdx.y;
+    const int row_lo = blockIdx.x * rows_per_block, row_hi = min(HW, row_lo + rows_per_block);
+    for (int cc = tc; cc < geo.C8; cc += geo.TPR) {
+        float sa[8], sb[8];
+        {
+            const float* a = ab + ((int64_t)b * geo.C + cc * 8) * 2;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { sa[e] = a[2 * e]; sb[e] = a[2 * e + 1]; }
+        }
+        GN_SOURCE(float, x1, x2, b, HW, C1, C2, geo.C1_8, cc)
+        auto emit = [&](int r, float (&f)[8]) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float t = f[e] * sa[e] + sb[e];
+                f[e] = silu ? silu_f(t) : t;
+            }
+            if (mod_scale != nullptr) {
+                const int64_t mo = ((int64_t)b * HW + r) * mod_stride + cc * 8;
+                float ms[8], mh[8];
+                ld8f(mod_scale + mo, ms);
+                ld8f(mod_shift + mo, mh);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] = f[e] * (1.f + ms[e]) + mh[e];
+            }
+            const int64_t pix = (int64_t)b * HW + r;
+            // (planes: the row width as an int; through IoF32's store, which forms it in 64 bits, this kernel grows by 13 lines)
+            if (OUT == OUT_PLANES) st_planes8((bf16*)y + pix * (2 * geo.C), geo.C, cc * 8, f);
+            else IoF32<OUT>::store(y, pix, geo.C, cc * 8, f);
+        };
+        int r = row_lo + rsub;
+        for (; r + geo.rif < row_hi; r += 2 * geo.rif) {
+            float f0[8], f1[8];
+            ld8f(src + (int64_t)r * cstride + coff, f0);
+            ld8f(src + (int64_t)(r + geo.rif) * cstride + coff, f1);
+            emit(r, f0);
+            emit(r + geo.rif, f1);
+        }
+        for (; r < row_hi; r += geo.rif) {
+            float f[8];
+            ld8f(src + (int64_t)r * cstride + coff, f);
+            emit(r, f);
+        }
     }
 }
 
@@ -305,238 +473,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// Small tensors (deep UNet levels: 32x32 / 64x64 maps): the three launches above are latency-bound (3 x ~7 us for
-// 4 MB).  One workgroup per (image, group) instead: the group's HW x (C/groups) slab is read ONCE into registers
-// (<= 32 sixteen-byte vectors per thread), reduced in fp64 through LDS in a fixed order, and either normalised and
-// written (APPLY) or turned into the per-channel (scale, shift) rows of the fused conv prologue (!APPLY).
-// Needs 8 | C/groups (a vector never straddles groups) and, for [x | x2], groups that do not straddle the sources.
-// ---------------------------------------------------------------------------------------
-constexpr int GN_SMALL_MAXV = 32;
-
-template <typename T, bool APPLY>
-__global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x1, const T* __restrict__ x2, T* __restrict__ y,
-                                                       float* __restrict__ ab, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, int HW, int C1, int C2, int groups,
-                                                       float eps, int silu) {
-    __shared__ double red[2][4];
-    __shared__ float mr[2];
-    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int C = C1 + C2, gs = C / groups, gs8 = gs >> 3;   // gs8 is a power of two <= 256
-    const int ch0 = g * gs;
-    const T* src;
-    int cs, coff;
-    if (ch0 < C1) { src = x1 + (int64_t)b * HW * C1; cs = C1; coff = ch0; }
-    else { src = x2 + (int64_t)b * HW * C2; cs = C2; coff = ch0 - C1; }
-    const int chunk = tid & (gs8 - 1);           // fixed per thread: 256 is a multiple of gs8
-    const int row0 = tid / gs8, rstep = 256 / gs8;
-    const int nv = (HW - row0 + rstep - 1) / rstep;   // vectors of this thread (<= GN_SMALL_MAXV, may be <= 0)
-    u32x4 v[GN_SMALL_MAXV];
-#pragma unroll
-    for (int i = 0; i < GN_SMALL_MAXV; ++i)
-        if (i < nv) v[i] = *(const u32x4*)(src + (int64_t)(row0 + i * rstep) * cs + coff + chunk * 8);
-    float s = 0.f, ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < GN_SMALL_MAXV; ++i)
-        if (i < nv) {
-            float f[8];
-            unpack8<T>(v[i], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s += f[e]; ss += f[e] * f[e]; }
-        }
-    double ds = (double)s, dss = (double)ss;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ds += __shfl_xor(ds, o); dss += __shfl_xor(dss, o); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = ds; red[1][tid >> 6] = dss; }
-    __syncthreads();
-    if (tid == 0) {
-        ds = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        dss = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        const double inv_count = 1.0 / ((double)HW * (double)gs);
-        const double mean = ds * inv_count;
-        double var = dss * inv_count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        mr[0] = (float)mean;
-        mr[1] = (float)var;
-    }
-    __syncthreads();
-    const float mean = mr[0], rstd = 1.0f / sqrtf(mr[1] + eps);
-    if (!APPLY) {
-        if (tid < gs) {
-            const int c = ch0 + tid;
-            const float a = (gamma ? gamma[c] : 1.f) * rstd;
-            ab[((int64_t)b * C + c) * 2] = a;
-            ab[((int64_t)b * C + c) * 2 + 1] = (beta ? beta[c] : 0.f) - mean * a;
-        }
-        return;
-    }
-    float sa[8], sb[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = ch0 + chunk * 8 + e;
-        sa[e] = (gamma ? gamma[c] : 1.f) * rstd;
-        sb[e] = (beta ? beta[c] : 0.f) - mean * sa[e];
-    }
-    T* dst = y + (int64_t)b * HW * C + ch0 + chunk * 8;
-#pragma unroll
-    for (int i = 0; i < GN_SMALL_MAXV; ++i)
-        if (i < nv) {
-            float f[8];
-            unpack8<T>(v[i], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float t = f[e] * sa[e] + sb[e];
-                f[e] = silu ? silu_f(t) : t;
-            }
-            *(u32x4*)(dst + (int64_t)(row0 + i * rstep) * C) = pack8<T>(f);
-        }
-}
-
-
-// ---------------------------------------------------------------------------------------
-// fp32-input forms for the split-operand product path (round 4; RSVLD_SPLIT): the residual stream of a network in the "split"
-// precision is fp32 NHWC, and every tensor that only feeds a matrix product leaves its producer as two bf16 planes per row,
-// [lo(C) | hi(C)] with hi = bf16(v), lo = bf16(v - hi).  Same thread <-> 8-channel-chunk mapping and the same two-level
-// deterministic reduction as the 16-bit kernels above; 32 bytes per lane and row.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-}
-// planes row: lo at [c], hi at [C + c]
-__device__ __forceinline__ void st_planes8(bf16* row, int C, int c, const float (&f)[8]) {
-    bf16x8 hv;
-    float lo[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { hv[e] = (bf16)f[e]; lo[e] = f[e] - (float)hv[e]; }
-    *(u32x4*)(row + c) = pack8<bf16>(lo);
-    *(u32x4*)(row + C + c) = __builtin_bit_cast(u32x4, hv);
-}
-
-__global__ __launch_bounds__(256) void gn_partial_f32_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                             float* __restrict__ part, int HW, int C1, int C2, int groups,
-                                                             int rows_per_chunk, int nchunks) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* sm = (float*)smem_raw;  // [rif][C][2]
-    const int C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y;
-    const int row_lo = chunk * rows_per_chunk, row_hi = min(HW, row_lo + rows_per_chunk);
-    const int tc = tid % TPR, rsub = tid / TPR;
-    if (rsub < rif) {
-        for (int cc = tc; cc < C8; cc += TPR) {
-            float s[8], ss[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
-            const float* src;
-            int64_t cstride;
-            int coff;
-            if (cc < C1_8) { src = x1 + (int64_t)b * HW * C1; cstride = C1; coff = cc * 8; }
-            else { src = x2 + (int64_t)b * HW * C2; cstride = C2; coff = (cc - C1_8) * 8; }
-            int r = row_lo + rsub;
-            for (; r + rif < row_hi; r += 2 * rif) {   // two rows (4 x 16 B) in flight
-                float f0[8], f1[8];
-                ld8f(src + (int64_t)r * cstride + coff, f0);
-                ld8f(src + (int64_t)(r + rif) * cstride + coff, f1);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] += f0[e]; ss[e] += f0[e] * f0[e]; }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] += f1[e]; ss[e] += f1[e] * f1[e]; }
-            }
-            for (; r < row_hi; r += rif) {
-                float f[8];
-                ld8f(src + (int64_t)r * cstride + coff, f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
-            }
-            float* dst = sm + ((int64_t)rsub * C + cc * 8) * 2;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { dst[2 * e] = s[e]; dst[2 * e + 1] = ss[e]; }
-        }
-    }
-    __syncthreads();
-    const int gs = C / groups;
-    for (int g = tid; g < groups; g += 256) {
-        float s = 0.f, ss = 0.f;
-        for (int r = 0; r < rif; ++r) {
-            const float* src = sm + ((int64_t)r * C + g * gs) * 2;
-            for (int e = 0; e < gs; ++e) { s += src[2 * e]; ss += src[2 * e + 1]; }
-        }
-        float* o = part + (((int64_t)b * nchunks + chunk) * groups + g) * 2;
-        o[0] = s;
-        o[1] = ss;
-    }
-}
-
-// y = act(a[b,c] * v + s[b,c]) [* (1 + mod_scale) + mod_shift]; fp32 in (one or two sources); OUT: 0 planes, 1 fp32, 2 fp16, 3 RSVLD_F16Q8 rows
-template <int OUT>
-__global__ __launch_bounds__(256) void gn_apply_split_kernel(const float* __restrict__ x1, const float* __restrict__ x2, void* __restrict__ y,
-                                                             const float* __restrict__ ab, const float* __restrict__ mod_scale,
-                                                             const float* __restrict__ mod_shift, int HW, int C1, int C2, int silu,
-                                                             int rows_per_block, int mod_stride) {
-    const int C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const int tid = threadIdx.x, tc = tid % TPR, rsub = tid / TPR;
-    if (rsub >= rif) return;
-    const int b = blockIdx.y;
-    const int row_lo = blockIdx.x * rows_per_block, row_hi = min(HW, row_lo + rows_per_block);
-    for (int cc = tc; cc < C8; cc += TPR) {
-        float sa[8], sb[8];
-        {
-            const float* a = ab + ((int64_t)b * C + cc * 8) * 2;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { sa[e] = a[2 * e]; sb[e] = a[2 * e + 1]; }
-        }
-        const float* src;
-        int64_t cstride;
-        int coff;
-        if (cc < C1_8) { src = x1 + (int64_t)b * HW * C1; cstride = C1; coff = cc * 8; }
-        else { src = x2 + (int64_t)b * HW * C2; cstride = C2; coff = (cc - C1_8) * 8; }
-        auto emit = [&](int r, float (&f)[8]) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float t = f[e] * sa[e] + sb[e];
-                f[e] = silu ? silu_f(t) : t;
-            }
-            if (mod_scale != nullptr) {
-                const int64_t mo = ((int64_t)b * HW + r) * mod_stride + cc * 8;
-                float ms[8], mh[8];
-                ld8f(mod_scale + mo, ms);
-                ld8f(mod_shift + mo, mh);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = f[e] * (1.f + ms[e]) + mh[e];
-            }
-            const int64_t pix = (int64_t)b * HW + r;
-            if (OUT == 1) {
-                float* o = (float*)y + pix * C + cc * 8;
-                *(f32x4*)o = (f32x4){f[0], f[1], f[2], f[3]};
-                *(f32x4*)(o + 4) = (f32x4){f[4], f[5], f[6], f[7]};
-            } else if (OUT == 2) {
-                *(u32x4*)((f16*)y + pix * C + cc * 8) = pack8<f16>(f);
-            } else if (OUT == 3) {
-                st_hq8<true, RSVLD_HQ8_SX_LO, RSVLD_HQ8_SX_HI>((f16*)y + pix * (2 * (int64_t)C), C, cc * 8, f);
-            } else {
-                st_planes8((bf16*)y + pix * (2 * C), C, cc * 8, f);
-            }
-        };
-        int r = row_lo + rsub;
-        for (; r + rif < row_hi; r += 2 * rif) {
-            float f0[8], f1[8];
-            ld8f(src + (int64_t)r * cstride + coff, f0);
-            ld8f(src + (int64_t)(r + rif) * cstride + coff, f1);
-            emit(r, f0);
-            emit(r + rif, f1);
-        }
-        for (; r < row_hi; r += rif) {
-            float f[8];
-            ld8f(src + (int64_t)r * cstride + coff, f);
-            emit(r, f);
-        }
-    }
-}
-
-// LayerNorm of fp32 rows -> planes (or fp32): the 16-bit kernel's structure (one wave per row group, rows and the lane's
-// gamma / beta in registers, exact two-pass variance) with 32-byte pieces
+// LayerNorm of fp32 rows -> OUT rows: the 16-bit kernel's structure (one wave per row group, rows and the lane's gamma / beta in
+// registers, exact two-pass variance) with 32-byte pieces.  The two stay apart: they differ in how a row piece is held (packed
+// u32x4 by value / 8 floats in place), and one kernel over a trait for that moves layernorm_kernel<T, 8, 1> (registers renamed) or
+// layernorm_split_kernel<4, 1, fp32> (-10 lines) with the piece in place, and 8 of the 12 fp32-input kernels with it by value.
 template <int MAXC, int ROWS, int OUT>
 __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __restrict__ x, void* __restrict__ y,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -594,19 +534,93 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
                     float o[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (f[r][j][e] - mean) * rstd * ga[j][e] + be[j][e];
-                    if (OUT == 1) {
-                        float* d = (float*)y + (row0 + r) * C + cc * 8;
-                        *(f32x4*)d = (f32x4){o[0], o[1], o[2], o[3]};
-                        *(f32x4*)(d + 4) = (f32x4){o[4], o[5], o[6], o[7]};
-                    } else if (OUT == 2) {
-                        *(u32x4*)((f16*)y + (row0 + r) * C + cc * 8) = pack8<f16>(o);
-                    } else {
-                        st_planes8((bf16*)y + (row0 + r) * (2 * (int64_t)C), C, cc * 8, o);
-                    }
+                    IoF32<OUT>::store(y, row0 + r, C, cc * 8, o);
                 }
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// Small tensors (deep UNet levels: 32x32 / 64x64 maps): the three launches above are latency-bound (3 x ~7 us for
+// 4 MB).  One workgroup per (image, group) instead: the group's HW x (C/groups) slab is read ONCE into registers
+// (<= 32 sixteen-byte vectors per thread), reduced in fp64 through LDS in a fixed order, and either normalised and
+// written (APPLY) or turned into the per-channel (scale, shift) rows of the fused conv prologue (!APPLY).
+// Needs 8 | C/groups (a vector never straddles groups) and, for [x | x2], groups that do not straddle the sources.
+// ---------------------------------------------------------------------------------------
+constexpr int GN_SMALL_MAXV = 32;
+
+template <typename T, bool APPLY>
+__global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x1, const T* __restrict__ x2, T* __restrict__ y,
+                                                       float* __restrict__ ab, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, int HW, int C1, int C2, int groups,
+                                                       float eps, int silu) {
+    __shared__ double red[2][4];
+    __shared__ float mr[2];
+    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int C = C1 + C2, gs = C / groups, gs8 = gs >> 3;   // gs8 is a power of two <= 256
+    const int ch0 = g * gs;
+    const T* src;
+    int cs, coff;
+    if (ch0 < C1) { src = x1 + (int64_t)b * HW * C1; cs = C1; coff = ch0; }
+    else { src = x2 + (int64_t)b * HW * C2; cs = C2; coff = ch0 - C1; }
+    const int chunk = tid & (gs8 - 1);           // fixed per thread: 256 is a multiple of gs8
+    const int row0 = tid / gs8, rstep = 256 / gs8;
+    const int nv = (HW - row0 + rstep - 1) / rstep;   // vectors of this thread (<= GN_SMALL_MAXV, may be <= 0)
+    u32x4 v[GN_SMALL_MAXV];
+#pragma unroll
+    for (int i = 0; i < GN_SMALL_MAXV; ++i)
+        if (i < nv) v[i] = *(const u32x4*)(src + (int64_t)(row0 + i * rstep) * cs + coff + chunk * 8);
+    float s = 0.f, ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < GN_SMALL_MAXV; ++i)
+        if (i < nv) {
+            float f[8];
+            unpack8<T>(v[i], f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { s += f[e]; ss += f[e] * f[e]; }
+        }
+    double ds = (double)s, dss = (double)ss;
+    GN_BLOCK_PUT2(ds, dss, red, tid);
+    if (tid == 0) {
+        GN_BLOCK_GET2(ds, dss, red);
+        const double inv_count = 1.0 / ((double)HW * (double)gs);
+        double mean, var;
+        gn_moments(ds, dss, inv_count, mean, var);
+        mr[0] = (float)mean;
+        mr[1] = (float)var;
+    }
+    __syncthreads();
+    const float mean = mr[0], rstd = 1.0f / sqrtf(mr[1] + eps);
+    if (!APPLY) {
+        if (tid < gs) {
+            const int c = ch0 + tid;
+            const float a = GN_AFFINE_A_MUL(gamma, c, rstd);
+            ab[((int64_t)b * C + c) * 2] = a;
+            ab[((int64_t)b * C + c) * 2 + 1] = gn_affine_s(beta, c, mean, a);
+        }
+        return;
+    }
+    float sa[8], sb[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = ch0 + chunk * 8 + e;
+        sa[e] = GN_AFFINE_A_MUL(gamma, c, rstd);
+        sb[e] = gn_affine_s(beta, c, mean, sa[e]);
+    }
+    T* dst = y + (int64_t)b * HW * C + ch0 + chunk * 8;
+#pragma unroll
+    for (int i = 0; i < GN_SMALL_MAXV; ++i)
+        if (i < nv) {
+            float f[8];
+            unpack8<T>(v[i], f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float t = f[e] * sa[e] + sb[e];
+                f[e] = silu ? silu_f(t) : t;
+            }
+            *(u32x4*)(dst + (int64_t)(row0 + i * rstep) * C) = pack8<T>(f);
+        }
 }
 
 // (mean, biased variance) per (image, group) -> the per-channel affine (gamma rstd, beta - mean gamma rstd)
@@ -616,11 +630,14 @@ __global__ void gn_ab_from_stats_kernel(const float* __restrict__ mean_var, cons
     if (i >= total) return;
     const int b = i / C, c = i - b * C, g = c / (C / groups);
     const float mean = mean_var[((int64_t)b * groups + g) * 2], var = mean_var[((int64_t)b * groups + g) * 2 + 1];
-    const float a = (gamma ? gamma[c] : 1.f) * (1.0f / sqrtf(var + eps));
+    const float a = GN_AFFINE_A_MUL(gamma, c, 1.0f / sqrtf(var + eps));
     ab[2 * (int64_t)i] = a;
-    ab[2 * (int64_t)i + 1] = (beta ? beta[c] : 0.f) - mean * a;
+    ab[2 * (int64_t)i + 1] = gn_affine_s(beta, c, mean, a);
 }
 
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
 bool gn_small_ok(int B, int HW, int C1, int C2, int groups) {
     const int C = C1 + C2, gs = C / groups;
     if (gs % 8) return false;
@@ -647,47 +664,108 @@ GnPlan gn_plan(int B, int HW) {
     return p;
 }
 
-bool gn_shape_ok(int B, int HW, int C1, int C2, int groups) {
-    if (B <= 0 || HW <= 0 || C1 <= 0 || C1 % 8 || C2 < 0 || C2 % 8 || groups <= 0) return false;
-    const int C = C1 + C2;
-    if (C % groups) return false;
-    if (C > 8192 || groups > 256) return false;
-    return true;
+// operand checks of the entry points: the sizes of [x (C1) | x2 (C2)], the same with its pointers, and the groups over C1 + C2
+bool gn_dims_ok(int B, int HW, int C1, int C2) { return B > 0 && HW > 0 && C1 > 0 && C1 % 8 == 0 && C2 >= 0 && C2 % 8 == 0; }
+bool gn_x_ok(const void* x, const void* x2, int B, int HW, int C1, int C2) {
+    return x != nullptr && gn_dims_ok(B, HW, C1, C2) && (C2 > 0) == (x2 != nullptr);
+}
+bool gn_groups_ok(int C, int groups) { return groups > 0 && C % groups == 0 && C <= 8192 && groups <= 256; }
+bool gn_mod_ok(const void* mod_scale1p, const void* mod_shift, int mod_stride, int align) {
+    return (mod_scale1p != nullptr) == (mod_shift != nullptr) && mod_stride >= 0 && mod_stride % align == 0;
 }
 
-template <typename T>
+double gn_inv_count(int HW, int C, int groups) { return 1.0 / ((double)HW * (double)(C / groups)); }
+
+template <typename In>
+void launch_partials(const void* x, const void* x2, float* part, int B, int HW, int C1, int C2, int groups, const GnPlan& pl,
+                     hipStream_t s) {
+    typedef typename In::in T;
+    hipLaunchKernelGGL(gn_partial_kernel<In>, dim3(pl.nchunks, B), dim3(256), GnGeom(C1, C2).lds_bytes(), s, (const T*)x,
+                       (const T*)x2, part, HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
+}
+
+// partials in ws -> (mean, var) rows
+template <typename In>
 int gn_stats_impl(const void* x, const void* x2, float* stats, int B, int HW, int C1, int C2, int groups, void* ws,
                   hipStream_t s) {
     const GnPlan pl = gn_plan(B, HW);
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const size_t smem = (size_t)rif * C * 2 * sizeof(float);
-    float* part = (float*)ws;
-    hipLaunchKernelGGL(gn_partial_kernel<T>, dim3(pl.nchunks, B), dim3(256), smem, s, (const T*)x, (const T*)x2, part,
-                       HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
+    launch_partials<In>(x, x2, (float*)ws, B, HW, C1, C2, groups, pl, s);
     const int total = B * groups;
-    const double inv_count = 1.0 / ((double)HW * (double)(C / groups));
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s, part, stats, groups, pl.nchunks,
-                       inv_count, total);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s, (const float*)ws, stats, groups, pl.nchunks,
+                       gn_inv_count(HW, C1 + C2, groups), total);
     return rsvld_check_launch();
+}
+
+// partials in ws -> per-channel (scale, shift) rows
+template <typename In>
+int gn_scale_shift_impl(const void* x, const void* x2, const float* gamma, const float* beta, float* scale_shift, int B, int HW,
+                        int C1, int C2, int groups, float eps, void* ws, hipStream_t s) {
+    const GnPlan pl = gn_plan(B, HW);
+    launch_partials<In>(x, x2, (float*)ws, B, HW, C1, C2, groups, pl, s);
+    hipLaunchKernelGGL(gn_ab_kernel<false>, dim3(groups, B), dim3(256), 0, s, (const float*)ws, pl.nchunks, C1 + C2, nullptr, 0, 0,
+                       gamma, beta, scale_shift, nullptr, groups, eps, gn_inv_count(HW, C1 + C2, groups));
+    return rsvld_check_launch();
+}
+
+// the apply pass's rows per block and blocks per image: ~2048 blocks over the chip, at least U * rif rows per block so the
+// unrolled loop is used
+template <typename Io>
+int gn_apply_rows_per_block(int B, int HW, int C1, int C2) {
+    int max_blocks = 2048 / B;
+    if (max_blocks < 1) max_blocks = 1;
+    int rpb = (HW + max_blocks - 1) / max_blocks;
+    const int min_rows = Io::U * GnGeom(C1, C2).rif;
+    return rpb < min_rows ? min_rows : rpb;
 }
 
 template <typename T>
 int gn_apply_impl(const void* x, const void* x2, void* y, const float* stats, const float* gamma, const float* beta,
                   const void* mscale, const void* mshift, int mod_stride, int B, int HW, int C1, int C2, int groups,
                   float eps, int silu, hipStream_t s) {
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    // ~2048 blocks over the chip, at least 4*rif rows per block so the unrolled loop is used
-    int max_blocks = 2048 / (B > 0 ? B : 1);
-    if (max_blocks < 1) max_blocks = 1;
-    int rpb = (HW + max_blocks - 1) / max_blocks;
-    if (rpb < 4 * rif) rpb = 4 * rif;
-    const int nblk = (HW + rpb - 1) / rpb;
-    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)nblk, B), dim3(256), 0, s, (const T*)x, (const T*)x2,
+    const int rpb = gn_apply_rows_per_block<Io16<T>>(B, HW, C1, C2);
+    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)cdiv64(HW, rpb), B), dim3(256), 0, s, (const T*)x, (const T*)x2,
                        (T*)y, stats, gamma, beta, (const T*)mscale, (const T*)mshift, HW, C1, C2, groups, eps, silu,
-                       rpb, mod_stride > 0 ? mod_stride : C);
+                       rpb, mod_stride > 0 ? mod_stride : C1 + C2);
     return rsvld_check_launch();
+}
+
+template <typename T, bool APPLY>
+int gn_small_impl(const void* x, const void* x2, void* y, float* ab, const float* gamma, const float* beta, int B, int HW, int C1,
+                  int C2, int groups, float eps, int silu, hipStream_t s) {
+    hipLaunchKernelGGL((gn_small_kernel<T, APPLY>), dim3(groups, B), dim3(256), 0, s, (const T*)x, (const T*)x2, (T*)y, ab, gamma,
+                       beta, HW, C1, C2, groups, eps, silu);
+    return rsvld_check_launch();
+}
+
+template <typename Io, int MAXC>
+void launch_layernorm_maxc(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps,
+                           hipStream_t s) {
+    constexpr int ROWS = Io::ln_rows(MAXC);   // rows per wave in flight; 4 waves per block
+    const int64_t n = cdiv64(rows, 4 * ROWS);
+    const dim3 grid((unsigned)(n < Io::LN_MAX_BLOCKS ? n : Io::LN_MAX_BLOCKS));
+    if constexpr (std::is_same<typename Io::in, float>::value)
+        hipLaunchKernelGGL((layernorm_split_kernel<MAXC, ROWS, Io::out_form>), grid, dim3(256), 0, s, (const float*)x, y, gamma, beta, rows, C, eps);
+    else
+        hipLaunchKernelGGL((layernorm_kernel<typename Io::in, MAXC, ROWS>), grid, dim3(256), 0, s, (const typename Io::in*)x, (typename Io::in*)y, gamma, beta, rows, C, eps);
+}
+template <typename Io>
+void launch_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps, hipStream_t s) {
+    const int chunks_per_lane = (C / 8 + 63) / 64;
+    if (chunks_per_lane <= 2) launch_layernorm_maxc<Io, 2>(x, y, gamma, beta, rows, C, eps, s);         // C <= 1024
+    else if (chunks_per_lane == 3) launch_layernorm_maxc<Io, 3>(x, y, gamma, beta, rows, C, eps, s);    // C <= 1536 (the 1280-channel transformer blocks)
+    else if (chunks_per_lane <= 4) launch_layernorm_maxc<Io, 4>(x, y, gamma, beta, rows, C, eps, s);    // C <= 2048
+    else launch_layernorm_maxc<Io, 8>(x, y, gamma, beta, rows, C, eps, s);
+}
+
+// f(IoF32<form>()) for an output form 0 .. MAX that the caller has range-checked
+template <int MAX, typename F>
+void with_out_form(int form, F f) {
+    if constexpr (MAX >= OUT_HQ8) {
+        if (form == OUT_HQ8) return f(IoF32<OUT_HQ8>());
+    }
+    if (form == OUT_F32) return f(IoF32<OUT_F32>());
+    if (form == OUT_F16) return f(IoF32<OUT_F16>());
+    return f(IoF32<OUT_PLANES>());
 }
 
 }  // namespace
@@ -702,10 +780,10 @@ extern "C" int64_t rsvld_groupnorm_ws_bytes(int B, int HW, int C, int groups) {
 
 extern "C" int rsvld_groupnorm_stats(const void* x, const void* x2, float* mean_var, int B, int HW, int C1, int C2,
                                      int groups, int dtype, void* ws, void* stream) {
-    if (!x || !mean_var || !ws || !gn_shape_ok(B, HW, C1, C2, groups) || ((C2 > 0) != (x2 != nullptr))) return RSVLD_EINVAL;
+    if (!mean_var || !ws || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == RSVLD_F16) return gn_stats_impl<f16>(x, x2, mean_var, B, HW, C1, C2, groups, ws, s);
-    if (dtype == RSVLD_BF16) return gn_stats_impl<bf16>(x, x2, mean_var, B, HW, C1, C2, groups, ws, s);
+    if (dtype == RSVLD_F16) return gn_stats_impl<Io16<f16>>(x, x2, mean_var, B, HW, C1, C2, groups, ws, s);
+    if (dtype == RSVLD_BF16) return gn_stats_impl<Io16<bf16>>(x, x2, mean_var, B, HW, C1, C2, groups, ws, s);
     return RSVLD_EINVAL;
 }
 
@@ -713,8 +791,8 @@ extern "C" int rsvld_groupnorm_apply(const void* x, const void* x2, void* y, con
                                      const float* gamma, const float* beta, const void* mod_scale1p,
                                      const void* mod_shift, int mod_stride, int B, int HW, int C1, int C2, int groups,
                                      float eps, int silu, int dtype, void* stream) {
-    if (!x || !y || !mean_var || !gn_shape_ok(B, HW, C1, C2, groups) || ((C2 > 0) != (x2 != nullptr))) return RSVLD_EINVAL;
-    if ((mod_scale1p != nullptr) != (mod_shift != nullptr) || mod_stride < 0 || (mod_stride & 7)) return RSVLD_EINVAL;
+    if (!y || !mean_var || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
+    if (!gn_mod_ok(mod_scale1p, mod_shift, mod_stride, 8)) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == RSVLD_F16)
         return gn_apply_impl<f16>(x, x2, y, mean_var, gamma, beta, mod_scale1p, mod_shift, mod_stride, B, HW, C1, C2, groups, eps, silu, s);
@@ -726,18 +804,12 @@ extern "C" int rsvld_groupnorm_apply(const void* x, const void* x2, void* y, con
 extern "C" int rsvld_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma, const float* beta,
                                     const void* mod_scale1p, const void* mod_shift, int mod_stride, int B, int HW, int C1,
                                     int C2, int groups, float eps, int silu, int dtype, void* ws, void* stream) {
-    if (!ws) return RSVLD_EINVAL;
-    if (!gn_shape_ok(B, HW, C1, C2, groups)) return RSVLD_EINVAL;
-    if (mod_scale1p == nullptr && mod_shift == nullptr && x && y && ((C2 > 0) == (x2 != nullptr)) && B <= 65535 &&
+    if (!ws || !gn_dims_ok(B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
+    if (mod_scale1p == nullptr && mod_shift == nullptr && y && gn_x_ok(x, x2, B, HW, C1, C2) && B <= 65535 &&
         gn_small_ok(B, HW, C1, C2, groups) && (dtype == RSVLD_F16 || dtype == RSVLD_BF16)) {
         hipStream_t s = (hipStream_t)stream;
-        if (dtype == RSVLD_F16)
-            hipLaunchKernelGGL((gn_small_kernel<f16, true>), dim3(groups, B), dim3(256), 0, s, (const f16*)x, (const f16*)x2,
-                               (f16*)y, nullptr, gamma, beta, HW, C1, C2, groups, eps, silu);
-        else
-            hipLaunchKernelGGL((gn_small_kernel<bf16, true>), dim3(groups, B), dim3(256), 0, s, (const bf16*)x, (const bf16*)x2,
-                               (bf16*)y, nullptr, gamma, beta, HW, C1, C2, groups, eps, silu);
-        return rsvld_check_launch();
+        if (dtype == RSVLD_F16) return gn_small_impl<f16, true>(x, x2, y, nullptr, gamma, beta, B, HW, C1, C2, groups, eps, silu, s);
+        return gn_small_impl<bf16, true>(x, x2, y, nullptr, gamma, beta, B, HW, C1, C2, groups, eps, silu, s);
     }
     const GnPlan pl = gn_plan(B, HW);
     float* stats = (float*)ws + (int64_t)B * pl.nchunks * groups * 2;
@@ -750,31 +822,15 @@ extern "C" int rsvld_groupnorm_nhwc(const void* x, const void* x2, void* y, cons
 extern "C" int rsvld_groupnorm_scale_shift(const void* x, const void* x2, const float* gamma, const float* beta,
                                            float* scale_shift, int B, int HW, int C1, int C2, int groups, float eps,
                                            int dtype, void* ws, void* stream) {
-    if (!x || !ws || !scale_shift || !gn_shape_ok(B, HW, C1, C2, groups) || ((C2 > 0) != (x2 != nullptr))) return RSVLD_EINVAL;
+    if (!ws || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
     if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (B <= 65535 && gn_small_ok(B, HW, C1, C2, groups)) {
-        if (dtype == RSVLD_F16)
-            hipLaunchKernelGGL((gn_small_kernel<f16, false>), dim3(groups, B), dim3(256), 0, s, (const f16*)x, (const f16*)x2,
-                               (f16*)nullptr, scale_shift, gamma, beta, HW, C1, C2, groups, eps, 0);
-        else
-            hipLaunchKernelGGL((gn_small_kernel<bf16, false>), dim3(groups, B), dim3(256), 0, s, (const bf16*)x, (const bf16*)x2,
-                               (bf16*)nullptr, scale_shift, gamma, beta, HW, C1, C2, groups, eps, 0);
-        return rsvld_check_launch();
+        if (dtype == RSVLD_F16) return gn_small_impl<f16, false>(x, x2, nullptr, scale_shift, gamma, beta, B, HW, C1, C2, groups, eps, 0, s);
+        return gn_small_impl<bf16, false>(x, x2, nullptr, scale_shift, gamma, beta, B, HW, C1, C2, groups, eps, 0, s);
     }
-    const GnPlan pl = gn_plan(B, HW);
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const size_t smem = (size_t)rif * C * 2 * sizeof(float);
-    float* part = (float*)ws;
-    if (dtype == RSVLD_F16)
-        hipLaunchKernelGGL(gn_partial_kernel<f16>, dim3(pl.nchunks, B), dim3(256), smem, s, (const f16*)x, (const f16*)x2, part, HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
-    else
-        hipLaunchKernelGGL(gn_partial_kernel<bf16>, dim3(pl.nchunks, B), dim3(256), smem, s, (const bf16*)x, (const bf16*)x2, part, HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
-    const double inv_count = 1.0 / ((double)HW * (double)(C / groups));
-    hipLaunchKernelGGL(gn_ab_kernel<false>, dim3(groups, B), dim3(256), 0, s, part, pl.nchunks, C, nullptr, 0, 0, gamma, beta,
-                       scale_shift, nullptr, groups, eps, inv_count);
-    return rsvld_check_launch();
+    if (dtype == RSVLD_F16) return gn_scale_shift_impl<Io16<f16>>(x, x2, gamma, beta, scale_shift, B, HW, C1, C2, groups, eps, ws, s);
+    return gn_scale_shift_impl<Io16<bf16>>(x, x2, gamma, beta, scale_shift, B, HW, C1, C2, groups, eps, ws, s);
 }
 
 extern "C" int rsvld_groupnorm_scale_shift_from_partials(const float* part1, int ntiles1, int C1, const float* part2,
@@ -783,133 +839,56 @@ extern "C" int rsvld_groupnorm_scale_shift_from_partials(const float* part1, int
                                                          void* stream) {
     if (!part1 || !scale_shift || B <= 0 || HW <= 0 || C1 <= 0 || C2 < 0 || ntiles1 <= 0 || groups <= 0) return RSVLD_EINVAL;
     if ((C2 > 0) != (part2 != nullptr) || (C2 > 0 && ntiles2 <= 0) || (C1 + C2) % groups != 0 || B > 65535) return RSVLD_EINVAL;
-    const double inv_count = 1.0 / ((double)HW * (double)((C1 + C2) / groups));
     hipLaunchKernelGGL(gn_ab_kernel<true>, dim3(groups, B), dim3(256), 0, (hipStream_t)stream, part1, ntiles1, C1, part2,
-                       ntiles2, C2, gamma, beta, scale_shift, nullptr, groups, eps, inv_count);
+                       ntiles2, C2, gamma, beta, scale_shift, nullptr, groups, eps, gn_inv_count(HW, C1 + C2, groups));
     return rsvld_check_launch();
-}
-
-template <typename T>
-static void launch_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps,
-                             hipStream_t s) {
-    const int chunks_per_lane = (C / 8 + 63) / 64;
-    auto blocks = [&](int rows_per_block) {   // at most 4096 blocks: waves keep gamma / beta in registers over their rows
-        const int64_t n = cdiv64(rows, rows_per_block);
-        return (unsigned)(n < 4096 ? n : 4096);
-    };
-    if (chunks_per_lane <= 2) {        // C <= 1024: 4 rows per wave in flight
-        hipLaunchKernelGGL((layernorm_kernel<T, 2, 4>), dim3(blocks(16)), dim3(256), 0, s, (const T*)x, (T*)y, gamma, beta, rows, C, eps);
-    } else if (chunks_per_lane == 3) { // C <= 1536 (the 1280-channel transformer blocks): 3 rows per wave in flight
-        hipLaunchKernelGGL((layernorm_kernel<T, 3, 3>), dim3(blocks(12)), dim3(256), 0, s, (const T*)x, (T*)y, gamma, beta, rows, C, eps);
-    } else if (chunks_per_lane <= 4) { // C <= 2048
-        hipLaunchKernelGGL((layernorm_kernel<T, 4, 2>), dim3(blocks(8)), dim3(256), 0, s, (const T*)x, (T*)y, gamma, beta, rows, C, eps);
-    } else {
-        hipLaunchKernelGGL((layernorm_kernel<T, 8, 1>), dim3(blocks(4)), dim3(256), 0, s, (const T*)x, (T*)y, gamma, beta, rows, C, eps);
-    }
 }
 
 extern "C" int rsvld_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C,
                                float eps, int dtype, void* stream) {
     if (!x || !y || rows <= 0 || C <= 0 || C % 8 || C > 4096) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == RSVLD_F16) launch_layernorm<f16>(x, y, gamma, beta, rows, C, eps, s);
-    else if (dtype == RSVLD_BF16) launch_layernorm<bf16>(x, y, gamma, beta, rows, C, eps, s);
+    if (dtype == RSVLD_F16) launch_layernorm<Io16<f16>>(x, y, gamma, beta, rows, C, eps, s);
+    else if (dtype == RSVLD_BF16) launch_layernorm<Io16<bf16>>(x, y, gamma, beta, rows, C, eps, s);
     else return RSVLD_EINVAL;
     return rsvld_check_launch();
 }
 
-// ---- split-operand product path (fp32 NHWC in; see the kernels above)
+// ---- split-operand product path (fp32 NHWC in)
 extern "C" int rsvld_groupnorm_scale_shift_f32(const float* x, const float* x2, const float* gamma, const float* beta,
                                                float* scale_shift, int B, int HW, int C1, int C2, int groups, float eps, void* ws,
                                                void* stream) {
-    if (!x || !ws || !scale_shift || !gn_shape_ok(B, HW, C1, C2, groups) || ((C2 > 0) != (x2 != nullptr)) || B > 65535) return RSVLD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const GnPlan pl = gn_plan(B, HW);
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const size_t smem = (size_t)rif * C * 2 * sizeof(float);
-    float* part = (float*)ws;
-    hipLaunchKernelGGL(gn_partial_f32_kernel, dim3(pl.nchunks, B), dim3(256), smem, s, x, x2, part, HW, C1, C2, groups,
-                       pl.rows_per_chunk, pl.nchunks);
-    const double inv_count = 1.0 / ((double)HW * (double)(C / groups));
-    hipLaunchKernelGGL(gn_ab_kernel<false>, dim3(groups, B), dim3(256), 0, s, part, pl.nchunks, C, nullptr, 0, 0, gamma, beta,
-                       scale_shift, nullptr, groups, eps, inv_count);
-    return rsvld_check_launch();
+    if (!ws || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
+    return gn_scale_shift_impl<InF32>(x, x2, gamma, beta, scale_shift, B, HW, C1, C2, groups, eps, ws, (hipStream_t)stream);
 }
 
 extern "C" int rsvld_groupnorm_apply_split(const float* x, const float* x2, void* out, const float* scale_shift,
                                            const float* mod_scale1p, const float* mod_shift, int mod_stride, int B, int HW, int C1,
                                            int C2, int silu, int out_f32, void* stream) {
-    if (!x || !out || !scale_shift || B <= 0 || B > 65535 || HW <= 0 || C1 <= 0 || C1 % 8 || C2 < 0 || C2 % 8 || ((C2 > 0) != (x2 != nullptr)))
-        return RSVLD_EINVAL;
-    if ((mod_scale1p != nullptr) != (mod_shift != nullptr) || mod_stride < 0 || (mod_stride & 3)) return RSVLD_EINVAL;
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    int max_blocks = 2048 / B;
-    if (max_blocks < 1) max_blocks = 1;
-    int rpb = (HW + max_blocks - 1) / max_blocks;
-    if (rpb < 2 * rif) rpb = 2 * rif;
-    const int nblk = (HW + rpb - 1) / rpb;
-    hipStream_t s = (hipStream_t)stream;
-    if (out_f32 < 0 || out_f32 > 3 || (out_f32 == 3 && (C1 + C2) % 32)) return RSVLD_EINVAL;
-    if (out_f32 == 3)
-        hipLaunchKernelGGL(gn_apply_split_kernel<3>, dim3((unsigned)nblk, B), dim3(256), 0, s, x, x2, out, scale_shift, mod_scale1p,
-                           mod_shift, HW, C1, C2, silu, rpb, mod_stride > 0 ? mod_stride : C);
-    else if (out_f32 == 1)
-        hipLaunchKernelGGL(gn_apply_split_kernel<1>, dim3((unsigned)nblk, B), dim3(256), 0, s, x, x2, out, scale_shift, mod_scale1p,
-                           mod_shift, HW, C1, C2, silu, rpb, mod_stride > 0 ? mod_stride : C);
-    else if (out_f32 == 2)
-        hipLaunchKernelGGL(gn_apply_split_kernel<2>, dim3((unsigned)nblk, B), dim3(256), 0, s, x, x2, out, scale_shift, mod_scale1p,
-                           mod_shift, HW, C1, C2, silu, rpb, mod_stride > 0 ? mod_stride : C);
-    else
-        hipLaunchKernelGGL(gn_apply_split_kernel<0>, dim3((unsigned)nblk, B), dim3(256), 0, s, x, x2, out, scale_shift, mod_scale1p,
-                           mod_shift, HW, C1, C2, silu, rpb, mod_stride > 0 ? mod_stride : C);
+    if (!out || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || B > 65535) return RSVLD_EINVAL;
+    if (!gn_mod_ok(mod_scale1p, mod_shift, mod_stride, 4)) return RSVLD_EINVAL;
+    if (out_f32 < 0 || out_f32 > 3 || (out_f32 == OUT_HQ8 && (C1 + C2) % 32)) return RSVLD_EINVAL;
+    with_out_form<OUT_HQ8>(out_f32, [&](auto io) {
+        constexpr int OUT = decltype(io)::out_form;
+        const int rpb = gn_apply_rows_per_block<decltype(io)>(B, HW, C1, C2);
+        hipLaunchKernelGGL(gn_apply_split_kernel<OUT>, dim3((unsigned)cdiv64(HW, rpb), B), dim3(256), 0, (hipStream_t)stream, x, x2,
+                           out, scale_shift, mod_scale1p, mod_shift, HW, C1, C2, silu, rpb, mod_stride > 0 ? mod_stride : C1 + C2);
+    });
     return rsvld_check_launch();
-}
-
-template <int OUT_F32>
-static void launch_layernorm_split(const float* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps,
-                                   hipStream_t s) {
-    const int chunks_per_lane = (C / 8 + 63) / 64;
-    // at most ~3 resident workgroups per CU of a 256-CU chip: a wave then walks several row groups and its gamma / beta rows (as many
-    // bytes as two rows of x at C = 1 280) are loaded once per wave instead of once per two rows (round 5: 4 096 workgroups of one row
-    // group each ran the 32 768 x 1 280 LayerNorms of Stage 2 at 2.5 TB/s)
-    auto blocks = [&](int rows_per_block) {
-        const int64_t n = cdiv64(rows, rows_per_block);
-        return (unsigned)(n < 768 ? n : 768);
-    };
-    if (chunks_per_lane <= 2) hipLaunchKernelGGL((layernorm_split_kernel<2, 2, OUT_F32>), dim3(blocks(8)), dim3(256), 0, s, x, y, gamma, beta, rows, C, eps);
-    else if (chunks_per_lane == 3) hipLaunchKernelGGL((layernorm_split_kernel<3, 2, OUT_F32>), dim3(blocks(8)), dim3(256), 0, s, x, y, gamma, beta, rows, C, eps);
-    else if (chunks_per_lane <= 4) hipLaunchKernelGGL((layernorm_split_kernel<4, 1, OUT_F32>), dim3(blocks(4)), dim3(256), 0, s, x, y, gamma, beta, rows, C, eps);
-    else hipLaunchKernelGGL((layernorm_split_kernel<8, 1, OUT_F32>), dim3(blocks(4)), dim3(256), 0, s, x, y, gamma, beta, rows, C, eps);
 }
 
 extern "C" int rsvld_layernorm_split(const float* x, void* out, const float* gamma, const float* beta, int64_t rows, int C, float eps,
                                      int out_f32, void* stream) {
     if (!x || !out || rows <= 0 || C <= 0 || C % 8 || C > 4096) return RSVLD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
     if (out_f32 < 0 || out_f32 > 2) return RSVLD_EINVAL;
-    if (out_f32 == 1) launch_layernorm_split<1>(x, out, gamma, beta, rows, C, eps, s);
-    else if (out_f32 == 2) launch_layernorm_split<2>(x, out, gamma, beta, rows, C, eps, s);
-    else launch_layernorm_split<0>(x, out, gamma, beta, rows, C, eps, s);
+    with_out_form<OUT_F16>(out_f32, [&](auto io) { launch_layernorm<decltype(io)>(x, out, gamma, beta, rows, C, eps, (hipStream_t)stream); });
     return rsvld_check_launch();
 }
 
 extern "C" int rsvld_groupnorm_stats_f32_fast(const float* x, const float* x2, float* mean_var, int B, int HW, int C1, int C2, int groups,
                                               void* ws, void* stream) {
-    if (!x || !mean_var || !ws || !gn_shape_ok(B, HW, C1, C2, groups) || ((C2 > 0) != (x2 != nullptr)) || B > 65535) return RSVLD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const GnPlan pl = gn_plan(B, HW);
-    const int C = C1 + C2, C8 = C / 8;
-    const int TPR = C8 < 256 ? C8 : 256, rif = 256 / TPR;
-    const size_t smem = (size_t)rif * C * 2 * sizeof(float);
-    float* part = (float*)ws;
-    hipLaunchKernelGGL(gn_partial_f32_kernel, dim3(pl.nchunks, B), dim3(256), smem, s, x, x2, part, HW, C1, C2, groups,
-                       pl.rows_per_chunk, pl.nchunks);
-    const int total = B * groups;
-    const double inv_count = 1.0 / ((double)HW * (double)(C / groups));
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s, part, mean_var, groups, pl.nchunks, inv_count, total);
-    return rsvld_check_launch();
+    if (!mean_var || !ws || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
+    return gn_stats_impl<InF32>(x, x2, mean_var, B, HW, C1, C2, groups, ws, (hipStream_t)stream);
 }
 
 extern "C" int rsvld_groupnorm_scale_shift_from_stats(const float* mean_var, const float* gamma, const float* beta, float* scale_shift,

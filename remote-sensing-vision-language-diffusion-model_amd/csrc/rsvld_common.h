@@ -63,6 +63,30 @@ template <typename T> __device__ __forceinline__ u32x4 pack8(const float (&f)[8]
     return __builtin_bit_cast(u32x4, v);
 }
 
+// 8 consecutive fp32 values as two 16-byte accesses
+__device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
+    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
+}
+__device__ __forceinline__ void st8f(float* p, const float (&f)[8]) {
+    *(f32x4*)p = (f32x4){f[0], f[1], f[2], f[3]};
+    *(f32x4*)(p + 4) = (f32x4){f[4], f[5], f[6], f[7]};
+}
+// split operands and bf16 planes: x = hi + lo in bf16 (round to nearest even both times)
+__device__ __forceinline__ void split2(float x, bf16& hi, bf16& lo) {
+    hi = (bf16)x;
+    lo = (bf16)(x - (float)hi);
+}
+__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        bf16 h, l;
+        split2(x[e], h, l);
+        hi[e] = h;
+        lo[e] = l;
+    }
+}
+
 // x * sigmoid(x) with v_exp_f32 + v_rcp_f32 (1 ulp): an IEEE division here made the GroupNorm apply pass VALU-bound
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // exact-erf GELU (sgm/modules/attention.py:84-96 uses F.gelu's default).  erf by Abramowitz-Stegun 7.1.26
@@ -114,7 +138,9 @@ __device__ __forceinline__ uint32_t cvt4_e4m3(float a, float b, float c, float d
     return (uint32_t)r;
 }
 __device__ __forceinline__ float sat_e4m3(float v) { return fminf(fmaxf(v, -448.f), 448.f); }
-__device__ __forceinline__ float sat_f16_nan(float s) { return fabsf(s) > 65504.f ? copysignf(65504.f, s) : s; }   // (NaN stays NaN)
+// clamp to the finite fp16 range WITHOUT swallowing NaN: fminf / fmaxf lower to minnum / maxnum, which return the non-NaN operand
+// (fmaxf(NaN, -65504) = -65504), so the clamp is a compare + select on |s| and NaN (all compares false) falls through unchanged
+__device__ __forceinline__ float sat_f16_nan(float s) { return fabsf(s) > 65504.f ? copysignf(65504.f, s) : s; }
 // 8 consecutive channels c0 .. c0 + 7 (c0 % 8 == 0) of one row; FIRST_LO: the lo part is P0 (activations), else P1 (weights)
 template <bool FIRST_LO, int S_LO, int S_HI>
 __device__ __forceinline__ void st_hq8(f16* row, int C, int c0, const float (&f)[8]) {

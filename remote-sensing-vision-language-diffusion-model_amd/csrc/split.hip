@@ -18,16 +18,10 @@ typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-}
-__device__ __forceinline__ void split8v(const float (&f)[8], u32x4& lo, u32x4& hi) {
-    bf16x8 hv;
-    float l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { hv[e] = (bf16)f[e]; l[e] = f[e] - (float)hv[e]; }
-    lo = pack8<bf16>(l);
+__device__ __forceinline__ void split8v(const float (&f)[8], u32x4& lo, u32x4& hi) {   // split8 as two 16-byte register quads
+    bf16x8 hv, lv;
+    split8(f, hv, lv);
+    lo = __builtin_bit_cast(u32x4, lv);
     hi = __builtin_bit_cast(u32x4, hv);
 }
 
@@ -53,16 +47,10 @@ __global__ __launch_bounds__(256) void merge_planes_kernel(const bf16* __restric
         float l[8], h[8];
         unpack8<bf16>(*(const u32x4*)(y + row * (2 * (int64_t)C) + c), l);
         unpack8<bf16>(*(const u32x4*)(y + row * (2 * (int64_t)C) + C + c), h);
-        float* o = x + row * C + c;
+        float* o = x + row * C + c;   // (not st8f on h + l: that form reorders this kernel's instructions, same count)
         *(f32x4*)o = (f32x4){h[0] + l[0], h[1] + l[1], h[2] + l[2], h[3] + l[3]};
         *(f32x4*)(o + 4) = (f32x4){h[4] + l[4], h[5] + l[5], h[6] + l[6], h[7] + l[7]};
     }
-}
-
-// clamp to the finite fp16 range WITHOUT swallowing NaN: fminf / fmaxf lower to minnum / maxnum, which return the non-NaN operand
-// (fmaxf(NaN, -65504) = -65504), so the clamp is a compare + select on |s| and NaN (all compares false) falls through unchanged
-__device__ __forceinline__ float sat_f16_keep_nan(float s) {
-    return fabsf(s) > 65504.f ? copysignf(65504.f, s) : s;
 }
 
 // planes (rows of lo | hi, the two planes `ps` elements apart, rows `ld` elements apart: a channel slice of a wider planes tensor
@@ -76,7 +64,7 @@ __global__ __launch_bounds__(256) void planes_to_f16_kernel(const bf16* __restri
         unpack8<bf16>(*(const u32x4*)(y + row * ld + c), l);
         unpack8<bf16>(*(const u32x4*)(y + row * ld + ps + c), h);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = sat_f16_keep_nan(h[e] + l[e]);   // saturate: a finite fp32 value stays finite, NaN stays NaN
+        for (int e = 0; e < 8; ++e) h[e] = sat_f16_nan(h[e] + l[e]);   // saturate: a finite fp32 value stays finite, NaN stays NaN
         *(u32x4*)(o + row * old + c) = pack8<f16>(h);
     }
 }
@@ -789,7 +777,7 @@ __global__ __launch_bounds__(256) void pack_weight_pairs_kernel(const float* __r
         f16x8 h;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            h[e] = (f16)sat_f16_keep_nan(f[e]);
+            h[e] = (f16)sat_f16_nan(f[e]);
             l[e] = f[e] - (float)h[e];
         }
         f16* d = o + row * (2 * (int64_t)C) + c;

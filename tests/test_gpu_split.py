@@ -168,7 +168,8 @@ def test_conv2d_split(cuda, case):
 
 
 @pytest.mark.parametrize("shape,silu,two", [((2, 128, 19, 23), True, False), ((1, 64, 70, 66), True, True), ((1, 640, 32, 32), False, False),
-                                            ((1, 1920, 16, 16), True, True)])
+                                            ((1, 1920, 16, 16), True, True),
+                                            ((1, 2560, 5, 5), True, False), ((1, 2560, 5, 5), True, True)])   # C / 8 > 256: two chunks per thread
 def test_group_norm_split(cuda, shape, silu, two):
     """fp32 NHWC in -> fp32 and planes out; two sources = the skip concat, never materialised; conv2d(norm=) through the same kernels"""
     from rsvld_amd import ops
