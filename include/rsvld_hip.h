@@ -89,6 +89,10 @@ typedef struct rsvld_conv_desc {
 
 /* rsvld_conv_desc.tune (benchmarking only; every combination computes the same function) */
 #define RSVLD_TUNE_TILE_MASK 7          /* 1: 256x64, 2: 128x64, 3: 128x128, 4: 64x128 implicit-GEMM tile */
+                                        /* (1 and 2 are read for Cout <= 64 only, where 128x64 is the default anyway; for Cout > 64 they
+                                         * select no tile of their own: like 3, any non-zero value other than 4 runs 128x128, because
+                                         * the 64x64 / 64x128 re-tiling of small grids is the choice of mask 0.  Cout <= 32 is always
+                                         * 256x32.  tests/test_gpu_matrix_exact.py has one row per instantiation.) */
 #define RSVLD_TUNE_STAGES_SHIFT 3       /* bits 3..5: LDS ring depth 2..4 (0 = per-tile default)          */
 #define RSVLD_TUNE_NO_KSPLIT (1 << 6)   /* no intra-workgroup split-K variants                            */
 #define RSVLD_TUNE_REG_STAGING (1 << 7) /* register-staged operands instead of LDS-DMA                    */

@@ -210,8 +210,9 @@ GEMM_CASES = [
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", GEMM_CASES)
 def test_gemm256_linear(cuda, dtype, case):
-    """csrc/gemm.hip: the 256x256 ping-pong GEMM that takes the large 1x1 / Linear layers; vs torch fp32 and vs the
-    implicit-GEMM kernel on the same call (RSVLD_GEMM256_OFF is read once per process, so the cross-check is numeric)."""
+    """csrc/gemm.hip: the 256x256 ping-pong GEMM that takes the large 1x1 / Linear layers; vs torch fp32.  The cross-check against the
+    implicit-GEMM kernel on the same call (RSVLD_TUNE_NO_GEMM256) is test_gpu_matrix_exact.test_gemm256_exact_all_forms_and_implicit_gemm:
+    exact operands, equal outputs."""
     from rsvld_amd import ops, _lib as L
     M, K, N, act, use_res = case
     g = torch.Generator().manual_seed(M + K + N)
