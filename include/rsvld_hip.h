@@ -484,6 +484,26 @@ int rsvld_attention_split_d512_shared(const void* q, const void* x, void* out, i
                                       int64_t o_batch_stride, int64_t o_tok_stride, int64_t o_plane,
                                       float scale, int out_f32, void* stream);
 
+/* ---- 8-bit image path (csrc/image.hip): the host steps around the two stages, opt-in through PipelineConfig.device_io.  Every
+ * number that decides a bit -- filter coefficients, bounds, look-up tables, tap indices -- is built on the host and passed as a
+ * small device table (rsvld_amd/imageops.py); images are HWC uint8 or NCHW fp32 with 1..4 channels, batch 1. */
+/* One separable pass of Pillow's 8-bit Image.resize(..., BICUBIC) (data/dataset.py:16-42 through torchvision's resize,
+ * models/util.py:132-156): axis 0 = horizontal, src [in_h][in_w][C] -> dst [in_h][out_len][C]; axis 1 = vertical,
+ * dst [out_len][in_w][C].  Output position j uses table row first + j (first: the outputs a centre crop throws away are skipped):
+ * bounds[row] = (xmin, n), coeffs[row][ksize] int32 in 22-bit fixed point; dst = clamp((2^21 + sum src[xmin + i] * k[i]) >> 22). */
+int rsvld_resample_u8(const uint8_t* src, uint8_t* dst, const int32_t* bounds, const int32_t* coeffs, int in_h, int in_w,
+                      int channels, int axis, int out_len, int first, int table_len, int ksize, void* stream);
+/* uint8 HWC -> fp32 NCHW through a 256-entry fp32 table (x / 255 * 2 - 1 of models/util.py:152-156, ToTensor + (x - 0.5) / 0.5 of
+ * data/dataset.py:30-42) */
+int rsvld_u8_hwc_to_nchw_f32(const uint8_t* src, const float* lut, float* dst, int H, int W, int channels, void* stream);
+/* fp32 NCHW -> uint8 HWC.  mode 0: utils/tensor2img.py:4-21 with min_max = (-1, 1): clamp, (c + 1) * 0.5, rint(u * 255);
+ * mode 1: models/util.py:159-166: x * 127.5 + 127.5, clamp to [0, 255], truncate.  Each product and sum is rounded on its own. */
+int rsvld_nchw_f32_to_u8_hwc(const float* src, uint8_t* dst, int H, int W, int channels, int mode, void* stream);
+/* F.interpolate(mode="bicubic", align_corners=False) of fp32 NCHW [C][H][W] to (h0, w0), fused with mode 1 above
+ * (models/util.py:159-166); idx_* [n][4] clamped tap indices, w_* [n][4] fp32 weights per output row / column */
+int rsvld_bicubic_f32_to_u8_hwc(const float* src, uint8_t* dst, const int32_t* idx_y, const float* w_y, const int32_t* idx_x,
+                                const float* w_x, int channels, int H, int W, int h0, int w0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

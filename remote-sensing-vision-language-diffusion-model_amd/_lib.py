@@ -126,6 +126,10 @@ SIGNATURES = {
     "rsvld_attention_split_d512_shared": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _i, _vp]),
     "rsvld_attention_split_d64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i,
                                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _i, _vp]),
+    "rsvld_resample_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rsvld_u8_hwc_to_nchw_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsvld_nchw_f32_to_u8_hwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "rsvld_bicubic_f32_to_u8_hwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -6,16 +6,22 @@ import torch
 from PIL import Image
 
 
-def resize_and_convert(img, scale, resample=Image.BICUBIC):
-    w, h = img.size
+def resize_geometry(w, h, scale):
+    """-> (nw, nh, target, left, top): the resized size and the centre-crop box of ``resize_and_convert`` (the device loader,
+    rsvld_amd.imageops.load_sr_input, takes its sizes from here too)."""
     target = int(max(w, h) * scale)
     # torchvision.transforms.functional.resize(img, int): the shorter side becomes `target`, aspect kept
     if w <= h:
         nw, nh = target, int(target * h / w)
     else:
         nh, nw = target, int(target * w / h)
-    img = img.resize((nw, nh), resample)
     left, top = int(round((nw - target) / 2.0)), int(round((nh - target) / 2.0))
+    return nw, nh, target, left, top
+
+
+def resize_and_convert(img, scale, resample=Image.BICUBIC):
+    nw, nh, target, left, top = resize_geometry(*img.size, scale)
+    img = img.resize((nw, nh), resample)
     return img.crop((left, top, left + target, top + target))
 
 

@@ -15,6 +15,7 @@ from pathlib import Path
 import torch
 from PIL import Image
 
+from . import imageops
 from .configs import sr3 as SR3
 from .data import dataset as SR_Dataset
 from .models.util import PIL2Tensor, Tensor2PIL, create_SR_model
@@ -69,6 +70,7 @@ class PipelineConfig:
     sr3_steps: int = 0            # 0 = the option file's 'val' schedule (500 steps, configs/sr_sr3.json)
     allow_random_init: bool = False   # tests / benchmarks only: run without checkpoints on seeded random weights
     overlap_vae_with_caption: bool = True   # Stage 2's opening VAE passes on a second HIP stream beside the live caption pass
+    device_io: bool = False           # resize / crop / 8-bit conversions around both stages on the GPU (rsvld_amd.imageops) instead of PIL + numpy + CPU torch
 
     def __post_init__(self):
         self.output_dir = Path(self.output_dir)
@@ -79,6 +81,8 @@ class PipelineConfig:
 
 class SuperResolutionPipeline:
     _side_stream = None     # ONE second HIP stream for every image's VAE front (the caching allocator keys its free blocks by stream)
+    _image_plan = None      # device_io: the device tables of rsvld_amd.imageops, built on first use and kept for every image
+    _handoff = None         # device_io: (the PIL hand-off image of the current input, the device uint8 it is the host copy of)
 
     def __init__(self, cfg: PipelineConfig):
         self.cfg = cfg
@@ -113,14 +117,30 @@ class SuperResolutionPipeline:
         if self.cfg.use_tile_vae:
             self.refinement_model.init_tile_vae(self.cfg.encoder_tile_size, self.cfg.decoder_tile_size)
 
+    def _plan(self):
+        if self._image_plan is None:
+            self._image_plan = imageops.ImagePlan()
+        return self._image_plan
+
     def run_stage1_sr3_upscale(self, image_path: Path) -> Image.Image:
-        val_data = SR_Dataset.load_sr_input(str(image_path), self.cfg.upscale_factor)
+        if self.cfg.device_io:
+            # the decoded LR image goes up as uint8; resize, centre crop and the [-1, 1] conversion are kernels
+            val_data = imageops.load_sr_input(str(image_path), self.cfg.upscale_factor, self.sr3_model.device, self._plan())
+        else:
+            val_data = SR_Dataset.load_sr_input(str(image_path), self.cfg.upscale_factor)
         self.sr3_model.feed_data(val_data)
         self.sr3_model.test(continous=True)
         sr = self.sr3_model.SR
         if sr.dim() == 4:
             sr = sr[-1]
-        sr_pil = Image.fromarray(T2I.tensor2img(sr, min_max=(-1, 1)))      # 8-bit hand-off, as the reference
+        if self.cfg.device_io:
+            # quantised on the device: the uint8 image comes down (a quarter of the fp32 tensor) for the PNG and the caption pass,
+            # and stays up for Stage 2
+            u8 = imageops.tensor2img(sr, min_max=(-1, 1))
+            sr_pil = Image.fromarray(u8.cpu().numpy())
+            self._handoff = (sr_pil, u8)
+        else:
+            sr_pil = Image.fromarray(T2I.tensor2img(sr, min_max=(-1, 1)))      # 8-bit hand-off, as the reference
         sr_pil.save(self.cfg.output_dir / f"sr3_{self.cfg.filename}.png")
         return sr_pil
 
@@ -145,6 +165,14 @@ class SuperResolutionPipeline:
                                    prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed)[0]
 
     def _stage2_input(self, sr_image):
+        if self.cfg.device_io:
+            # Stage 1's own device copy when ``sr_image`` is its hand-off image; any other image is uploaded as uint8
+            held = self._handoff is not None and self._handoff[0] is sr_image
+            if not held and sr_image.mode != "RGB":      # (Pillow resizes an image with alpha through premultiplied alpha: no kernel for that)
+                raise imageops.L.RsvldError(f"device_io: Stage 2 takes an RGB image, got mode {sr_image.mode!r}")
+            u8 = self._handoff[1] if held else imageops.upload_u8(sr_image, self.cfg.sr_model_device)
+            lq, h0, w0 = imageops.pil2tensor(u8.to(self.cfg.sr_model_device), upscale=1, min_size=self.cfg.min_size, plan=self._plan())
+            return lq.unsqueeze(0)[:, :3], h0, w0
         lq, h0, w0 = PIL2Tensor(sr_image, upscale=1, min_size=self.cfg.min_size)
         return lq.unsqueeze(0).to(self.cfg.sr_model_device)[:, :3], h0, w0
 
@@ -181,7 +209,10 @@ class SuperResolutionPipeline:
         outs = []
         for i, s in enumerate(samples):
             path = c.output_dir / f"{c.filename}_final_{i}.png"
-            Tensor2PIL(s, h0, w0).save(path)
+            if c.device_io:      # bicubic back to the hand-off size and the 8-bit quantiser in one kernel; only the uint8 image comes down
+                Image.fromarray(imageops.tensor2pil_u8(s.float().contiguous(), h0, w0, plan=self._plan()).cpu().numpy()).save(path)
+            else:
+                Tensor2PIL(s, h0, w0).save(path)
             outs.append(path)
         return outs
 
@@ -206,6 +237,8 @@ def main(argv=None):
     p.add_argument("--llava_path", type=str, default="lmms-lab/llama3-llava-next-8b")
     p.add_argument("--llava_adapter", type=str, default="./CKPT_PTH/Llava-next")
     p.add_argument("--use_tile_vae", action="store_true")
+    p.add_argument("--device_io", action="store_true", help="resize, crop and the 8-bit conversions around both stages on the GPU "
+                   "(rsvld_amd.imageops; bit-identical to the host route except one 8-bit step in a few bytes per 100 000 of a resized final image)")
     p.add_argument("--fp32", action="store_true", help="both stages on the fp32-operand kernels (reference CPU-path precision; slow)")
     p.add_argument("--tolerance", action="store_true", help="the tolerance-compliant composition (what bench.py times): inside 1e-3 of the reference's CPU path after 50 + 50 steps at ~1.3 x "
                    "the default's time.  Stage 1: fp16 tensors x fp16 weight pairs (two MFMAs per product); Stage 2: fp32 residual "
@@ -221,6 +254,7 @@ def main(argv=None):
     cfg = PipelineConfig(input_img=a.input_img, output_dir=a.output_dir, upscale_factor=a.upscale_factor, seed=a.seed,
                          img_threshold=a.img_threshold, edm_steps=a.edm_steps, sr3_steps=a.sr3_steps, caption=a.caption,
                          no_llava=a.no_llava, llava_path=a.llava_path, llava_adapter=a.llava_adapter, use_tile_vae=a.use_tile_vae,
+                         device_io=a.device_io,
                          **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if a.fp32 else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if a.tolerance else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if a.split else

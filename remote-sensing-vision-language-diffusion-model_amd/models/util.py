@@ -70,10 +70,9 @@ def get_img_describe(*args, **kw):
     return _describe(*args, **kw)
 
 
-def PIL2Tensor(img, upscale=1, min_size=1024, fix_resize=None):
-    """PIL.Image -> Tensor[C,H,W] RGB in [-1,1]; sides rounded to multiples of 64 (util.py:132-156)."""
-    from PIL import Image
-    w, h = img.size
+def pil2tensor_size(w, h, upscale=1, min_size=1024, fix_resize=None):
+    """-> (w, h, h0, w0): the x64 size ``PIL2Tensor`` resizes a (w, h) image to and the hand-off size it reports (the device route,
+    rsvld_amd.imageops.pil2tensor, takes its sizes from here too)."""
     w *= upscale
     h *= upscale
     w0, h0 = round(w), round(h)
@@ -88,6 +87,13 @@ def PIL2Tensor(img, upscale=1, min_size=1024, fix_resize=None):
         w0, h0 = round(w), round(h)
     w = int(np.round(w / 64.0)) * 64
     h = int(np.round(h / 64.0)) * 64
+    return w, h, h0, w0
+
+
+def PIL2Tensor(img, upscale=1, min_size=1024, fix_resize=None):
+    """PIL.Image -> Tensor[C,H,W] RGB in [-1,1]; sides rounded to multiples of 64 (util.py:132-156)."""
+    from PIL import Image
+    w, h, h0, w0 = pil2tensor_size(*img.size, upscale, min_size, fix_resize)
     x = img.resize((w, h), Image.BICUBIC)
     x = np.array(x).round().clip(0, 255).astype(np.uint8)
     x = x / 255 * 2 - 1
