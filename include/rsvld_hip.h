@@ -155,17 +155,20 @@ int rsvld_conv2d_nhwc(const rsvld_conv_desc* d, void* stream);
  * normalised tensor is never written to HBM.  Same descriptor / epilogue as rsvld_conv2d_nhwc.
  * rsvld_conv3x3_halo_supported tells whether a descriptor is eligible (1) or must use the gather kernel (0).
  * Replaces GN+SiLU+Conv3x3 of unet.py:81-92, openaimodel.py:263-301, model.py:128-141.
- * out_stats_partials (optional, fp32 [B][ceil(Ho/8)*ceil(Wo/32)][Cout][2]): per-tile per-channel (sum, sum of squares)
+ * out_stats_partials (optional, fp64 [B][ceil(Ho/8)*ceil(Wo/32)][Cout][2]): per-tile per-channel (sum, sum of squares)
  * of the stored output, produced in the epilogue, so that the NEXT GroupNorm needs no pass over the tensor
- * (consumed by rsvld_groupnorm_scale_shift_from_partials).  Deterministic: plain stores, merged later in fp64. */
+ * (consumed by rsvld_groupnorm_scale_shift_from_partials).  Deterministic: plain stores, merged later in fp64.
+ * fp64 because the variance is E[x^2] - mean^2 of the merged pair: an fp32 pair keeps it to 2^-24 (mean / sigma)^2 only.
+ * A kernel that writes an fp32 tensor sums in fp32 about a pivot (one of its own values) and restores (sum, sum of squares) in
+ * fp64; a 16-bit output keeps plain fp32 sums, widened at the store.  8-byte aligned (RSVLD_EINVAL otherwise). */
 int rsvld_conv3x3_halo_supported(const rsvld_conv_desc* d);
 int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* norm_scale_shift, int norm_silu,
-                            float* out_stats_partials, void* stream);
+                            double* out_stats_partials, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU / Swish) over NHWC, statistics in fp32, two launches
- * (deterministic partial sums -> finalize+apply).  `ws` must hold
- * rsvld_groupnorm_ws_bytes(B, HW, C, groups) bytes.
+ * (deterministic fp32 partial sums per row chunk, merged in fp64 -> finalize+apply).  `ws` must hold
+ * rsvld_groupnorm_ws_bytes(B, HW, C, groups) bytes (room for the fp64 partials of the fp32-input entry points below).
  *   y = act( (x - mean[b,g]) * rstd[b,g] * gamma[c] + beta[c] )
  * With x2 != NULL statistics and output cover the concatenation [x | x2] along C.
  * If scale1p/shift (16-bit, rows of `mod_stride` elements, 0 = C; both may point into one stacked
@@ -201,8 +204,8 @@ int rsvld_groupnorm_scale_shift(const void* x, const void* x2, const float* gamm
                                 int dtype, void* ws, void* stream);
 
 /* same affine from per-channel partial sums written by conv epilogues (one or two producers: [x | x2]) */
-int rsvld_groupnorm_scale_shift_from_partials(const float* part1, int ntiles1, int C1,
-                                              const float* part2, int ntiles2, int C2,
+int rsvld_groupnorm_scale_shift_from_partials(const double* part1, int ntiles1, int C1,
+                                              const double* part2, int ntiles2, int C2,
                                               const float* gamma, const float* beta, float* scale_shift,
                                               int B, int HW, int groups, float eps, void* stream);
 
@@ -447,7 +450,8 @@ int rsvld_planes_to_triple(const void* planes, void* w3, int64_t rows, int64_t r
  * (cols_p = cols padded to a multiple of 8; pad columns are written as zeros).  One wave per row, two passes. */
 int rsvld_softmax_rows_split(const float* s, void* p_planes, int64_t rows, int cols, int cols_p, int64_t ld, float scale, void* stream);
 /* GroupNorm statistics of fp32 NHWC [x | x2] -> the per-(image, channel) affine (scale, shift) fp32 [B][C1+C2][2]; ws holds
- * rsvld_groupnorm_ws_bytes(B, HW, C1+C2, groups) bytes.  fp32 partial sums per row chunk, fp64 merge in a fixed order. */
+ * rsvld_groupnorm_ws_bytes(B, HW, C1+C2, groups) bytes and is 8-byte aligned (RSVLD_EINVAL otherwise).  fp64 (sum, sum of squares)
+ * per row chunk (pivoted fp32 sums inside a thread), fp64 merge in a fixed order. */
 int rsvld_groupnorm_scale_shift_f32(const float* x, const float* x2, const float* gamma, const float* beta, float* scale_shift,
                                     int B, int HW, int C1, int C2, int groups, float eps, void* ws, void* stream);
 /* statistics only, (mean, biased variance) fp32 [B][groups][2], through the same coalesced pass (the tiled VAE merges them across

@@ -30,7 +30,7 @@ struct HaloArgs {
     const void* residual;
     void* out;
     const float* ab;     // [B][Cin+Cin2][2] = (scale, shift) of the fused GroupNorm, or nullptr
-    float* stats;        // [B][tiles_y*tiles_x][Cout][2] per-tile per-channel (sum, sumsq) of the OUTPUT, or nullptr
+    double* stats;       // [B][tiles_y*tiles_x][Cout][2] per-tile per-channel (sum, sumsq) of the OUTPUT in fp64, or nullptr
     int B, H, W, Cin, Cin2, Cout;   // H, W: OUTPUT map (= input map, or 2x the input when ush = 1)
     int Hs, Ws, ush;                // source map and the nearest-x2 shift
     int out_f32, act, norm_silu;
@@ -83,12 +83,25 @@ __device__ __forceinline__ void halo_src_of(const HaloArgs& p, int ch0, int& whi
 
 // ---- epilogue shared by the halo kernels: accumulators -> LDS (fp32) -> bias / row vector / SiLU / residual ->
 // 16-byte NHWC stores, plus the per-channel (sum, sumsq) partials of every 8x32-pixel sub-tile for the next GroupNorm.
+// The partials are fp64.  An fp32 (sum, sumsq) pair holds the variance of the merged statistics to 2^-24 (mean / sigma)^2 only:
+// enough for a 16-bit tensor, 2.4e-4 at mean / sigma = 64 for an fp32 one.  So a kernel that writes an fp32 tensor (SEG > 1 with
+// out_f32) sums in fp32 about a pivot k, the first value the thread stores in the sub-tile: sum (v - k) and sum (v - k)^2 carry
+// the spread alone, and an offset common to a channel's values (a bias) never enters the squares.  At the flush every thread moves
+// its pair to the channel's pivot (the value at the sub-tile's first pixel, through LDS; still fp32, the two pivots are a few
+// sigma apart), the pairs are added up in fp32 as before, and (s + n k, q + 2 k s + n k^2) in fp64 is the (sum, sumsq) stored.
+// A 16-bit output (SEG = 1, or SEG = 2 writing fp16) keeps pivot 0: plain fp32 sums in their old order, widened at the store.
+// Small integer values (every fp32 sum of squares below 2^24) give exact integer partials either way.
+// The pivot is taken at the thread's FIRST pixel of a sub-tile (pass % SUB == 0, j == 0).  A thread's pixels are the tile rows
+// rr + j RPP: for RPP = 32 or 64 one column x and rising y, for RPP = 16 the columns x, x + 16 of rising y.  The first one has
+// the smallest x and y, so if it lies outside the map every other one does too.
 // NW waves own 64*NW pixels (8 rows of 32 per 4 waves); passes of EPI_ROWS pixels; the staging tile aliases the (dead)
 // operand buffers.
 template <typename T, int BN, int TM, int TN, int NW = 4, int SEG = 1>
 __device__ __forceinline__ void halo_epilogue(const HaloArgs& p, char* smem, f32x16 (&acc)[TN][TM], int tid, int wm, int wn,
                                               int l31, int lh, int x0, int y0, int n0, int img, int tx, int ty) {
     constexpr bool SPLIT = SEG == 3;
+    constexpr bool PIVOT = SEG > 1;
+    const bool pivot = PIVOT && p.out_f32;   // (workgroup-uniform) a 16-bit output keeps the plain sums: its partials stay bit for bit what they were
     // the residual has the output's type: fp32 beside an fp32 / planes output of the multi-segment forms, 16-bit otherwise
     const bool res32 = SEG > 1 && (SPLIT || p.out_f32);
     constexpr int NT = 64 * NW, PIX = 64 * NW;
@@ -104,9 +117,10 @@ __device__ __forceinline__ void halo_epilogue(const HaloArgs& p, char* smem, f32
 #pragma unroll
     for (int e = 0; e < 8; ++e) bv[e] = (p.bias != nullptr && n + e < p.Cout) ? p.bias[n + e] : 0.f;
     // statistics of the stored tensor for the NEXT GroupNorm: this thread's 8 channels, summed over its pixels
-    float st_s[8], st_q[8];
+    float st_s[8], st_q[8], st_k[8];
+    int st_n = 0;   // pixels summed since the last flush
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { st_s[e] = 0.f; st_q[e] = 0.f; }
+    for (int e = 0; e < 8; ++e) { st_s[e] = 0.f; st_q[e] = 0.f; st_k[e] = 0.f; }
     constexpr int RPT = EPI_ROWS / RPP;        // rows each thread stores per pass
 #pragma unroll
     for (int pass = 0; pass < EPI_PASSES; ++pass) {
@@ -176,7 +190,13 @@ __device__ __forceinline__ void halo_epilogue(const HaloArgs& p, char* smem, f32
                 }
                 if (p.stats != nullptr) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { st_s[e] += v[e]; st_q[e] += v[e] * v[e]; }
+                    for (int e = 0; e < 8; ++e) {
+                        if (PIVOT && j == 0 && pass % SUB == 0 && pivot) st_k[e] = v[e];
+                        const float dv = PIVOT ? v[e] - st_k[e] : v[e];
+                        st_s[e] += dv;
+                        st_q[e] += dv * dv;
+                    }
+                    ++st_n;
                 }
                 if (SPLIT && !p.out_f32) {   // planes: lo | hi per pixel row
                     float lo[8];
@@ -196,24 +216,48 @@ __device__ __forceinline__ void halo_epilogue(const HaloArgs& p, char* smem, f32
             }
         }
         if (p.stats != nullptr && (pass % SUB) == SUB - 1) {   // workgroup-uniform: an 8x32 sub-tile is complete
-            __syncthreads();        // Ct is dead: reuse it as [RPP][BN][2]
+            __syncthreads();        // Ct is dead: reuse it as [RPP][BN][2] (+ [BN] pivots)
             float* red = (float*)smem;
+            float* piv = red + RPP * BN * 2;
+            if constexpr (PIVOT) {   // the channel's pivot for the whole sub-tile: that of the thread which owns the sub-tile's first pixel
+                if (rr == 0) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) piv[cc * 8 + e] = st_k[e];
+                }
+                __syncthreads();
+            }
+            const float nf = (float)st_n;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                red[((rr * BN) + cc * 8 + e) * 2] = st_s[e];
-                red[((rr * BN) + cc * 8 + e) * 2 + 1] = st_q[e];
+                float s_e = st_s[e], q_e = st_q[e];
+                if constexpr (PIVOT) {   // from the thread's pivot to the channel's, a few sigma away: fp32 holds that
+                    const float dk = st_k[e] - piv[cc * 8 + e];
+                    q_e += dk * (2.f * s_e + nf * dk);
+                    s_e += nf * dk;
+                }
+                red[((rr * BN) + cc * 8 + e) * 2] = s_e;
+                red[((rr * BN) + cc * 8 + e) * 2 + 1] = q_e;
                 st_s[e] = 0.f;
                 st_q[e] = 0.f;
+                st_k[e] = 0.f;
             }
+            st_n = 0;
             __syncthreads();
             const int ty8 = ty * (PIX / 256) + pass / SUB;   // row of the 8x32 partial grid
             if (tid < BN && n0 + tid < p.Cout && ty8 < p.tiles_y8) {
                 float a = 0.f, q = 0.f;
                 for (int r = 0; r < RPP; ++r) { a += red[(r * BN + tid) * 2]; q += red[(r * BN + tid) * 2 + 1]; }
+                double da = (double)a, dq = (double)q;
+                if constexpr (PIVOT) {   // back to (sum, sumsq) about zero, in fp64; the sub-tile's pixels inside the map
+                    const double k = (double)piv[tid];
+                    const double np = (double)(min(8, p.H - (y0 + 8 * (pass / SUB))) * min(32, p.W - x0));
+                    dq += k * (2.0 * da + np * k);
+                    da += np * k;
+                }
                 const int64_t tile = (int64_t)ty8 * p.tiles_x + tx;
-                float* o = p.stats + (((int64_t)img * p.tiles_x * p.tiles_y8 + tile) * p.Cout + n0 + tid) * 2;
-                o[0] = a;
-                o[1] = q;
+                double* o = p.stats + (((int64_t)img * p.tiles_x * p.tiles_y8 + tile) * p.Cout + n0 + tid) * 2;
+                o[0] = da;
+                o[1] = dq;
             }
         }
     }
@@ -827,7 +871,7 @@ int launch_halo32(HaloArgs a, hipStream_t s) {
     constexpr int THT = 2 * NW;
     constexpr int stage = 2 * ((THT + 2) * PW * 64) + (NW == 8 ? 3 : 2) * (2 * BN * 64) + 2 * AB32_BYTES;
     constexpr int epi = (BN > 64 ? 128 : 256) * (BN + 4) * 4;
-    constexpr int red = (64 * NW / (BN / 8)) * BN * 2 * 4;
+    constexpr int red = (64 * NW / (BN / 8)) * BN * 2 * 4 + BN * 4;   // the epilogue's [RPP][BN][2] sums and [BN] pivots
     constexpr int smem = stage > epi ? (stage > red ? stage : red) : (epi > red ? epi : red);
     const int norm = a.ab == nullptr ? 0 : (a.norm_silu ? 2 : 1);
     a.tiles_y = (a.H + THT - 1) / THT;
@@ -859,7 +903,8 @@ template <typename T, int BN, int WAVES_M, int TPS>
 int launch_halo(const HaloArgs& a, hipStream_t s) {
     constexpr int stage = PATCH_BYTES + 2 * TPS * BN * 128;
     constexpr int epi = (256 / (BN > 64 ? 2 : 1)) * (BN + 4) * 4;
-    constexpr int smem = stage > epi ? stage : epi;
+    constexpr int red = (256 / (BN / 8)) * BN * 2 * 4 + BN * 4;   // the epilogue's [RPP][BN][2] sums and [BN] pivots
+    constexpr int smem = stage > epi ? (stage > red ? stage : red) : (epi > red ? epi : red);
     const int64_t nwg = (int64_t)a.tiles_x * a.tiles_y * a.B * ((a.Cout + BN - 1) / BN);
     if (nwg >= ((int64_t)1 << 31)) return RSVLD_EUNSUPPORTED;
     auto go = [&](auto kern_c) -> int {
@@ -907,10 +952,11 @@ extern "C" int rsvld_conv3x3_halo_supported(const rsvld_conv_desc* d) {
 }
 
 extern "C" int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* norm_scale_shift, int norm_silu,
-                                       float* out_stats_partials, void* stream) {
+                                       double* out_stats_partials, void* stream) {
     if (!rsvld_conv3x3_halo_supported(d)) return RSVLD_EUNSUPPORTED;
     if (d->x == nullptr || d->w == nullptr || d->out == nullptr) return RSVLD_EINVAL;
     if (d->B <= 0 || d->Cout <= 0 || d->Cout % 8 != 0) return RSVLD_EINVAL;
+    if (((uintptr_t)out_stats_partials & 7) != 0) return RSVLD_EINVAL;   // fp64 partials
     if ((d->Cin2 > 0) != (d->x2 != nullptr)) return RSVLD_EINVAL;
     const bool split = d->dtype == RSVLD_SPLIT, w2 = d->dtype == RSVLD_F16W2, hq = d->dtype == RSVLD_F16Q8;
     const int seg = split ? 3 : w2 ? 2 : hq ? 5 : 1;

@@ -4,9 +4,10 @@
 // [lo(C) | hi(C)] with hi = bf16(v), lo = bf16(v - hi).  The two families share the partial pass (one template over an input
 // trait), the geometry, the source selection, the reduction tails, the output-form store and the host side; the apply pass and
 // LayerNorm stay one kernel per family (see there).
-// HBM-bound: every pass moves 16 B (fp32 input: 32 B) per lane and row, statistics in fp32 with a deterministic two-level
-// reduction (per-block partials -> fp64 finalize), no atomics.
+// HBM-bound: every pass moves 16 B (fp32 input: 32 B) per lane and row.  Statistics: per-block partials merged in fp64 in a fixed
+// order (deterministic, no atomics); an fp32 input's partials are fp64 themselves, from pivoted fp32 sums: see "pivot sums" below.
 #include "rsvld_common.h"
+#include <cstdint>
 #include <type_traits>
 
 namespace {
@@ -21,6 +22,8 @@ struct Io16 {   // f16 / bf16 rows in and out: 16 B per piece
     typedef T out;
     typedef u32x4 raw;
     static constexpr int U = 4;   // 4 independent 16-B loads in flight
+    static constexpr bool PIVOT = false;   // plain fp32 sums inside a thread (see "pivot sums")
+    typedef float part;                    // ... and fp32 row-chunk partials: this pass is what it always was
     static constexpr int ln_rows(int maxc) { return maxc <= 2 ? 4 : maxc == 3 ? 3 : maxc == 4 ? 2 : 1; }   // LayerNorm rows per wave
     // at most 4096 blocks: waves keep gamma / beta in registers over their rows
     static constexpr int LN_MAX_BLOCKS = 4096;
@@ -51,6 +54,8 @@ struct IoF32 {   // fp32 rows in (32 B per piece), OUT rows out
     typedef float raw[8];
     static constexpr int out_form = OUT;
     static constexpr int U = 2;   // two rows (4 x 16 B) in flight
+    static constexpr bool PIVOT = true;
+    typedef double part;
     static constexpr int ln_rows(int maxc) { return maxc <= 3 ? 2 : 1; }
     // at most ~3 resident workgroups per CU of a 256-CU chip: a wave then walks several row groups and its gamma / beta rows (as many
     // bytes as two rows of x at C = 1 280) are loaded once per wave instead of once per two rows (round 5: 4 096 workgroups of one row
@@ -83,7 +88,8 @@ struct GnGeom {
         TPR = C8 < 256 ? C8 : 256;
         rif = 256 / TPR;
     }
-    size_t lds_bytes() const { return (size_t)rif * C * 2 * sizeof(float); }   // gn_partial_kernel's [rif][C][2]
+    // gn_partial_kernel's [rif][C][2], and the pivots [C] where it has them
+    size_t lds_bytes(bool pivots) const { return ((size_t)rif * C * 2 + (pivots ? C : 0)) * sizeof(float); }
 };
 
 // chunk cc of image b of the channel concatenation [x1 (C1) | x2 (C2)]: declares src (its source's first row), cstride (that
@@ -112,6 +118,20 @@ struct GnGeom {
 #define GN_BLOCK_GET2(s, ss, red)                                \
     s = red[0][0] + red[0][1] + red[0][2] + red[0][3];           \
     ss = red[1][0] + red[1][1] + red[1][2] + red[1][3]
+// Pivot sums.  var = E[x^2] - mean^2 from (sum, sumsq) needs the pair to 2^-p (mean / sigma)^2 of the variance: fp64 holds that for any
+// input these kernels can store, fp32 does not (2^-24 * 64^2 = 2.4e-4 of the variance at mean / sigma = 64).  So every (sum, sumsq) of an
+// fp32 tensor that leaves a block is fp64.  Inside a thread the sums stay fp32 and cheap: the thread subtracts a pivot k -- one of
+// the very values it sums, so |x - k| is a few sigma -- and keeps s = sum (x - k), q = sum (x - k)^2, which carry the spread alone; then
+// (sum, sumsq) = (s + n k, q + 2 k s + n k^2) in fp64.  One subtraction per element, no further pass over the data, and exact
+// integer sums where the old fp32 pair was exact.
+// The fp32-input kernels do this.  The 16-bit kernels (the row-chunk pass with its fp32 partials, and the one-workgroup kernel) are
+// unchanged, so their statistics are bit for bit what they were: there the subtraction costs time (+3.4 % on a 1024 x 1024 x 64
+// map) and buys nothing the 16-bit bounds can see -- the storage types stop at mean / sigma = 128 (fp16) and 16 (bf16), where the
+// fp32 pair leaves 2.4e-3 and 6e-5 of the variance.
+__device__ __forceinline__ void gn_unpivot(double s, double q, double n, double k, double& sum, double& sumsq) {
+    sum = s + n * k;
+    sumsq = q + k * (2.0 * s + n * k);
+}
 // fp64 sums -> mean and biased variance, clamped at 0
 __device__ __forceinline__ void gn_moments(double s, double ss, double inv_count, double& mean, double& var) {
     mean = s * inv_count;
@@ -126,13 +146,15 @@ __device__ __forceinline__ void gn_moments(double s, double ss, double inv_count
 __device__ __forceinline__ float gn_affine_s(const float* beta, int c, float mean, float a) { return (beta ? beta[c] : 0.f) - mean * a; }
 
 // ---------------------------------------------------------------------------------------
-// pass 1: per (image, row-chunk) partial sums  part[b][chunk][g] = (sum, sumsq)
+// pass 1: per (image, row-chunk) partial sums  part[b][chunk][g] = (sum, sumsq), fp64 for an fp32 input (In::part)
 // thread -> fixed 8-channel chunk, strided over rows; per-channel sums go through LDS so
 // that any group size (2 .. C/groups, not necessarily a multiple of 8) is handled.
+// A channel's pivot is its value in the chunk's first row, for every thread of the block (kept in LDS for the threads that add
+// the groups up), so the LDS rows stay fp32 pairs of pivoted sums.
 // ---------------------------------------------------------------------------------------
 template <typename In>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* __restrict__ x1,
-                                                         const typename In::in* __restrict__ x2, float* __restrict__ part,
+                                                         const typename In::in* __restrict__ x2, typename In::part* __restrict__ part,
                                                          int HW, int C1, int C2, int groups, int rows_per_chunk, int nchunks) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* sm = (float*)smem_raw;  // [rif][C][2]
@@ -144,10 +166,18 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* 
     const int tc = tid % geo.TPR, rsub = tid / geo.TPR;
     if (rsub < geo.rif) {
         for (int cc = tc; cc < geo.C8; cc += geo.TPR) {
-            float s[8], ss[8];
+            float s[8], ss[8], k[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
             GN_SOURCE(typename In::in, x1, x2, b, HW, C1, C2, geo.C1_8, cc)
+            if constexpr (In::PIVOT) {
+                typename In::raw v;
+                In::load(src + (int64_t)row_lo * cstride + coff, v);
+                In::cvt(v, k);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) k[e] = 0.f;
+            }
             int r = row_lo + rsub;
             if constexpr (In::U == 2) {   // (fp32 input in its own words: through the generic loop below it compiles 13 lines shorter)
                 for (; r + geo.rif < row_hi; r += 2 * geo.rif) {
@@ -155,9 +185,9 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* 
                     ld8f(src + (int64_t)r * cstride + coff, f0);
                     ld8f(src + (int64_t)(r + geo.rif) * cstride + coff, f1);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { s[e] += f0[e]; ss[e] += f0[e] * f0[e]; }
+                    for (int e = 0; e < 8; ++e) { const float d = f0[e] - k[e]; s[e] += d; ss[e] += d * d; }
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { s[e] += f1[e]; ss[e] += f1[e] * f1[e]; }
+                    for (int e = 0; e < 8; ++e) { const float d = f1[e] - k[e]; s[e] += d; ss[e] += d * d; }
                 }
             } else
             for (; r + (In::U - 1) * geo.rif < row_hi; r += In::U * geo.rif) {  // U independent rows in flight
@@ -169,7 +199,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* 
                     float f[8];
                     In::cvt(v[u], f);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
+                    for (int e = 0; e < 8; ++e) { const float d = f[e] - k[e]; s[e] += d; ss[e] += d * d; }
                 }
             }
             for (; r < row_hi; r += geo.rif) {
@@ -178,30 +208,55 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const typename In::in* 
                 float f[8];
                 In::cvt(v, f);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
+                for (int e = 0; e < 8; ++e) { const float d = f[e] - k[e]; s[e] += d; ss[e] += d * d; }
             }
             float* dst = sm + ((int64_t)rsub * geo.C + cc * 8) * 2;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { dst[2 * e] = s[e]; dst[2 * e + 1] = ss[e]; }
+            if (In::PIVOT && rsub == 0) {   // (after the row loop: stored before it, the pivot's load would have to land before the first row is asked for)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sm[geo.rif * geo.C * 2 + cc * 8 + e] = k[e];
+            }
         }
     }
     __syncthreads();
     const int gs = geo.C / groups;
     for (int g = tid; g < groups; g += 256) {
-        float s = 0.f, ss = 0.f;
-        for (int r = 0; r < geo.rif; ++r) {
-            const float* src = sm + ((int64_t)r * geo.C + g * gs) * 2;
-            for (int e = 0; e < gs; ++e) { s += src[2 * e]; ss += src[2 * e + 1]; }
+        typename In::part* o = part + (((int64_t)b * nchunks + chunk) * groups + g) * 2;
+        if constexpr (In::PIVOT) {
+            const double nrows = (double)(row_hi - row_lo);
+            double s = 0.0, ss = 0.0;
+            for (int e = 0; e < gs; ++e) {
+                const int c = g * gs + e;
+                float cs = 0.f, cq = 0.f;   // the channel's pivoted sums over the rows in flight
+                for (int r = 0; r < geo.rif; ++r) {
+                    const float* q = sm + ((int64_t)r * geo.C + c) * 2;
+                    cs += q[0];
+                    cq += q[1];
+                }
+                double sum, sumsq;
+                gn_unpivot((double)cs, (double)cq, nrows, (double)sm[geo.rif * geo.C * 2 + c], sum, sumsq);
+                s += sum;
+                ss += sumsq;
+            }
+            o[0] = s;
+            o[1] = ss;
+        } else {
+            float s = 0.f, ss = 0.f;
+            for (int r = 0; r < geo.rif; ++r) {
+                const float* src = sm + ((int64_t)r * geo.C + g * gs) * 2;
+                for (int e = 0; e < gs; ++e) { s += src[2 * e]; ss += src[2 * e + 1]; }
+            }
+            o[0] = s;
+            o[1] = ss;
         }
-        float* o = part + (((int64_t)b * nchunks + chunk) * groups + g) * 2;
-        o[0] = s;
-        o[1] = ss;
     }
 }
 
 // pass 2: stats[b][g] = (mean, biased var); one wave per (image, group), lanes stride over the
 // chunk partials, fp64 merge in a fixed order (deterministic)
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats,
+template <typename P>
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const P* __restrict__ part, float* __restrict__ stats,
                                                           int groups, int nchunks, double inv_count, int total) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -209,7 +264,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     const int b = i / groups, g = i - b * groups;
     double s = 0.0, ss = 0.0;
     for (int c = lane; c < nchunks; c += 64) {
-        const float* p = part + (((int64_t)b * nchunks + c) * groups + g) * 2;
+        const P* p = part + (((int64_t)b * nchunks + c) * groups + g) * 2;
         s += (double)p[0];
         ss += (double)p[1];
     }
@@ -227,9 +282,10 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 //   PER_CHANNEL = false: partials [b][chunk][group][2] from gn_partial_kernel (a statistics pass over x)
 //   PER_CHANNEL = true : partials [b][tile][Cset][2] written by a conv epilogue (conv_halo.hip), one or two
 //                        producers (the skip concat [x | x2] is normalised jointly)
-template <bool PER_CHANNEL>
-__global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ part1, int n1, int C1,
-                                                    const float* __restrict__ part2, int n2, int C2,
+//   P: the partials' type: double from an epilogue or an fp32 input's statistics pass, float from a 16-bit input's
+template <bool PER_CHANNEL, typename P>
+__global__ __launch_bounds__(256) void gn_ab_kernel(const P* __restrict__ part1, int n1, int C1,
+                                                    const P* __restrict__ part2, int n2, int C2,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float* __restrict__ ab, float* __restrict__ stats_out, int groups,
                                                     float eps, double inv_count) {
@@ -240,7 +296,7 @@ __global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ pa
     double s = 0.0, ss = 0.0;
     if (PER_CHANNEL) {
         for (int c = g * gs; c < (g + 1) * gs; ++c) {
-            const float* base;
+            const P* base;
             int n, Cs, cc;
             if (c < C1) { base = part1 + (int64_t)b * n1 * C1 * 2; n = n1; Cs = C1; cc = c; }
             else { base = part2 + (int64_t)b * n2 * C2 * 2; n = n2; Cs = C2; cc = c - C1; }
@@ -251,7 +307,7 @@ __global__ __launch_bounds__(256) void gn_ab_kernel(const float* __restrict__ pa
         }
     } else {
         for (int t = tid; t < n1; t += 256) {
-            const float* q = part1 + (((int64_t)b * n1 + t) * groups + g) * 2;
+            const P* q = part1 + (((int64_t)b * n1 + t) * groups + g) * 2;
             s += (double)q[0];
             ss += (double)q[1];
         }
@@ -653,7 +709,7 @@ struct GnPlan {
     int nchunks, rows_per_chunk;
 };
 GnPlan gn_plan(int B, int HW) {
-    (void)B;   // the chunking fixes the order of the fp32 partial sums: it depends on the image size only, so an image's
+    (void)B;   // the chunking fixes the order of the partial sums: it depends on the image size only, so an image's
                // statistics are bit-identical whatever the batch around it
     const int max_chunks = 512;
     int rpc = (HW + max_chunks - 1) / max_chunks;
@@ -669,6 +725,7 @@ bool gn_dims_ok(int B, int HW, int C1, int C2) { return B > 0 && HW > 0 && C1 > 
 bool gn_x_ok(const void* x, const void* x2, int B, int HW, int C1, int C2) {
     return x != nullptr && gn_dims_ok(B, HW, C1, C2) && (C2 > 0) == (x2 != nullptr);
 }
+bool gn_align8(const void* p) { return ((uintptr_t)p & 7) == 0; }   // fp64 partials
 bool gn_groups_ok(int C, int groups) { return groups > 0 && C % groups == 0 && C <= 8192 && groups <= 256; }
 bool gn_mod_ok(const void* mod_scale1p, const void* mod_shift, int mod_stride, int align) {
     return (mod_scale1p != nullptr) == (mod_shift != nullptr) && mod_stride >= 0 && mod_stride % align == 0;
@@ -677,11 +734,18 @@ bool gn_mod_ok(const void* mod_scale1p, const void* mod_shift, int mod_stride, i
 double gn_inv_count(int HW, int C, int groups) { return 1.0 / ((double)HW * (double)(C / groups)); }
 
 template <typename In>
-void launch_partials(const void* x, const void* x2, float* part, int B, int HW, int C1, int C2, int groups, const GnPlan& pl,
+bool launch_partials(const void* x, const void* x2, typename In::part* part, int B, int HW, int C1, int C2, int groups, const GnPlan& pl,
                      hipStream_t s) {
     typedef typename In::in T;
-    hipLaunchKernelGGL(gn_partial_kernel<In>, dim3(pl.nchunks, B), dim3(256), GnGeom(C1, C2).lds_bytes(), s, (const T*)x,
+    const size_t lds = GnGeom(C1, C2).lds_bytes(In::PIVOT);
+    if (lds > 65536) {   // C > 5 460 with pivots: more than the 64 KiB of dynamic LDS a kernel gets unasked
+        static const hipError_t lds_attr = hipFuncSetAttribute((const void*)gn_partial_kernel<In>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                               (int)GnGeom(8192, 0).lds_bytes(In::PIVOT));
+        if (lds_attr != hipSuccess) return false;
+    }
+    hipLaunchKernelGGL(gn_partial_kernel<In>, dim3(pl.nchunks, B), dim3(256), lds, s, (const T*)x,
                        (const T*)x2, part, HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
+    return true;
 }
 
 // partials in ws -> (mean, var) rows
@@ -689,9 +753,10 @@ template <typename In>
 int gn_stats_impl(const void* x, const void* x2, float* stats, int B, int HW, int C1, int C2, int groups, void* ws,
                   hipStream_t s) {
     const GnPlan pl = gn_plan(B, HW);
-    launch_partials<In>(x, x2, (float*)ws, B, HW, C1, C2, groups, pl, s);
+    typedef typename In::part P;
+    if (!launch_partials<In>(x, x2, (P*)ws, B, HW, C1, C2, groups, pl, s)) return RSVLD_ELAUNCH;
     const int total = B * groups;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s, (const float*)ws, stats, groups, pl.nchunks,
+    hipLaunchKernelGGL(gn_finalize_kernel<P>, dim3((total + 3) / 4), dim3(256), 0, s, (const P*)ws, stats, groups, pl.nchunks,
                        gn_inv_count(HW, C1 + C2, groups), total);
     return rsvld_check_launch();
 }
@@ -701,8 +766,9 @@ template <typename In>
 int gn_scale_shift_impl(const void* x, const void* x2, const float* gamma, const float* beta, float* scale_shift, int B, int HW,
                         int C1, int C2, int groups, float eps, void* ws, hipStream_t s) {
     const GnPlan pl = gn_plan(B, HW);
-    launch_partials<In>(x, x2, (float*)ws, B, HW, C1, C2, groups, pl, s);
-    hipLaunchKernelGGL(gn_ab_kernel<false>, dim3(groups, B), dim3(256), 0, s, (const float*)ws, pl.nchunks, C1 + C2, nullptr, 0, 0,
+    typedef typename In::part P;
+    if (!launch_partials<In>(x, x2, (P*)ws, B, HW, C1, C2, groups, pl, s)) return RSVLD_ELAUNCH;
+    hipLaunchKernelGGL((gn_ab_kernel<false, P>), dim3(groups, B), dim3(256), 0, s, (const P*)ws, pl.nchunks, C1 + C2, (const P*)nullptr, 0, 0,
                        gamma, beta, scale_shift, nullptr, groups, eps, gn_inv_count(HW, C1 + C2, groups));
     return rsvld_check_launch();
 }
@@ -774,8 +840,8 @@ extern "C" int64_t rsvld_groupnorm_ws_bytes(int B, int HW, int C, int groups) {
     (void)C;
     if (B <= 0 || HW <= 0 || groups <= 0) return 0;
     const GnPlan pl = gn_plan(B, HW);
-    // partials + final stats
-    return ((int64_t)B * pl.nchunks * groups * 2 + (int64_t)B * groups * 2) * (int64_t)sizeof(float);
+    // room for fp64 partials (an fp32 input's; a 16-bit input's are fp32 and fill half of it), then the final fp32 stats
+    return (int64_t)B * pl.nchunks * groups * 2 * (int64_t)sizeof(double) + (int64_t)B * groups * 2 * (int64_t)sizeof(float);
 }
 
 extern "C" int rsvld_groupnorm_stats(const void* x, const void* x2, float* mean_var, int B, int HW, int C1, int C2,
@@ -812,7 +878,7 @@ extern "C" int rsvld_groupnorm_nhwc(const void* x, const void* x2, void* y, cons
         return gn_small_impl<bf16, true>(x, x2, y, nullptr, gamma, beta, B, HW, C1, C2, groups, eps, silu, s);
     }
     const GnPlan pl = gn_plan(B, HW);
-    float* stats = (float*)ws + (int64_t)B * pl.nchunks * groups * 2;
+    float* stats = (float*)((double*)ws + (int64_t)B * pl.nchunks * groups * 2);
     int rc = rsvld_groupnorm_stats(x, x2, stats, B, HW, C1, C2, groups, dtype, ws, stream);
     if (rc != RSVLD_OK) return rc;
     return rsvld_groupnorm_apply(x, x2, y, stats, gamma, beta, mod_scale1p, mod_shift, mod_stride, B, HW, C1, C2, groups,
@@ -833,13 +899,14 @@ extern "C" int rsvld_groupnorm_scale_shift(const void* x, const void* x2, const 
     return gn_scale_shift_impl<Io16<bf16>>(x, x2, gamma, beta, scale_shift, B, HW, C1, C2, groups, eps, ws, s);
 }
 
-extern "C" int rsvld_groupnorm_scale_shift_from_partials(const float* part1, int ntiles1, int C1, const float* part2,
+extern "C" int rsvld_groupnorm_scale_shift_from_partials(const double* part1, int ntiles1, int C1, const double* part2,
                                                          int ntiles2, int C2, const float* gamma, const float* beta,
                                                          float* scale_shift, int B, int HW, int groups, float eps,
                                                          void* stream) {
     if (!part1 || !scale_shift || B <= 0 || HW <= 0 || C1 <= 0 || C2 < 0 || ntiles1 <= 0 || groups <= 0) return RSVLD_EINVAL;
     if ((C2 > 0) != (part2 != nullptr) || (C2 > 0 && ntiles2 <= 0) || (C1 + C2) % groups != 0 || B > 65535) return RSVLD_EINVAL;
-    hipLaunchKernelGGL(gn_ab_kernel<true>, dim3(groups, B), dim3(256), 0, (hipStream_t)stream, part1, ntiles1, C1, part2,
+    if (!gn_align8(part1) || !gn_align8(part2)) return RSVLD_EINVAL;
+    hipLaunchKernelGGL((gn_ab_kernel<true, double>), dim3(groups, B), dim3(256), 0, (hipStream_t)stream, part1, ntiles1, C1, part2,
                        ntiles2, C2, gamma, beta, scale_shift, nullptr, groups, eps, gn_inv_count(HW, C1 + C2, groups));
     return rsvld_check_launch();
 }
@@ -858,7 +925,7 @@ extern "C" int rsvld_layernorm(const void* x, void* y, const float* gamma, const
 extern "C" int rsvld_groupnorm_scale_shift_f32(const float* x, const float* x2, const float* gamma, const float* beta,
                                                float* scale_shift, int B, int HW, int C1, int C2, int groups, float eps, void* ws,
                                                void* stream) {
-    if (!ws || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
+    if (!ws || !gn_align8(ws) || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
     return gn_scale_shift_impl<InF32>(x, x2, gamma, beta, scale_shift, B, HW, C1, C2, groups, eps, ws, (hipStream_t)stream);
 }
 
@@ -887,7 +954,7 @@ extern "C" int rsvld_layernorm_split(const float* x, void* out, const float* gam
 
 extern "C" int rsvld_groupnorm_stats_f32_fast(const float* x, const float* x2, float* mean_var, int B, int HW, int C1, int C2, int groups,
                                               void* ws, void* stream) {
-    if (!mean_var || !ws || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
+    if (!mean_var || !ws || !gn_align8(ws) || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups) || B > 65535) return RSVLD_EINVAL;
     return gn_stats_impl<InF32>(x, x2, mean_var, B, HW, C1, C2, groups, ws, (hipStream_t)stream);
 }
 

@@ -728,11 +728,11 @@ def _halo_wgs(B, Ho, Wo, cout_p, plan_div):
 
 def _halo_launch(name, flops, nbytes, d, out, ab, silu, stats):
     """rsvld_conv3x3_halo_nhwc on descriptor ``d`` (``ab`` / ``silu``: the fused GroupNorm of its input, or None / 0).  ``stats``: the
-    epilogue writes per-tile per-channel (sum, sumsq) of the output, attached to ``out`` as ``_gn_part`` for the consumer's ``norm=``."""
+    epilogue writes per-tile per-channel fp64 (sum, sumsq) of the output, attached to ``out`` as ``_gn_part`` for the consumer's ``norm=``."""
     part_out = None
     if stats:
         ntiles = _halo_tiles(d.Ho, d.Wo)
-        part_out = torch.empty((d.B, ntiles, d.Cout, 2), device=out.device, dtype=torch.float32)
+        part_out = torch.empty((d.B, ntiles, d.Cout, 2), device=out.device, dtype=torch.float64)
     _launch(name, flops, nbytes, lambda: L.check(L.load().rsvld_conv3x3_halo_nhwc(C.byref(d), _ptr(ab), int(silu), _ptr(part_out), _stream()),
                                                  "rsvld_conv3x3_halo_nhwc"))
     if part_out is not None:

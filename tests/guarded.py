@@ -7,7 +7,7 @@ lives in a buffer of its own,
 
     [ front guard | payload | rear guard ]         every byte outside the payload = 0xFF
 
-* 0xFF bytes are NaN as fp16, bf16, fp32 and e4m3 and -1 as an integer (``poison_is_nan``): one fill serves every operand type,
+* 0xFF bytes are NaN as fp16, bf16, fp32, fp64 and e4m3 and -1 as an integer (``poison_is_nan``): one fill serves every operand type,
   and a stray read that reaches a result makes it non-finite (0 * NaN = NaN).
 * the payload starts 256-byte aligned (the alignment of an allocator block, which vector loads may rely on) and ends FLUSH
   against the rear guard: the first byte past the last element is poison.  Aligned by over-allocating and offsetting, and
@@ -39,7 +39,7 @@ POISON = 0xFF
 ALIGN = 256
 MIN_GUARD = 1 << 20
 TILE_ROWS = 512
-POISON_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float8_e4m3fn)
+POISON_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.float8_e4m3fn)
 
 
 class GuardError(AssertionError):

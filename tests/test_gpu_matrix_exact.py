@@ -585,7 +585,7 @@ def test_halo_exact_output_and_partials(cuda, dtype, row, hs):
     c = build_halo_exact(dtype, row.cout, hs)
     got, part = _halo_call(ops, cuda, dtype, row, c, hs)
     assert torch.equal(got.cpu(), c["want"].to(dtype))
-    assert part.dtype == F32 and tuple(part.shape) == tuple(c["part"].shape)
+    assert part.dtype == torch.float64 and tuple(part.shape) == tuple(c["part"].shape)
     assert torch.equal(part.cpu().double(), c["part"])
 
 
