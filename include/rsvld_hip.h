@@ -165,6 +165,22 @@ int rsvld_conv3x3_halo_supported(const rsvld_conv_desc* d);
 int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* norm_scale_shift, int norm_silu,
                             double* out_stats_partials, void* stream);
 
+/* The launch plan of a convolution descriptor, as a HOST-ONLY query: no device is touched and the descriptor's pointers are compared
+ * with NULL only (any non-NULL value stands for a tensor).  Returns what rsvld_conv2d_nhwc would return for `d` before it launches:
+ * RSVLD_EINVAL / RSVLD_EUNSUPPORTED from the same check, else RSVLD_OK with the kernel it would run -- gemm256 != 0, or the
+ * implicit-GEMM instantiation (bm x bn tile, LDS ring depth, K groups per workgroup, staging), RSVLD_TUNE_* bits included.
+ * The halo_* fields answer for rsvld_conv3x3_halo_nhwc and are filled whatever the return code: halo_bn = 0 where
+ * rsvld_conv3x3_halo_supported says no; else the kernel's column block and waves, the workgroups of ONE planning unit (B / plan_div
+ * images, counted on 8 x 32-pixel tiles also where the 8-wave kernel runs 16 x 32: the figure a caller compares with its own
+ * threshold before preferring the halo kernel) and the tiles per image, the second dimension of out_stats_partials. */
+typedef struct rsvld_conv_plan {
+    int64_t halo_wgs;
+    int32_t halo_bn, halo_waves, halo_stat_tiles;
+    int32_t gemm256;       /* 0: the implicit-GEMM kernel; 1: gemm256, eligible for its persistent form; 2: gemm256, one tile per workgroup */
+    int32_t bm, bn, stages, ks, reg_staging;   /* zeros unless the implicit-GEMM kernel runs */
+} rsvld_conv_plan;
+int rsvld_plan_conv(const rsvld_conv_desc* d, rsvld_conv_plan* plan);
+
 /* ---------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU / Swish) over NHWC, statistics in fp32, two launches
  * (deterministic fp32 partial sums per row chunk, merged in fp64 -> finalize+apply).  `ws` must hold
@@ -180,6 +196,14 @@ int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* norm_scale_sh
  *   SR_modules.py:59-110 (ZeroSFT param_free_norm), :113-149 (ZeroCrossAttn norm1/2).
  * ------------------------------------------------------------------------------------- */
 int64_t rsvld_groupnorm_ws_bytes(int B, int HW, int C, int groups);
+/* The statistics route of a GroupNorm over [x (C1) | x2 (C2)], as a HOST-ONLY query (dtype RSVLD_F16 / RSVLD_BF16, or RSVLD_F32 for the
+ * fp32-input entry points further down).  small = 1: rsvld_groupnorm_nhwc (without a modulation) and rsvld_groupnorm_scale_shift run one
+ * workgroup per (image, group); 0: partial sums per chunk of rows.  nchunks x rows_per_chunk cover HW on that route (every entry point
+ * with a `ws`); rows_in_flight: the rows a block of its statistics kernel reads at once.  RSVLD_EINVAL for sizes the entry points refuse. */
+typedef struct rsvld_groupnorm_plan {
+    int32_t small, nchunks, rows_per_chunk, rows_in_flight;
+} rsvld_groupnorm_plan;
+int rsvld_plan_groupnorm(int dtype, int B, int HW, int C1, int C2, int groups, rsvld_groupnorm_plan* plan);
 int rsvld_groupnorm_nhwc(const void* x, const void* x2, void* y,
                          const float* gamma, const float* beta,
                          const void* mod_scale1p, const void* mod_shift, int mod_stride,

@@ -50,6 +50,20 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlan(C.Structure):
+    """rsvld_conv_plan: what rsvld_plan_conv says of a ConvDesc (host only)."""
+    _fields_ = [
+        ("halo_wgs", C.c_int64), ("halo_bn", C.c_int32), ("halo_waves", C.c_int32), ("halo_stat_tiles", C.c_int32),
+        ("gemm256", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("stages", C.c_int32), ("ks", C.c_int32),
+        ("reg_staging", C.c_int32),
+    ]
+
+
+class GroupnormPlan(C.Structure):
+    """rsvld_groupnorm_plan (rsvld_plan_groupnorm, host only)."""
+    _fields_ = [("small", C.c_int32), ("nchunks", C.c_int32), ("rows_per_chunk", C.c_int32), ("rows_in_flight", C.c_int32)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every symbol include/rsvld_hip.h declares
@@ -58,6 +72,8 @@ SIGNATURES = {
     "rsvld_conv2d_nhwc": (_i, [C.POINTER(ConvDesc), _vp]),
     "rsvld_conv3x3_halo_supported": (_i, [C.POINTER(ConvDesc)]),
     "rsvld_conv3x3_halo_nhwc": (_i, [C.POINTER(ConvDesc), _vp, _i, _vp, _vp]),
+    "rsvld_plan_conv": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvPlan)]),
+    "rsvld_plan_groupnorm": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(GroupnormPlan)]),
     "rsvld_groupnorm_scale_shift_from_partials": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "rsvld_groupnorm_scale_shift": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     "rsvld_groupnorm_ws_bytes": (_i64, [_i, _i, _i, _i]),

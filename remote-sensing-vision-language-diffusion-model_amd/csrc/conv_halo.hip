@@ -15,6 +15,7 @@
 // L2->LDS bytes per 256 pixels x 64 channels: 43.5 KiB patch + 9 x BN x 128 B weights, vs
 // 9 x (256+BN) x 128 B for the gather.  MFMA work per barrier doubles (32 MFMAs per wave per tap).
 #include "rsvld_common.h"
+#include "rsvld_plan.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -51,7 +52,7 @@ struct HaloArgs {
     int seg, Cseg;
 };
 
-constexpr int TH = 8, TW = 32, PW = TW + 2, PROWS = (TH + 2) * PW;   // 340 patch pixels
+constexpr int TH = rsvld_plan::HALO_TH, TW = rsvld_plan::HALO_TW, PW = TW + 2, PROWS = (TH + 2) * PW;   // 340 patch pixels
 constexpr int PATCH_BYTES = PROWS * 128;
 constexpr int PLOADS = (PROWS * 8 + 255) / 256;                        // 11 16-byte pieces per thread
 
@@ -922,44 +923,31 @@ int launch_halo(const HaloArgs& a, hipStream_t s) {
     return go(HALO_K(conv_halo_kernel<T, BN, WAVES_M, TPS, 1>));
 }
 
+// The launch table: the three tile forms, named here and nowhere else.  rsvld_plan::plan_halo (rsvld_plan.h) picks the row.
 template <typename T>
-int dispatch_halo(const HaloArgs& a, hipStream_t s) {
-    if (a.Cout <= 64) return launch_halo<T, 64, 4, 2>(a, s);
-    // 16x32-pixel tiles (one 8-wave workgroup per CU) once that grid still covers most of the chip
-    const int64_t wg16 = (int64_t)a.tiles_x * ((a.H + 15) / 16) * a.B_plan * ((a.Cout + 127) / 128);
-    // measured (tools/bench_halo.py, one box): +3..13 % from 192 channels of K up, -3 % at 128 (longer pipeline fill)
-    const bool use8 = (a.tune & RSVLD_TUNE_HALO_NW8) ? true : (a.tune & RSVLD_TUNE_HALO_NW4) ? false
-                                                             : (wg16 >= 192 && a.Ctot >= 192);
-    if (use8) return launch_halo32<T, 128, 8>(a, s);
-    return launch_halo32<T, 128, 4>(a, s);
+int launch_plan(const rsvld_plan::HaloPlan& p, const HaloArgs& a, hipStream_t s) {
+    if (p.bn == 64 && p.waves == 4) return launch_halo<T, 64, 4, 2>(a, s);
+    if (p.bn == 128 && p.waves == 4) return launch_halo32<T, 128, 4>(a, s);
+    if (p.bn == 128 && p.waves == 8) return launch_halo32<T, 128, 8>(a, s);
+    return RSVLD_EUNSUPPORTED;
 }
 
 }  // namespace
 
-// 3x3 / stride 1 / pad 1, no up-sampling, every source a multiple of 64 channels
-extern "C" int rsvld_conv3x3_halo_supported(const rsvld_conv_desc* d) {
-    if (d == nullptr) return 0;
-    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1) return 0;
-    const int up = d->upsample ? 2 : 1;
-    if (d->Ho != up * d->H || d->Wo != up * d->W) return 0;
-    if (d->Cin % 64 != 0 || d->Cin2 % 64 != 0) return 0;
-    if (d->act == RSVLD_ACT_GEGLU) return 0;
-    if (d->out_f32 && d->Cout > 32 && d->dtype != RSVLD_SPLIT && d->dtype != RSVLD_F16W2 && d->dtype != RSVLD_F16Q8) return 0;
-    if (d->dtype == RSVLD_F16Q8 && (d->Cout <= 64 || !d->out_f32 || d->upsample || d->Cin2 != 0)) return 0;   // the 128-wide kernels only; fp32 out; ONE source
-                                                                                                              // (the GroupNorm apply pass that writes q8 rows has already concatenated)
-    if (d->Wo < 16 || d->Ho < 4) return 0;   // tiny maps: the 8x32 tile would be mostly padding
-    return 1;
-}
+// 3x3 / stride 1 / pad 1, every source a multiple of 64 channels (rsvld_plan.h)
+extern "C" int rsvld_conv3x3_halo_supported(const rsvld_conv_desc* d) { return rsvld_plan::halo_supported(d) ? 1 : 0; }
 
 extern "C" int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* norm_scale_shift, int norm_silu,
                                        double* out_stats_partials, void* stream) {
-    if (!rsvld_conv3x3_halo_supported(d)) return RSVLD_EUNSUPPORTED;
+    rsvld_plan::HaloPlan pl;
+    if (!rsvld_plan::plan_halo(d, &pl)) return RSVLD_EUNSUPPORTED;
     if (d->x == nullptr || d->w == nullptr || d->out == nullptr) return RSVLD_EINVAL;
     if (d->B <= 0 || d->Cout <= 0 || d->Cout % 8 != 0) return RSVLD_EINVAL;
     if (((uintptr_t)out_stats_partials & 7) != 0) return RSVLD_EINVAL;   // fp64 partials
     if ((d->Cin2 > 0) != (d->x2 != nullptr)) return RSVLD_EINVAL;
-    const bool split = d->dtype == RSVLD_SPLIT, w2 = d->dtype == RSVLD_F16W2, hq = d->dtype == RSVLD_F16Q8;
-    const int seg = split ? 3 : w2 ? 2 : hq ? 5 : 1;
+    const rsvld_plan::Forms f = rsvld_plan::forms_of(d->dtype);
+    const bool split = f.split, w2 = f.w2, hq = f.hq;
+    const int seg = rsvld_plan::halo_seg(f);
     if (d->dtype != RSVLD_F16 && d->dtype != RSVLD_BF16 && seg == 1) return RSVLD_EINVAL;
     if (d->out_f32 < 0 || d->out_f32 > 1) return RSVLD_EINVAL;   // (an fp16 output of RSVLD_SPLIT exists for the Linear layers only)
     if ((split || hq) && norm_scale_shift != nullptr) return RSVLD_EUNSUPPORTED;   // the normalised tensor is split by its own kernel (rsvld_groupnorm_apply_split)
@@ -973,12 +961,12 @@ extern "C" int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* no
     a.seg = seg;
     a.Cseg = d->Cin + d->Cin2;
     a.B = d->B; a.H = d->Ho; a.W = d->Wo; a.Cin = d->Cin; a.Cin2 = d->Cin2; a.Cout = d->Cout;
-    a.B_plan = d->plan_div > 1 ? (d->B + d->plan_div - 1) / d->plan_div : d->B;
+    a.B_plan = (int)rsvld_plan::plan_unit(d->B, d->plan_div);
     a.tune = d->tune;
     a.Hs = d->H; a.Ws = d->W; a.ush = d->upsample ? 1 : 0;
     a.out_f32 = d->out_f32 ? 1 : 0; a.act = d->act; a.norm_silu = norm_silu ? 1 : 0;
     a.alpha = d->alpha; a.beta = d->beta;
-    a.Ctot = (hq ? 2 : seg) * (d->Cin + d->Cin2);   // logical K' channels per tap (16-bit elements of a weight row)
+    a.Ctot = rsvld_plan::halo_ctot(d);
     a.nchunks = a.Ctot / 64;
     a.tiles_x = (d->Wo + TW - 1) / TW;
     a.tiles_y = (d->Ho + TH - 1) / TH;
@@ -986,5 +974,5 @@ extern "C" int rsvld_conv3x3_halo_nhwc(const rsvld_conv_desc* d, const float* no
     a.rv_stride = d->rowvec_stride > 0 ? d->rowvec_stride : d->Cout;
     a.Cout_out = d->Cout;
     hipStream_t s = (hipStream_t)stream;
-    return (d->dtype == RSVLD_F16 || w2 || hq) ? dispatch_halo<f16>(a, s) : dispatch_halo<bf16>(a, s);   // RSVLD_SPLIT runs the bf16 kernels, RSVLD_F16W2 the fp16 ones
+    return (d->dtype == RSVLD_F16 || w2 || hq) ? launch_plan<f16>(pl, a, s) : launch_plan<bf16>(pl, a, s);   // RSVLD_SPLIT runs the bf16 kernels, RSVLD_F16W2 the fp16 ones
 }

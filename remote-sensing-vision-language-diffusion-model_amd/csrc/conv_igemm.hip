@@ -32,6 +32,7 @@
 #include <string.h>
 
 #include "rsvld_common.h"
+#include "rsvld_plan.h"
 #include <type_traits>
 
 namespace {
@@ -507,89 +508,49 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
 #undef CONV_K
 }
 
-// Tile choice.  Cout <= 32: 256x32.  Cout <= 64: 128x64 (48 KiB LDS -> 3 workgroups per CU: these layers
-// have few K-steps per tile, so co-resident workgroups hide each other's prologue / epilogue).  Otherwise
-// 128x128, except when that grid would leave CUs idle (< 256 workgroups): then 64x128 doubles the grid.
-// All grid-size tests use M_plan (the rows of ONE of the plan_div stacked units): the plan, and with it the
-// order of every accumulation, does not depend on how many units share the launch.
-template <typename T, bool GLDS>
-int dispatch_conv2(const ConvArgs& a, hipStream_t s) {
-    if (a.Cout <= 32) return launch_conv<T, 256, 32, 4, 1, GLDS>(a, s);
-    const int ov = a.tune & RSVLD_TUNE_TILE_MASK;
-    const int st = GLDS ? ((a.tune >> RSVLD_TUNE_STAGES_SHIFT) & 7) : 2;
-    const bool ksplit = !(a.tune & RSVLD_TUNE_NO_KSPLIT);
-    if (a.Cout <= 64) {
-        if (ov == 1) return launch_conv<T, 256, 64, 4, 1, GLDS>(a, s);
-        if constexpr (GLDS) {   // measured: 3 WGs/CU x 1 tile in flight (48 KiB) beats 2 WGs/CU x 2 tiles (72 KiB)
-            if (st == 3) return launch_conv<T, 128, 64, 4, 1, true, 3>(a, s);
-            if (st == 4) return launch_conv<T, 128, 64, 4, 1, true, 4>(a, s);
-        }
-        return launch_conv<T, 128, 64, 4, 1, GLDS>(a, s);
-    }
-    const int64_t wg128 = (int64_t)((a.M_plan + 127) / 128) * ((a.Cout + 127) / 128);
-    const int64_t wg64x128 = (int64_t)((a.M_plan + 63) / 64) * ((a.Cout + 127) / 128);
-    if constexpr (GLDS) {
-        // small-M linears (Stage-2 transformer blocks at 16x16 / 32x32 tokens): even 64x128 leaves most CUs idle and
-        // the K loop is a latency-bound weight stream.  64x64 tiles double the grid again; 4 x 16 KiB stages keep
-        // 3 tiles in flight per workgroup at 2 workgroups per CU.
-        if (ov == 0 && wg64x128 < 256) {
-            const int64_t wg64 = (int64_t)((a.M_plan + 63) / 64) * ((a.Cout + 63) / 64);
-            if (ksplit && st == 0 && wg64 <= 256 && a.nk >= 16) return launch_conv<T, 64, 64, 2, 2, true, 4, 2>(a, s);
-            return launch_conv<T, 64, 64, 2, 2, true, 4>(a, s);
-        }
-    }
-    if (ov == 4 || (ov == 0 && wg128 < 256)) {
-        if constexpr (GLDS) {
-            // one 64x128 workgroup per CU at most and a long K loop: two K groups (8 waves) per tile
-            if (ksplit && st == 0 && wg64x128 <= 256 && a.nk >= 16) return launch_conv<T, 64, 128, 2, 2, true, 3, 2>(a, s);
-            if (st == 3 || st == 0) return launch_conv<T, 64, 128, 2, 2, true, 3>(a, s);   // 72 KiB: 2 WGs / CU
-            if (st == 4) return launch_conv<T, 64, 128, 2, 2, true, 4>(a, s);
-        }
-        return launch_conv<T, 64, 128, 2, 2, GLDS>(a, s);
-    }
-    if constexpr (GLDS) {   // measured: the 96 KiB ring drops to 1 WG/CU and loses 30 % to 2 x 64 KiB double buffers
-        if (st == 3) return launch_conv<T, 128, 128, 2, 2, true, 3>(a, s);
-        if (st == 4) return launch_conv<T, 128, 128, 2, 2, true, 4>(a, s);
-    }
-    return launch_conv<T, 128, 128, 2, 2, GLDS>(a, s);
-}
+// The launch table: every instantiation of conv_igemm_kernel, named here and nowhere else -- (BM, BN, WAVES_M, WAVES_N, GLDS, STAGES, KS),
+// 14 staged by LDS-DMA and 5 through registers.  rsvld_plan::plan_igemm (rsvld_plan.h) picks the row.
+#define CONV_TABLE(X)                                                                                   \
+    X(256, 32, 4, 1, true, 2, 1) X(256, 32, 4, 1, false, 2, 1)                                          \
+    X(256, 64, 4, 1, true, 2, 1) X(256, 64, 4, 1, false, 2, 1)                                          \
+    X(128, 64, 4, 1, true, 2, 1) X(128, 64, 4, 1, false, 2, 1)                                          \
+    X(128, 64, 4, 1, true, 3, 1) X(128, 64, 4, 1, true, 4, 1)                                           \
+    X(64, 64, 2, 2, true, 4, 1) X(64, 64, 2, 2, true, 4, 2)                                             \
+    X(64, 128, 2, 2, true, 2, 1) X(64, 128, 2, 2, false, 2, 1)                                          \
+    X(64, 128, 2, 2, true, 3, 1) X(64, 128, 2, 2, true, 3, 2) X(64, 128, 2, 2, true, 4, 1)              \
+    X(128, 128, 2, 2, true, 2, 1) X(128, 128, 2, 2, false, 2, 1)                                        \
+    X(128, 128, 2, 2, true, 3, 1) X(128, 128, 2, 2, true, 4, 1)
 
 template <typename T>
-int dispatch_conv(const ConvArgs& a, hipStream_t s) {
-    return (a.tune & RSVLD_TUNE_REG_STAGING) ? dispatch_conv2<T, false>(a, s) : dispatch_conv2<T, true>(a, s);
+int launch_plan(const rsvld_plan::IgemmPlan& p, const ConvArgs& a, hipStream_t s) {
+#define CONV_ROW(BM, BN, WM, WN, GLDS, STAGES, KS)                                                       \
+    if (p.bm == BM && p.bn == BN && p.reg_staging == (GLDS ? 0 : 1) && p.stages == STAGES && p.ks == KS) \
+        return launch_conv<T, BM, BN, WM, WN, GLDS, STAGES, KS>(a, s);
+    CONV_TABLE(CONV_ROW)
+#undef CONV_ROW
+    return RSVLD_EUNSUPPORTED;   // (no plan lies outside the table: tests/test_matrix_exact_cases.py sweeps the planner against it)
 }
 
 }  // namespace
 
 int rsvld_gemm256_try(const rsvld_conv_desc* d, void* stream);   // gemm.hip: large 1x1 / Linear layers
 
+extern "C" int rsvld_plan_conv(const rsvld_conv_desc* d, rsvld_conv_plan* plan) {
+    return plan == nullptr ? RSVLD_EINVAL : rsvld_plan::plan_conv(d, plan);
+}
+
 extern "C" int rsvld_conv2d_nhwc(const rsvld_conv_desc* d, void* stream) {
-    if (d == nullptr || d->x == nullptr || d->w == nullptr || d->out == nullptr) return RSVLD_EINVAL;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0) return RSVLD_EINVAL;
-    if (d->Cin <= 0 || d->Cin % 8 != 0 || d->Cout <= 0 || d->Cout % 8 != 0) return RSVLD_EINVAL;
-    if (d->Cin2 < 0 || d->Cin2 % 8 != 0 || ((d->Cin2 > 0) != (d->x2 != nullptr))) return RSVLD_EINVAL;
-    if (d->KH <= 0 || d->KW <= 0 || d->stride <= 0) return RSVLD_EINVAL;
-    // RSVLD_F16W1: the weight-pair kernels (SEG = 2: fp16 in, fp32 out + fp32 residual) over ONE K segment -- their second-segment wrap of the
-    // channel index never triggers when Ctot = Cseg, and the weight rows are K long
-    const bool split = d->dtype == RSVLD_SPLIT, w1 = d->dtype == RSVLD_F16W1, w2 = d->dtype == RSVLD_F16W2 || w1;
-    const int seg = split ? 3 : w2 ? 2 : 1;
-    if (d->dtype != RSVLD_F16 && d->dtype != RSVLD_BF16 && seg == 1) return RSVLD_EINVAL;
-    if (w1 && (d->out_f32 != 1 || d->KH != 1 || d->KW != 1)) return RSVLD_EINVAL;
-    if (d->out_f32 < 0 || d->out_f32 > 2 || (d->out_f32 == 2 && !split)) return RSVLD_EINVAL;
-    if (seg == 1 && d->out_f32 && (d->Cout > 32 || d->act == RSVLD_ACT_GEGLU || d->residual != nullptr)) return RSVLD_EUNSUPPORTED;
-    if (split && d->out_f32 != 1 && d->residual != nullptr) return RSVLD_EINVAL;   // planes / fp16 out of RSVLD_SPLIT: no residual (the stream stays fp32)
-    if (d->act == RSVLD_ACT_GEGLU && (d->Cout % 16 != 0 || d->residual != nullptr)) return RSVLD_EINVAL;
-    if ((int64_t)d->B * d->Ho * d->Wo >= (int64_t)1 << 31) return RSVLD_EUNSUPPORTED;
-    if ((int64_t)d->B * d->H * d->W >= (int64_t)1 << 31) return RSVLD_EUNSUPPORTED;
-    // every output pixel must read inside the (optionally up-sampled) padded input: shape sanity
     {
-        const int Hin = d->upsample ? 2 * d->H : d->H, Win = d->upsample ? 2 * d->W : d->W;
-        if ((d->Ho - 1) * d->stride - d->pad_t >= Hin || (d->Wo - 1) * d->stride - d->pad_l >= Win) return RSVLD_EINVAL;
+        const int rc = rsvld_plan::validate_conv(d);
+        if (rc != RSVLD_OK) return rc;
     }
     {
         const int rc = rsvld_gemm256_try(d, stream);   // the dedicated GEMM takes the shapes it is built for
         if (rc != RSVLD_EUNSUPPORTED) return rc;
     }
+    const rsvld_plan::Forms f = rsvld_plan::forms_of(d->dtype);
+    const bool split = f.split, w1 = f.w1, w2 = f.w2 || f.w1;
+    const int seg = rsvld_plan::igemm_seg(f);
     ConvArgs a;
     a.x = d->x; a.x2 = d->x2; a.w = d->w; a.bias = d->bias; a.rowvec = d->rowvec;
     a.residual = d->residual; a.out = d->out;
@@ -607,7 +568,7 @@ extern "C" int rsvld_conv2d_nhwc(const rsvld_conv_desc* d, void* stream) {
     a.Ho = d->Ho; a.Wo = d->Wo; a.upsample = d->upsample ? 1 : 0;
     a.out_f32 = d->out_f32 == 1 ? 1 : 0; a.act = d->act; a.alpha = d->alpha; a.beta = d->beta;
     a.M = d->B * d->Ho * d->Wo;
-    a.M_plan = d->plan_div > 1 ? (a.M + d->plan_div - 1) / d->plan_div : a.M;
+    a.M_plan = (int)rsvld_plan::plan_unit(a.M, d->plan_div);
     a.tune = d->tune;
     a.HoWo = d->Ho * d->Wo;
     a.C1_8 = d->Cin / 8;
@@ -617,9 +578,10 @@ extern "C" int rsvld_conv2d_nhwc(const rsvld_conv_desc* d, void* stream) {
     a.Cseg8 = (d->Cin + d->Cin2) / 8;
     a.Ctot8 = (w1 ? 1 : seg) * a.Cseg8;
     a.KC = d->KH * d->KW * a.Ctot8;
-    a.nk = (a.KC + 7) / 8;
+    a.nk = rsvld_plan::igemm_nk(d);   // K steps of 8 pieces over KC
     a.Cout_out = d->act == RSVLD_ACT_GEGLU ? d->Cout / 2 : d->Cout;
     a.rv_stride = d->rowvec_stride > 0 ? d->rowvec_stride : d->Cout;
     hipStream_t s = (hipStream_t)stream;
-    return (d->dtype == RSVLD_F16 || w2) ? dispatch_conv<f16>(a, s) : dispatch_conv<bf16>(a, s);   // RSVLD_SPLIT runs the bf16 kernels, RSVLD_F16W2 the fp16 ones
+    const rsvld_plan::IgemmPlan pl = rsvld_plan::plan_igemm(d);
+    return (d->dtype == RSVLD_F16 || w2) ? launch_plan<f16>(pl, a, s) : launch_plan<bf16>(pl, a, s);   // RSVLD_SPLIT runs the bf16 kernels, RSVLD_F16W2 the fp16 ones
 }

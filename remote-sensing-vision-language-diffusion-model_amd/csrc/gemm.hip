@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "rsvld_common.h"
+#include "rsvld_plan.h"
 #include <type_traits>
 
 namespace {
@@ -1074,39 +1075,26 @@ int gemm_go(dim3 grid, hipStream_t s, const GemmArgs& a) {
 }  // namespace
 
 int rsvld_gemm256_try(const rsvld_conv_desc* d, void* stream) {
+    rsvld_plan::Gemm256Plan pl;   // eligibility and form: rsvld_plan.h
+    {
+        const int rc = rsvld_plan::plan_gemm256(d, &pl);
+        if (rc != RSVLD_OK) return rc;
+    }
     const bool split = d->dtype == RSVLD_SPLIT, w2 = d->dtype == RSVLD_F16W2, w1 = d->dtype == RSVLD_F16W1;
-    const int seg = split ? 3 : w2 ? 2 : 1;          // K segments (RSVLD_F16W1: one, in the SEG = 4 kernels: the multi-segment family's outputs)
-    if (d->tune & RSVLD_TUNE_NO_GEMM256) return RSVLD_EUNSUPPORTED;   // A/B switch
-    if (w1 && d->out_f32 != 1) return RSVLD_EINVAL;
-    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad_t != 0 || d->pad_l != 0 || d->upsample) return RSVLD_EUNSUPPORTED;
-    if (d->x2 != nullptr || d->Cin2 != 0 || d->rowvec != nullptr || (d->out_f32 && seg == 1 && !w1)) return RSVLD_EUNSUPPORTED;
-    if (d->Cin % 32 != 0 || d->Cout % 8 != 0) return RSVLD_EUNSUPPORTED;
+    const int seg = split ? 3 : w2 ? 2 : 1;
     const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
-    if (d->H != d->Ho || d->W != d->Wo) return RSVLD_EUNSUPPORTED;
-    // eligibility is decided on the rows of ONE of the plan_div stacked units (batch-invariant plan)
-    const int64_t Mp = d->plan_div > 1 ? (M + d->plan_div - 1) / d->plan_div : M;
-    if (d->Cout < 256 || Mp < 4096) return RSVLD_EUNSUPPORTED;
-    const int64_t tiles = ((Mp + 255) / 256) * ((d->Cout + 255) / 256);
-    if (tiles < 128) return RSVLD_EUNSUPPORTED;   // one workgroup per CU; measured: from half the chip up it beats the 128x128 kernel
-    // 32-bit lane offsets inside a tile: 256 rows of the activation tensor (planes: 2 K per row) / of the weights (pair 2 K, triple 3 K)
-    if ((int64_t)256 * d->Cin * 2 * seg >= ((int64_t)1 << 32) || M >= ((int64_t)1 << 31)) return RSVLD_EUNSUPPORTED;
-    if (d->act == RSVLD_ACT_GEGLU && (d->Cout % 16 != 0 || d->residual != nullptr)) return RSVLD_EINVAL;
-    // RSVLD_SPLIT: the residual is the fp32 stream and goes with the fp32 output only (RSVLD_F16W2: the residual has the output's type)
-    if (split && d->out_f32 != 1 && d->residual != nullptr) return RSVLD_EINVAL;
-    if ((d->out_f32 == 2 && !split) || d->out_f32 < 0 || d->out_f32 > 2) return RSVLD_EINVAL;
     GemmArgs a;
     a.x = d->x; a.w = d->w; a.bias = d->bias; a.residual = d->residual; a.out = d->out;
     a.M = (int)M; a.N = d->Cout; a.K = d->Cin;
     a.N_out = d->act == RSVLD_ACT_GEGLU ? d->Cout / 2 : d->Cout;
     a.act = d->act; a.alpha = d->alpha; a.beta = d->beta;
-    // out_kind: 0 = 16-bit (T, or fp16 from the multi-segment forms), 1 = fp32, 2 = bf16 planes (RSVLD_SPLIT's native output)
-    a.out_kind = w1 ? 1 : seg == 1 ? 0 : d->out_f32 == 1 ? 1 : (split && d->out_f32 == 0) ? 2 : 0;
+    a.out_kind = pl.out_kind;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nmt = (unsigned)((M + 255) / 256), nnt = (unsigned)((d->Cout + 255) / 256);
     const dim3 grid1(nmt, nnt);
-    // the persistent form: 16-bit output, at least four K tiles (its K loop peels tile 0 and requests three tiles ahead)
-    const bool wide_res = (seg > 1 || w1) && a.out_kind == 1 && a.residual != nullptr && a.act == RSVLD_ACT_NONE;   // fp32 out + fp32 residual
-    if (!(d->tune & RSVLD_TUNE_GEMM_ONE_TILE) && (a.out_kind == 0 || wide_res) && seg * d->Cin >= 128) {
+    // The launch table: every gemm_go<gemm256_kernel<...>> is named below and nowhere else.  The persistent form first, where the plan
+    // allows it, a device tells its CU count and the family has that instantiation; else one tile per workgroup.
+    if (pl.form == rsvld_plan::GEMM256_PERSISTENT) {
         static const int n_cu = [] {
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
@@ -1116,7 +1104,7 @@ int rsvld_gemm256_try(const rsvld_conv_desc* d, void* stream) {
             const dim3 pgrid((unsigned)min((int64_t)nmt * nnt, (int64_t)n_cu));
             const int pv = (a.act == RSVLD_ACT_GEGLU ? 2 : a.act == RSVLD_ACT_SILU ? 1 : 0) | (a.alpha == 1.0f ? 4 : 0) | (a.residual != nullptr ? 8 : 0);
             const bool h = d->dtype == RSVLD_F16;
-            if (wide_res) {
+            if (pl.wide_res) {
                 return split ? gemm_go<gemm256_kernel<bf16, 3, true, 0, 2>, G_SMEM_P>(pgrid, s, a)
                        : w1  ? gemm_go<gemm256_kernel<f16, 4, true, 0, 2>, G_SMEM_P>(pgrid, s, a)
                              : gemm_go<gemm256_kernel<f16, 2, true, 0, 2>, G_SMEM_P>(pgrid, s, a);

@@ -7,6 +7,7 @@
 // HBM-bound: every pass moves 16 B (fp32 input: 32 B) per lane and row.  Statistics: per-block partials merged in fp64 in a fixed
 // order (deterministic, no atomics); an fp32 input's partials are fp64 themselves, from pivoted fp32 sums: see "pivot sums" below.
 #include "rsvld_common.h"
+#include "rsvld_plan.h"
 #include <cstdint>
 #include <type_traits>
 
@@ -85,7 +86,7 @@ struct GnGeom {
     int rif;   // rows in flight
     __host__ __device__ GnGeom(int C1, int C2) {
         C = C1 + C2, C8 = C >> 3, C1_8 = C1 >> 3;
-        TPR = C8 < 256 ? C8 : 256;
+        TPR = rsvld_plan::gn_threads_per_row(C8);
         rif = 256 / TPR;
     }
     // gn_partial_kernel's [rif][C][2], and the pivots [C] where it has them
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
 // written (APPLY) or turned into the per-channel (scale, shift) rows of the fused conv prologue (!APPLY).
 // Needs 8 | C/groups (a vector never straddles groups) and, for [x | x2], groups that do not straddle the sources.
 // ---------------------------------------------------------------------------------------
-constexpr int GN_SMALL_MAXV = 32;
+using rsvld_plan::GN_SMALL_MAXV;
 
 template <typename T, bool APPLY>
 __global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x1, const T* __restrict__ x2, T* __restrict__ y,
@@ -694,39 +695,18 @@ __global__ void gn_ab_from_stats_kernel(const float* __restrict__ mean_var, cons
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-bool gn_small_ok(int B, int HW, int C1, int C2, int groups) {
-    const int C = C1 + C2, gs = C / groups;
-    if (gs % 8) return false;
-    const int gs8 = gs / 8;
-    if (gs8 > 256 || (gs8 & (gs8 - 1))) return false;
-    if (C2 > 0 && C1 % gs) return false;
-    if ((int64_t)HW * gs8 > (int64_t)256 * GN_SMALL_MAXV) return false;
-    (void)B;                   // (the choice must not depend on the batch: batch-invariant results)
-    return groups >= 32;       // enough workgroups per image to be worth one launch
-}
+// which route, and the row chunks of the partials route: rsvld_plan.h
+using rsvld_plan::GnPlan;
+using rsvld_plan::gn_plan;
+using rsvld_plan::gn_small_route;
+using rsvld_plan::gn_dims_ok;
+using rsvld_plan::gn_groups_ok;
 
-struct GnPlan {
-    int nchunks, rows_per_chunk;
-};
-GnPlan gn_plan(int B, int HW) {
-    (void)B;   // the chunking fixes the order of the partial sums: it depends on the image size only, so an image's
-               // statistics are bit-identical whatever the batch around it
-    const int max_chunks = 512;
-    int rpc = (HW + max_chunks - 1) / max_chunks;
-    if (rpc < 64) rpc = 64;
-    GnPlan p;
-    p.rows_per_chunk = rpc;
-    p.nchunks = (HW + rpc - 1) / rpc;
-    return p;
-}
-
-// operand checks of the entry points: the sizes of [x (C1) | x2 (C2)], the same with its pointers, and the groups over C1 + C2
-bool gn_dims_ok(int B, int HW, int C1, int C2) { return B > 0 && HW > 0 && C1 > 0 && C1 % 8 == 0 && C2 >= 0 && C2 % 8 == 0; }
+// operand checks of the entry points: the sizes of [x (C1) | x2 (C2)] with its pointers (sizes and groups alone: rsvld_plan.h)
 bool gn_x_ok(const void* x, const void* x2, int B, int HW, int C1, int C2) {
     return x != nullptr && gn_dims_ok(B, HW, C1, C2) && (C2 > 0) == (x2 != nullptr);
 }
 bool gn_align8(const void* p) { return ((uintptr_t)p & 7) == 0; }   // fp64 partials
-bool gn_groups_ok(int C, int groups) { return groups > 0 && C % groups == 0 && C <= 8192 && groups <= 256; }
 bool gn_mod_ok(const void* mod_scale1p, const void* mod_shift, int mod_stride, int align) {
     return (mod_scale1p != nullptr) == (mod_shift != nullptr) && mod_stride >= 0 && mod_stride % align == 0;
 }
@@ -752,7 +732,7 @@ bool launch_partials(const void* x, const void* x2, typename In::part* part, int
 template <typename In>
 int gn_stats_impl(const void* x, const void* x2, float* stats, int B, int HW, int C1, int C2, int groups, void* ws,
                   hipStream_t s) {
-    const GnPlan pl = gn_plan(B, HW);
+    const GnPlan pl = gn_plan(HW);
     typedef typename In::part P;
     if (!launch_partials<In>(x, x2, (P*)ws, B, HW, C1, C2, groups, pl, s)) return RSVLD_ELAUNCH;
     const int total = B * groups;
@@ -765,7 +745,7 @@ int gn_stats_impl(const void* x, const void* x2, float* stats, int B, int HW, in
 template <typename In>
 int gn_scale_shift_impl(const void* x, const void* x2, const float* gamma, const float* beta, float* scale_shift, int B, int HW,
                         int C1, int C2, int groups, float eps, void* ws, hipStream_t s) {
-    const GnPlan pl = gn_plan(B, HW);
+    const GnPlan pl = gn_plan(HW);
     typedef typename In::part P;
     if (!launch_partials<In>(x, x2, (P*)ws, B, HW, C1, C2, groups, pl, s)) return RSVLD_ELAUNCH;
     hipLaunchKernelGGL((gn_ab_kernel<false, P>), dim3(groups, B), dim3(256), 0, s, (const P*)ws, pl.nchunks, C1 + C2, (const P*)nullptr, 0, 0,
@@ -836,10 +816,14 @@ void with_out_form(int form, F f) {
 
 }  // namespace
 
+extern "C" int rsvld_plan_groupnorm(int dtype, int B, int HW, int C1, int C2, int groups, rsvld_groupnorm_plan* plan) {
+    return plan == nullptr ? RSVLD_EINVAL : rsvld_plan::plan_groupnorm(dtype, B, HW, C1, C2, groups, plan);
+}
+
 extern "C" int64_t rsvld_groupnorm_ws_bytes(int B, int HW, int C, int groups) {
     (void)C;
     if (B <= 0 || HW <= 0 || groups <= 0) return 0;
-    const GnPlan pl = gn_plan(B, HW);
+    const GnPlan pl = gn_plan(HW);
     // room for fp64 partials (an fp32 input's; a 16-bit input's are fp32 and fill half of it), then the final fp32 stats
     return (int64_t)B * pl.nchunks * groups * 2 * (int64_t)sizeof(double) + (int64_t)B * groups * 2 * (int64_t)sizeof(float);
 }
@@ -871,13 +855,13 @@ extern "C" int rsvld_groupnorm_nhwc(const void* x, const void* x2, void* y, cons
                                     const void* mod_scale1p, const void* mod_shift, int mod_stride, int B, int HW, int C1,
                                     int C2, int groups, float eps, int silu, int dtype, void* ws, void* stream) {
     if (!ws || !gn_dims_ok(B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
-    if (mod_scale1p == nullptr && mod_shift == nullptr && y && gn_x_ok(x, x2, B, HW, C1, C2) && B <= 65535 &&
-        gn_small_ok(B, HW, C1, C2, groups) && (dtype == RSVLD_F16 || dtype == RSVLD_BF16)) {
+    if (mod_scale1p == nullptr && mod_shift == nullptr && y && gn_x_ok(x, x2, B, HW, C1, C2) &&
+        gn_small_route(dtype, B, HW, C1, C2, groups)) {
         hipStream_t s = (hipStream_t)stream;
         if (dtype == RSVLD_F16) return gn_small_impl<f16, true>(x, x2, y, nullptr, gamma, beta, B, HW, C1, C2, groups, eps, silu, s);
         return gn_small_impl<bf16, true>(x, x2, y, nullptr, gamma, beta, B, HW, C1, C2, groups, eps, silu, s);
     }
-    const GnPlan pl = gn_plan(B, HW);
+    const GnPlan pl = gn_plan(HW);
     float* stats = (float*)((double*)ws + (int64_t)B * pl.nchunks * groups * 2);
     int rc = rsvld_groupnorm_stats(x, x2, stats, B, HW, C1, C2, groups, dtype, ws, stream);
     if (rc != RSVLD_OK) return rc;
@@ -891,7 +875,7 @@ extern "C" int rsvld_groupnorm_scale_shift(const void* x, const void* x2, const 
     if (!ws || !scale_shift || !gn_x_ok(x, x2, B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
     if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (B <= 65535 && gn_small_ok(B, HW, C1, C2, groups)) {
+    if (gn_small_route(dtype, B, HW, C1, C2, groups)) {
         if (dtype == RSVLD_F16) return gn_small_impl<f16, false>(x, x2, nullptr, scale_shift, gamma, beta, B, HW, C1, C2, groups, eps, 0, s);
         return gn_small_impl<bf16, false>(x, x2, nullptr, scale_shift, gamma, beta, B, HW, C1, C2, groups, eps, 0, s);
     }

@@ -1,0 +1,276 @@
+// rsvld_plan.h — which kernel runs for a layer, decided in ONE place: the planners of conv_igemm.hip (implicit GEMM), gemm.hip (gemm256),
+// conv_halo.hip and norm.hip (GroupNorm).  Plain host C++: integer arithmetic on a descriptor, no HIP call, no device query, no pointer
+// dereference beyond the descriptor (its pointers are compared with NULL only).  Each entry point validates, plans here and launches
+// the plan through a flat table of instantiations; rsvld_plan_conv / rsvld_plan_groupnorm (include/rsvld_hip.h) hand the same plans to the
+// caller, so that nothing outside this header restates a threshold.
+#pragma once
+#include <stdint.h>
+#include "rsvld_hip.h"
+
+namespace rsvld_plan {
+
+// rows (or batch rows) of ONE of the plan_div stacked units: every grid-size test below uses it, so the plan, and with it the order of every
+// accumulation, does not depend on how many units share the launch
+inline int64_t plan_unit(int64_t n, int plan_div) { return plan_div > 1 ? (n + plan_div - 1) / plan_div : n; }
+
+// K segments per tap of the multi-segment operand forms (RSVLD_F16W1: the pair kernels over ONE segment)
+struct Forms {
+    bool split, w1, w2, hq;
+};
+inline Forms forms_of(int dtype) { return {dtype == RSVLD_SPLIT, dtype == RSVLD_F16W1, dtype == RSVLD_F16W2, dtype == RSVLD_F16Q8}; }
+
+// ---------------------------------------------------------------------------------------
+// implicit GEMM (conv_igemm.hip): one instantiation of conv_igemm_kernel
+// ---------------------------------------------------------------------------------------
+struct IgemmPlan {
+    int bm, bn, stages, ks;   // tile rows x columns, LDS ring depth, K groups per workgroup
+    int reg_staging;          // 0: operands staged by LDS-DMA, 1: through registers (RSVLD_TUNE_REG_STAGING)
+};
+
+// Tile choice.  Cout <= 32: 256x32.  Cout <= 64: 128x64 (48 KiB LDS -> 3 workgroups per CU: these layers
+// have few K-steps per tile, so co-resident workgroups hide each other's prologue / epilogue).  Otherwise
+// 128x128, except when that grid would leave CUs idle (< 256 workgroups): then 64x128 doubles the grid.
+// M_plan: the output rows of one planning unit; nk: K steps of 64 channels.
+inline IgemmPlan plan_igemm(int64_t M_plan, int Cout, int nk, int tune) {
+    const bool glds = !(tune & RSVLD_TUNE_REG_STAGING);
+    const int reg = glds ? 0 : 1;
+    if (Cout <= 32) return {256, 32, 2, 1, reg};
+    const int ov = tune & RSVLD_TUNE_TILE_MASK;
+    const int st = glds ? ((tune >> RSVLD_TUNE_STAGES_SHIFT) & 7) : 2;   // the register-staged kernels are double-buffered only
+    const bool ksplit = !(tune & RSVLD_TUNE_NO_KSPLIT);
+    if (Cout <= 64) {
+        if (ov == 1) return {256, 64, 2, 1, reg};
+        // measured: 3 WGs/CU x 1 tile in flight (48 KiB) beats 2 WGs/CU x 2 tiles (72 KiB)
+        return {128, 64, (st == 3 || st == 4) ? st : 2, 1, reg};
+    }
+    const int64_t wg128 = ((M_plan + 127) / 128) * ((Cout + 127) / 128);
+    const int64_t wg64x128 = ((M_plan + 63) / 64) * ((Cout + 127) / 128);
+    // small-M linears (Stage-2 transformer blocks at 16x16 / 32x32 tokens): even 64x128 leaves most CUs idle and
+    // the K loop is a latency-bound weight stream.  64x64 tiles double the grid again; 4 x 16 KiB stages keep
+    // 3 tiles in flight per workgroup at 2 workgroups per CU.
+    if (glds && ov == 0 && wg64x128 < 256) {
+        const int64_t wg64 = ((M_plan + 63) / 64) * ((Cout + 63) / 64);
+        return {64, 64, 4, (ksplit && st == 0 && wg64 <= 256 && nk >= 16) ? 2 : 1, 0};
+    }
+    if (ov == 4 || (ov == 0 && wg128 < 256)) {
+        if (glds) {
+            // one 64x128 workgroup per CU at most and a long K loop: two K groups (8 waves) per tile
+            if (ksplit && st == 0 && wg64x128 <= 256 && nk >= 16) return {64, 128, 3, 2, 0};
+            if (st == 3 || st == 0) return {64, 128, 3, 1, 0};   // 72 KiB: 2 WGs / CU
+            if (st == 4) return {64, 128, 4, 1, 0};
+        }
+        return {64, 128, 2, 1, reg};
+    }
+    // measured: the 96 KiB ring drops to 1 WG/CU and loses 30 % to 2 x 64 KiB double buffers
+    return {128, 128, (st == 3 || st == 4) ? st : 2, 1, reg};
+}
+
+// ---------------------------------------------------------------------------------------
+// gemm256 (gemm.hip): large 1x1 / stride-1 / single-source layers
+// ---------------------------------------------------------------------------------------
+enum { GEMM256_NONE = 0, GEMM256_PERSISTENT = 1, GEMM256_ONE_TILE = 2 };
+struct Gemm256Plan {
+    int form;        // GEMM256_PERSISTENT: eligible for the persistent kernel (the launch falls back to one tile per workgroup where that
+                     // family has no persistent instantiation, or no device tells a CU count); GEMM256_ONE_TILE: one tile per workgroup
+    int out_kind;    // 0 = 16-bit (T, or fp16 from the multi-segment forms), 1 = fp32, 2 = bf16 planes (RSVLD_SPLIT's native output)
+    bool wide_res;   // fp32 out + fp32 residual, no activation: the persistent form of the multi-segment families
+};
+
+// RSVLD_OK: gemm256 takes the layer (*p filled); RSVLD_EUNSUPPORTED: the shape stays on the implicit-GEMM kernel; RSVLD_EINVAL
+inline int plan_gemm256(const rsvld_conv_desc* d, Gemm256Plan* p) {
+    const Forms f = forms_of(d->dtype);
+    const int seg = f.split ? 3 : f.w2 ? 2 : 1;      // K segments (RSVLD_F16W1: one, in the SEG = 4 kernels: the multi-segment family's outputs)
+    if (d->tune & RSVLD_TUNE_NO_GEMM256) return RSVLD_EUNSUPPORTED;   // A/B switch
+    if (f.w1 && d->out_f32 != 1) return RSVLD_EINVAL;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad_t != 0 || d->pad_l != 0 || d->upsample) return RSVLD_EUNSUPPORTED;
+    if (d->x2 != nullptr || d->Cin2 != 0 || d->rowvec != nullptr || (d->out_f32 && seg == 1 && !f.w1)) return RSVLD_EUNSUPPORTED;
+    if (d->Cin % 32 != 0 || d->Cout % 8 != 0) return RSVLD_EUNSUPPORTED;
+    const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
+    if (d->H != d->Ho || d->W != d->Wo) return RSVLD_EUNSUPPORTED;
+    const int64_t Mp = plan_unit(M, d->plan_div);
+    if (d->Cout < 256 || Mp < 4096) return RSVLD_EUNSUPPORTED;
+    const int64_t tiles = ((Mp + 255) / 256) * ((d->Cout + 255) / 256);
+    if (tiles < 128) return RSVLD_EUNSUPPORTED;   // one workgroup per CU; measured: from half the chip up it beats the 128x128 kernel
+    // 32-bit lane offsets inside a tile: 256 rows of the activation tensor (planes: 2 K per row) / of the weights (pair 2 K, triple 3 K)
+    if ((int64_t)256 * d->Cin * 2 * seg >= ((int64_t)1 << 32) || M >= ((int64_t)1 << 31)) return RSVLD_EUNSUPPORTED;
+    if (d->act == RSVLD_ACT_GEGLU && (d->Cout % 16 != 0 || d->residual != nullptr)) return RSVLD_EINVAL;
+    // RSVLD_SPLIT: the residual is the fp32 stream and goes with the fp32 output only (RSVLD_F16W2: the residual has the output's type)
+    if (f.split && d->out_f32 != 1 && d->residual != nullptr) return RSVLD_EINVAL;
+    if ((d->out_f32 == 2 && !f.split) || d->out_f32 < 0 || d->out_f32 > 2) return RSVLD_EINVAL;
+    p->out_kind = f.w1 ? 1 : seg == 1 ? 0 : d->out_f32 == 1 ? 1 : (f.split && d->out_f32 == 0) ? 2 : 0;
+    p->wide_res = (seg > 1 || f.w1) && p->out_kind == 1 && d->residual != nullptr && d->act == RSVLD_ACT_NONE;
+    // the persistent form: 16-bit output, at least four K tiles (its K loop peels tile 0 and requests three tiles ahead)
+    const bool persistent = !(d->tune & RSVLD_TUNE_GEMM_ONE_TILE) && (p->out_kind == 0 || p->wide_res) && seg * d->Cin >= 128;
+    p->form = persistent ? GEMM256_PERSISTENT : GEMM256_ONE_TILE;
+    return RSVLD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// rsvld_conv2d_nhwc: validate -> gemm256 -> implicit GEMM
+// ---------------------------------------------------------------------------------------
+// K segments the implicit-GEMM kernel walks per tap: RSVLD_SPLIT 3, RSVLD_F16W2 / RSVLD_F16W1 2 (the latter over ONE segment of channels)
+inline int igemm_seg(const Forms& f) { return f.split ? 3 : (f.w2 || f.w1) ? 2 : 1; }
+
+// the operand checks of rsvld_conv2d_nhwc, in its order
+inline int validate_conv(const rsvld_conv_desc* d) {
+    if (d == nullptr || d->x == nullptr || d->w == nullptr || d->out == nullptr) return RSVLD_EINVAL;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0) return RSVLD_EINVAL;
+    if (d->Cin <= 0 || d->Cin % 8 != 0 || d->Cout <= 0 || d->Cout % 8 != 0) return RSVLD_EINVAL;
+    if (d->Cin2 < 0 || d->Cin2 % 8 != 0 || ((d->Cin2 > 0) != (d->x2 != nullptr))) return RSVLD_EINVAL;
+    if (d->KH <= 0 || d->KW <= 0 || d->stride <= 0) return RSVLD_EINVAL;
+    // RSVLD_F16W1: the weight-pair kernels (SEG = 2: fp16 in, fp32 out + fp32 residual) over ONE K segment -- their second-segment wrap of the
+    // channel index never triggers when Ctot = Cseg, and the weight rows are K long
+    const Forms f = forms_of(d->dtype);
+    const int seg = igemm_seg(f);
+    if (d->dtype != RSVLD_F16 && d->dtype != RSVLD_BF16 && seg == 1) return RSVLD_EINVAL;
+    if (f.w1 && (d->out_f32 != 1 || d->KH != 1 || d->KW != 1)) return RSVLD_EINVAL;
+    if (d->out_f32 < 0 || d->out_f32 > 2 || (d->out_f32 == 2 && !f.split)) return RSVLD_EINVAL;
+    if (seg == 1 && d->out_f32 && (d->Cout > 32 || d->act == RSVLD_ACT_GEGLU || d->residual != nullptr)) return RSVLD_EUNSUPPORTED;
+    if (f.split && d->out_f32 != 1 && d->residual != nullptr) return RSVLD_EINVAL;   // planes / fp16 out of RSVLD_SPLIT: no residual (the stream stays fp32)
+    if (d->act == RSVLD_ACT_GEGLU && (d->Cout % 16 != 0 || d->residual != nullptr)) return RSVLD_EINVAL;
+    if ((int64_t)d->B * d->Ho * d->Wo >= (int64_t)1 << 31) return RSVLD_EUNSUPPORTED;
+    if ((int64_t)d->B * d->H * d->W >= (int64_t)1 << 31) return RSVLD_EUNSUPPORTED;
+    // every output pixel must read inside the (optionally up-sampled) padded input: shape sanity
+    const int Hin = d->upsample ? 2 * d->H : d->H, Win = d->upsample ? 2 * d->W : d->W;
+    if ((d->Ho - 1) * d->stride - d->pad_t >= Hin || (d->Wo - 1) * d->stride - d->pad_l >= Win) return RSVLD_EINVAL;
+    return RSVLD_OK;
+}
+
+// K steps of the implicit-GEMM kernel: 16-byte pieces of 8 channels per tap and segment, 8 pieces per step
+inline int igemm_nk(const rsvld_conv_desc* d) {
+    const Forms f = forms_of(d->dtype);
+    const int Ctot8 = (f.w1 ? 1 : igemm_seg(f)) * ((d->Cin + d->Cin2) / 8);
+    return (d->KH * d->KW * Ctot8 + 7) / 8;
+}
+inline IgemmPlan plan_igemm(const rsvld_conv_desc* d) {   // of a descriptor validate_conv accepted
+    const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
+    return plan_igemm(plan_unit(M, d->plan_div), d->Cout, igemm_nk(d), d->tune);
+}
+
+// ---------------------------------------------------------------------------------------
+// halo convolution (conv_halo.hip)
+// ---------------------------------------------------------------------------------------
+constexpr int HALO_TH = 8, HALO_TW = 32;   // output pixels of a tile; the 8-wave kernel stacks two tiles (16 x 32)
+struct HaloPlan {
+    int bn, waves;       // output channels per workgroup; 4 waves on an 8 x 32 tile or 8 waves on 16 x 32
+    int64_t wgs;         // workgroups of ONE planning unit, on 8-row tiles also where the 8-wave kernel runs
+    int stat_tiles;      // 8 x 32 tiles per image: the rows of the epilogue's statistics partials
+};
+
+// 3x3 / stride 1 / pad 1, every source a multiple of 64 channels
+inline bool halo_supported(const rsvld_conv_desc* d) {
+    if (d == nullptr) return false;
+    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1) return false;
+    const int up = d->upsample ? 2 : 1;
+    if (d->Ho != up * d->H || d->Wo != up * d->W) return false;
+    if (d->Cin % 64 != 0 || d->Cin2 % 64 != 0) return false;
+    if (d->act == RSVLD_ACT_GEGLU) return false;
+    if (d->out_f32 && d->Cout > 32 && d->dtype != RSVLD_SPLIT && d->dtype != RSVLD_F16W2 && d->dtype != RSVLD_F16Q8) return false;
+    // RSVLD_F16Q8: the 128-wide kernels only; fp32 out; ONE source (the GroupNorm apply pass that writes q8 rows has already concatenated)
+    if (d->dtype == RSVLD_F16Q8 && (d->Cout <= 64 || !d->out_f32 || d->upsample || d->Cin2 != 0)) return false;
+    if (d->Wo < 16 || d->Ho < 4) return false;   // tiny maps: the 8x32 tile would be mostly padding
+    return true;
+}
+
+// K segments per tap the halo kernels walk (RSVLD_F16Q8: SEG = 5, two fp16 segments' worth of weight row)
+inline int halo_seg(const Forms& f) { return f.split ? 3 : f.w2 ? 2 : f.hq ? 5 : 1; }
+
+// logical K' channels per tap (16-bit elements of a weight row)
+inline int halo_ctot(const rsvld_conv_desc* d) {
+    const Forms f = forms_of(d->dtype);
+    return (f.hq ? 2 : halo_seg(f)) * (d->Cin + d->Cin2);
+}
+
+inline bool plan_halo(const rsvld_conv_desc* d, HaloPlan* p) {
+    if (!halo_supported(d)) return false;
+    const int64_t B_plan = plan_unit(d->B, d->plan_div);
+    const int tiles_x = (d->Wo + HALO_TW - 1) / HALO_TW;
+    p->stat_tiles = tiles_x * ((d->Ho + HALO_TH - 1) / HALO_TH);
+    if (d->Cout <= 64) {
+        p->bn = 64, p->waves = 4;
+    } else {
+        // 16x32-pixel tiles (one 8-wave workgroup per CU) once that grid still covers most of the chip
+        const int64_t wg16 = (int64_t)tiles_x * ((d->Ho + 2 * HALO_TH - 1) / (2 * HALO_TH)) * B_plan * ((d->Cout + 127) / 128);
+        // measured (tools/bench_halo.py, one box): +3..13 % from 192 channels of K up, -3 % at 128 (longer pipeline fill)
+        const bool use8 = (d->tune & RSVLD_TUNE_HALO_NW8) ? true : (d->tune & RSVLD_TUNE_HALO_NW4) ? false : (wg16 >= 192 && halo_ctot(d) >= 192);
+        p->bn = 128, p->waves = use8 ? 8 : 4;
+    }
+    p->wgs = B_plan * p->stat_tiles * ((d->Cout + p->bn - 1) / p->bn);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------
+// the whole plan of a convolution descriptor (rsvld_plan_conv)
+// ---------------------------------------------------------------------------------------
+inline int plan_conv(const rsvld_conv_desc* d, rsvld_conv_plan* out) {
+    *out = rsvld_conv_plan{};
+    HaloPlan h;
+    if (plan_halo(d, &h)) out->halo_wgs = h.wgs, out->halo_bn = h.bn, out->halo_waves = h.waves, out->halo_stat_tiles = h.stat_tiles;
+    int rc = validate_conv(d);
+    if (rc != RSVLD_OK) return rc;
+    Gemm256Plan g;
+    rc = plan_gemm256(d, &g);
+    if (rc == RSVLD_OK) {
+        out->gemm256 = g.form;
+        return RSVLD_OK;
+    }
+    if (rc != RSVLD_EUNSUPPORTED) return rc;
+    const IgemmPlan p = plan_igemm(d);
+    out->bm = p.bm, out->bn = p.bn, out->stages = p.stages, out->ks = p.ks, out->reg_staging = p.reg_staging;
+    return RSVLD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// GroupNorm (norm.hip)
+// ---------------------------------------------------------------------------------------
+constexpr int GN_SMALL_MAXV = 32;   // sixteen-byte vectors a thread of gn_small_kernel holds
+
+// threads per row of gn_partial_kernel over C8 eight-channel vectors; 256 / that = its rows in flight
+constexpr int gn_threads_per_row(int C8) { return C8 < 256 ? C8 : 256; }
+
+// one workgroup per (image, group) with the group's slab in registers: 8 | C/groups (a vector never straddles groups), groups that
+// do not straddle the two sources, at most GN_SMALL_MAXV vectors per thread
+inline bool gn_small_ok(int HW, int C1, int C2, int groups) {
+    const int C = C1 + C2, gs = C / groups;
+    if (gs % 8) return false;
+    const int gs8 = gs / 8;
+    if (gs8 > 256 || (gs8 & (gs8 - 1))) return false;
+    if (C2 > 0 && C1 % gs) return false;
+    if ((int64_t)HW * gs8 > (int64_t)256 * GN_SMALL_MAXV) return false;
+    // (the choice must not depend on the batch: batch-invariant results)
+    return groups >= 32;       // enough workgroups per image to be worth one launch
+}
+
+struct GnPlan {
+    int nchunks, rows_per_chunk;
+};
+// the row chunks of the partials route.  The chunking fixes the order of the partial sums: it depends on the image size only, so an
+// image's statistics are bit-identical whatever the batch around it
+inline GnPlan gn_plan(int HW) {
+    const int max_chunks = 512;
+    int rpc = (HW + max_chunks - 1) / max_chunks;
+    if (rpc < 64) rpc = 64;
+    return {(HW + rpc - 1) / rpc, rpc};
+}
+
+// operand checks of the GroupNorm entry points: the sizes of [x (C1) | x2 (C2)] and the groups over C1 + C2
+inline bool gn_dims_ok(int B, int HW, int C1, int C2) { return B > 0 && HW > 0 && C1 > 0 && C1 % 8 == 0 && C2 >= 0 && C2 % 8 == 0; }
+inline bool gn_groups_ok(int C, int groups) { return groups > 0 && C % groups == 0 && C <= 8192 && groups <= 256; }
+
+// the one-workgroup route of rsvld_groupnorm_nhwc / rsvld_groupnorm_scale_shift: 16-bit inputs, a grid of (groups, B)
+inline bool gn_small_route(int dtype, int B, int HW, int C1, int C2, int groups) {
+    return (dtype == RSVLD_F16 || dtype == RSVLD_BF16) && B <= 65535 && gn_small_ok(HW, C1, C2, groups);
+}
+
+inline int plan_groupnorm(int dtype, int B, int HW, int C1, int C2, int groups, rsvld_groupnorm_plan* out) {
+    *out = rsvld_groupnorm_plan{};
+    if (!gn_dims_ok(B, HW, C1, C2) || !gn_groups_ok(C1 + C2, groups)) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16 && dtype != RSVLD_F32) return RSVLD_EINVAL;
+    const GnPlan pl = gn_plan(HW);
+    out->small = gn_small_route(dtype, B, HW, C1, C2, groups) ? 1 : 0;
+    out->nchunks = pl.nchunks, out->rows_per_chunk = pl.rows_per_chunk;
+    out->rows_in_flight = 256 / gn_threads_per_row((C1 + C2) / 8);
+    return RSVLD_OK;
+}
+
+}  // namespace rsvld_plan

@@ -595,9 +595,9 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
                    upsample=upsample, act=act, alpha=alpha, beta=beta, x=x, x2=x2, w=wt, rowvec=rowvec, residual=residual, out=out)
     sfx = "_w1" if w1res else "_w2" if w2 else ""
     lib = L.load()
-    halo = ctx.use_halo and bool(lib.rsvld_conv3x3_halo_supported(C.byref(d)))
-    if halo:
-        halo = _halo_wgs(B, Ho, Wo, pc.cout_p, ctx.plan_div) >= ctx.halo_min_wgs and not (upsample and norm is not None)
+    plan, rc = _conv_plan(lib, d)
+    # policy: the halo kernel where the library has one for the layer and its grid fills the chip; no fused norm before an Upsample conv
+    halo = ctx.use_halo and plan.halo_bn != 0 and plan.halo_wgs >= ctx.halo_min_wgs and not (upsample and norm is not None)
     if norm is not None and not halo:   # unfused: normalise into a (single) tensor, then convolve it
         gamma, nbeta, groups, eps, silu = norm
         xn = group_norm(x, gamma, nbeta, groups, eps, x2=x2, silu=silu)
@@ -619,22 +619,11 @@ def conv2d(x, pc, *, x2=None, stride=1, pad=None, upsample=False, rowvec=None, r
                         lambda: L.check(lib.rsvld_groupnorm_scale_shift(_ptr(x), _ptr(x2), _ptr(gamma), _ptr(nbeta), _ptr(ab), B,
                                                                         H * W, Cin, Cin2, groups, eps, _dt(x), _ptr(ws), _stream()),
                                         "rsvld_groupnorm_scale_shift"))
-        name = ("conv_halo_64" if pc.cout_p <= 64 else "conv_halo_128") + sfx
-        _halo_launch(name + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, d, out, ab, silu,
-                     stats and (w2 or not out_f32))
+        _halo_launch(f"conv_halo_{plan.halo_bn}" + sfx + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, d, out, ab, silu,
+                     plan.halo_stat_tiles if stats and (w2 or not out_f32) else 0)
         return out
-    M = B * Ho * Wo
-    Mp = -(-M // ctx.plan_div)            # output rows of one planning unit: every plan decision below uses Mp
-    if (w2 or not out_f32) and _gemm256_label(d, Mp, 4 if w2 else 2):
-        variant = "gemm_256x256"
-    elif pc.cout_p <= 32:
-        variant = "conv_igemm_256x32"
-    elif pc.cout_p <= 64:
-        variant = "conv_igemm_128x64"
-    else:   # mirrors dispatch_conv2 in csrc/conv_igemm.hip
-        wg128 = ((Mp + 127) // 128) * ((pc.cout_p + 127) // 128)
-        wg64 = ((Mp + 63) // 64) * ((pc.cout_p + 127) // 128)
-        variant = "conv_igemm_64x64" if wg64 < 256 else ("conv_igemm_64x128" if wg128 < 256 else "conv_igemm_128x128")
+    L.check(rc, "rsvld_plan_conv")
+    variant = "gemm_256x256" if plan.gemm256 else f"conv_igemm_{plan.bm}x{plan.bn}"   # the kernel that runs, tune bits included
     _launch(variant + sfx + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample), flops, nbytes, lambda: L.check(lib.rsvld_conv2d_nhwc(C.byref(d), _stream()), "rsvld_conv2d_nhwc"))
     if out_f32 and out.dim() == 4:
         out._nhwc = True     # an fp32 4-d tensor is otherwise taken for NCHW by the VAE's input adapter
@@ -714,38 +703,27 @@ def _conv_desc(shape, Cin2, pc, geo, dtype, out_f32, *, stride=1, upsample=False
         plan_div=ctx.plan_div if plan_div is None else plan_div, tune=ctx.tune if tune is None else tune)
 
 
-def _halo_tiles(Ho, Wo):
-    """8 x 32-pixel output tiles of conv_halo.hip per image: also the rows of its epilogue statistics."""
-    return ((Ho + 7) // 8) * ((Wo + 31) // 32)
+def _conv_plan(lib, d):
+    """rsvld_plan_conv (include/rsvld_hip.h; ``lib``: L.load()) of descriptor ``d`` -> ``(L.ConvPlan, rc)``: the library's own launch plan, asked once per
+    layer instead of restated here.  ``halo_bn`` (0: no halo kernel for this layer), ``halo_wgs`` (its workgroups per planning unit, for
+    ``halo_min_wgs`` / ``split_halo_min_wgs``) and ``halo_stat_tiles`` (rows of its epilogue statistics) hold whatever ``rc`` says;
+    ``rc``: what rsvld_conv2d_nhwc would return before launching, and with 0 ``gemm256`` or the implicit-GEMM tile ``bm`` x ``bn``.
+    Host arithmetic only: absent tensors may be null pointers where only the halo fields are read."""
+    plan = L.ConvPlan()
+    return plan, lib.rsvld_plan_conv(d, plan)     # (ctypes passes a structure by reference where the argument type is a pointer to it)
 
 
-def _halo_wgs(B, Ho, Wo, cout_p, plan_div):
-    """Workgroups conv_halo.hip would run for ONE planning unit (``-(-B // plan_div)`` batch rows): pixel tiles x blocks of 64
-    (Cout <= 64) or 128 output channels.  Compared with ``halo_min_wgs`` / ``split_halo_min_wgs`` (LaunchContext)."""
-    bn = 64 if cout_p <= 64 else 128
-    return -(-B // plan_div) * _halo_tiles(Ho, Wo) * ((cout_p + bn - 1) // bn)
-
-
-def _halo_launch(name, flops, nbytes, d, out, ab, silu, stats):
-    """rsvld_conv3x3_halo_nhwc on descriptor ``d`` (``ab`` / ``silu``: the fused GroupNorm of its input, or None / 0).  ``stats``: the
-    epilogue writes per-tile per-channel fp64 (sum, sumsq) of the output, attached to ``out`` as ``_gn_part`` for the consumer's ``norm=``."""
+def _halo_launch(name, flops, nbytes, d, out, ab, silu, ntiles):
+    """rsvld_conv3x3_halo_nhwc on descriptor ``d`` (``ab`` / ``silu``: the fused GroupNorm of its input, or None / 0).  ``ntiles``: 0, or
+    the plan's ``halo_stat_tiles``: the epilogue writes per-tile per-channel fp64 (sum, sumsq) of the output, attached to ``out`` as
+    ``_gn_part`` for the consumer's ``norm=``."""
     part_out = None
-    if stats:
-        ntiles = _halo_tiles(d.Ho, d.Wo)
+    if ntiles:
         part_out = torch.empty((d.B, ntiles, d.Cout, 2), device=out.device, dtype=torch.float64)
     _launch(name, flops, nbytes, lambda: L.check(L.load().rsvld_conv3x3_halo_nhwc(C.byref(d), _ptr(ab), int(silu), _ptr(part_out), _stream()),
                                                  "rsvld_conv3x3_halo_nhwc"))
     if part_out is not None:
         out._gn_part = (part_out, ntiles)
-
-
-def _gemm256_label(d, Mp, wbytes):
-    """Profiler label only: would rsvld_gemm256_try (csrc/gemm.hip) take the layer of descriptor ``d`` (``Mp`` output rows per planning
-    unit, ``wbytes`` per weight element and input channel: 2 plain, 4 pairs, 6 triples)?"""
-    Cin, Cout = d.Cin, d.Cout
-    return (d.KH == 1 and d.KW == 1 and d.stride == 1 and (d.pad_t, d.pad_l) == (0, 0) and not d.upsample and d.x2 is None
-            and d.rowvec is None and Cin % 32 == 0 and Cout >= 256 and Mp >= 4096 and ((Mp + 255) // 256) * ((Cout + 255) // 256) >= 128
-            and 256 * Cin * wbytes < 2 ** 32 and not (d.tune & L.TUNE_NO_GEMM256))
 
 
 def _conv2d_f32(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, alpha, beta, norm):
@@ -826,34 +804,33 @@ def to_q8rows(x):
 
 
 def _q8_conv_eligible(B, H, W, Cc, pc, stride, pad, upsample, act, out_planes):
-    """Can rsvld_conv3x3_halo_nhwc run this layer as RSVLD_F16Q8 (and would the halo kernel be chosen for it in the split precision)?"""
-    if pc.kh != 3 or pc.kw != 3 or stride != 1 or upsample or out_planes or act != L.ACT_NONE or pad not in (None, 1, (1, 1, 1, 1)):
-        return False
-    if Cc % 64 or pc.cout_p <= 64 or pc.cout_p % 8 or W < 16 or H < 4 or pc.w.dtype != torch.float32:
-        return False
+    """Can rsvld_conv3x3_halo_nhwc run this layer as RSVLD_F16Q8 (and would the halo kernel be chosen for it in the split precision)?
+    -> the layer's L.ConvPlan (for ``_conv2d_q8``), or None."""
     ctx = _CTX.get()
-    return ctx.use_halo and _halo_wgs(B, H, W, pc.cout_p, ctx.plan_div) >= ctx.split_halo_min_wgs
+    if not ctx.use_halo or act != L.ACT_NONE or pc.w.dtype != torch.float32:     # (_conv2d_q8 has no activation; _wq8 packs fp32 masters)
+        return None
+    plan, _ = _conv_plan(L.load(), _q8_conv_desc(B, H, W, Cc, pc, stride=stride, pad=pad, upsample=upsample, act=act, out_planes=out_planes))
+    return plan if plan.halo_bn != 0 and plan.halo_wgs >= ctx.split_halo_min_wgs else None
 
 
 def _q8_conv_desc(B, H, W, Cc, pc, *, stride=1, pad=1, upsample=False, act=L.ACT_NONE, out_planes=False, **operands):
     """The rsvld_conv_desc of ``pc`` on a ``[B, H, W, Cc]`` input as RSVLD_F16Q8 (``operands``: the tensors and scalars of ``_conv_desc``;
-    absent tensors: null pointers).  ``_conv2d_q8`` launches it; with the geometry of any layer ``_q8_conv_eligible`` is asked about, it
-    is what rsvld_conv3x3_halo_supported must accept."""
+    absent tensors: null pointers).  ``_conv2d_q8`` launches it; ``_q8_conv_eligible`` asks the library's plan of it."""
     shape = (B, H, W, Cc)
     return _conv_desc(shape, 0, pc, _conv_geometry(shape, pc, stride, pad, upsample, act), L.F16Q8, int(not out_planes), stride=stride,
                       upsample=upsample, act=act, **operands)
 
 
-def _conv2d_q8(xq, pc, *, rowvec, residual, alpha, beta, stats):
-    """3x3 / stride 1 / pad 1 on Q8Rows: fp32 out (+ fp32 residual), epilogue statistics for the next GroupNorm."""
+def _conv2d_q8(xq, pc, *, rowvec, residual, alpha, beta, stats, plan):
+    """3x3 / stride 1 / pad 1 on Q8Rows: fp32 out (+ fp32 residual), epilogue statistics for the next GroupNorm.  ``plan``: the layer's,
+    from ``_q8_conv_eligible``."""
     B, H, W, Cc = xq.shape
     out = torch.empty((B, H, W, pc.cout_p), device=xq.t.device, dtype=torch.float32)
     d = _q8_conv_desc(B, H, W, Cc, pc, x=xq.t, w=_wq8(pc), rowvec=rowvec, residual=residual, out=out, alpha=alpha, beta=beta)
-    if not L.load().rsvld_conv3x3_halo_supported(C.byref(d)):
-        raise L.RsvldError("conv2d (q8): shape not supported by the halo kernel (checked by _q8_conv_eligible)")
     flops = 2.0 * B * H * W * pc.cout * pc.cin * 9
     nbytes = 4.0 * (B * H * W * Cc + out.numel() + (0 if residual is None else residual.numel())) + 4.0 * pc.w.numel()
-    _halo_launch("conv_halo_128_q8" + _detail(B, H, W, Cc, 0, pc, 1, False), flops, nbytes, d, out, None, 0, stats)
+    _halo_launch(f"conv_halo_{plan.halo_bn}_q8" + _detail(B, H, W, Cc, 0, pc, 1, False), flops, nbytes, d, out, None, 0,
+                 plan.halo_stat_tiles if stats else 0)
     out._nhwc = True
     return out
 
@@ -946,11 +923,13 @@ def _conv2d_split(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, al
             x16 = _gn_apply_split(x, x2, ab, silu, planes=True, f16=True)
             return conv2d(x16, pc, stride=stride, pad=pad, upsample=upsample, rowvec=rowvec, residual=residual, act=act, alpha=alpha,
                           beta=beta, stats=stats, out_planes=out_planes, out_group=out_group, group=group)
-        if q8_group(norm_group) and _q8_conv_eligible(x.shape[0], x.shape[1], x.shape[2], x.shape[3] + (0 if x2 is None else x2.shape[3]), pc,
-                                                      stride, pad, upsample, act, out_planes):
+        q8_plan = q8_group(norm_group) and _q8_conv_eligible(x.shape[0], x.shape[1], x.shape[2],
+                                                             x.shape[3] + (0 if x2 is None else x2.shape[3]), pc, stride, pad, upsample, act,
+                                                             out_planes)
+        if q8_plan:
             # both operands keep ~22 bits, the two cross terms of the product run in e4m3 (RSVLD_F16Q8; SplitPolicy.q8_convs)
             return _conv2d_q8(_gn_apply_split(x, x2, ab, silu, planes=True, q8=True), pc, rowvec=rowvec, residual=residual, alpha=alpha,
-                              beta=beta, stats=stats)
+                              beta=beta, stats=stats, plan=q8_plan)
         x, x2 = _gn_apply_split(x, x2, ab, silu, planes=True), None
     ctx = _CTX.get()
     x = to_planes(x)
@@ -975,16 +954,13 @@ def _conv2d_split(x, pc, *, x2, stride, pad, upsample, rowvec, residual, act, al
     flops = 2.0 * B * Ho * Wo * pc.cout * pc.cin * pc.kh * pc.kw
     nbytes = 4.0 * (x.numel() + (0 if x2 is None else x2.numel()) + out.numel() / (2 if (out_planes or out_f16) else 1)
                     + (0 if residual is None else residual.numel())) + 6.0 * pc.w.numel()
-    halo = ctx.use_halo and bool(lib.rsvld_conv3x3_halo_supported(C.byref(d)))
-    if halo:
-        halo = _halo_wgs(B, Ho, Wo, pc.cout_p, ctx.plan_div) >= ctx.split_halo_min_wgs
-    if halo:
-        _halo_launch(("conv_halo_64_split" if pc.cout_p <= 64 else "conv_halo_128_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
-                     flops, nbytes, d, out, None, 0, stats and not out_planes)
+    plan, rc = _conv_plan(lib, d)
+    if ctx.use_halo and plan.halo_bn != 0 and plan.halo_wgs >= ctx.split_halo_min_wgs:
+        _halo_launch(f"conv_halo_{plan.halo_bn}_split" + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
+                     flops, nbytes, d, out, None, 0, plan.halo_stat_tiles if stats and not out_planes else 0)
     else:
-        M = B * Ho * Wo
-        Mp = -(-M // ctx.plan_div)
-        _launch(("gemm_256x256_split" if _gemm256_label(d, Mp, 6) else "conv_igemm_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
+        L.check(rc, "rsvld_plan_conv")
+        _launch(("gemm_256x256_split" if plan.gemm256 else "conv_igemm_split") + _detail(B, Ho, Wo, Cin, Cin2, pc, stride, upsample),
                 flops, nbytes, lambda: L.check(lib.rsvld_conv2d_nhwc(C.byref(d), _stream()), "rsvld_conv2d_nhwc"))
     if out_f16:
         return out

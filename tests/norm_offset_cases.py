@@ -43,34 +43,22 @@ def gn_bound(dtype, out="same"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# routes: mirrors of gn_small_ok / gn_plan (csrc/norm.hip)
+# routes: the library's own answer (rsvld_plan_groupnorm, a host-only query: needs the built library, no device)
 # ---------------------------------------------------------------------------------------------------------------------------------
-GN_SMALL_MAXV, GN_MAX_CHUNKS, GN_MIN_ROWS = 32, 512, 64
+def gn_plan(dtype, B, HW, C1, C2, groups):
+    """-> rsvld_groupnorm_plan: ``small`` (the one-workgroup route), ``nchunks`` x ``rows_per_chunk`` of the partials route and the
+    ``rows_in_flight`` of its statistics kernel."""
+    import ctypes
+    from rsvld_amd import _lib as L
+    plan = L.GroupnormPlan()
+    rc = L.load().rsvld_plan_groupnorm({F16: L.F16, BF16: L.BF16, F32: L.F32}[dtype], B, HW, C1, C2, groups, ctypes.byref(plan))
+    assert rc == 0, L.ERRORS.get(rc, rc)
+    return plan
 
 
-def mirror_gn_small_ok(HW, C1, C2, groups):
-    gs = (C1 + C2) // groups
-    if gs % 8:
-        return False
-    gs8 = gs // 8
-    if gs8 > 256 or gs8 & (gs8 - 1):
-        return False
-    if C2 > 0 and C1 % gs:
-        return False
-    if HW * gs8 > 256 * GN_SMALL_MAXV:
-        return False
-    return groups >= 32
-
-
-def mirror_gn_plan(HW):
-    """-> (nchunks, rows_per_chunk)"""
-    rpc = max((HW + GN_MAX_CHUNKS - 1) // GN_MAX_CHUNKS, GN_MIN_ROWS)
-    return (HW + rpc - 1) // rpc, rpc
-
-
-def gn_route(dtype, HW, C1, C2, groups):
+def gn_route(dtype, HW, C1, C2, groups, B=1):
     """The statistics route of rsvld_groupnorm_nhwc / _scale_shift: the one-workgroup kernel (16-bit only) or the row-chunk partials."""
-    return "small" if dtype != F32 and mirror_gn_small_ok(HW, C1, C2, groups) else "partial"
+    return "small" if gn_plan(dtype, B, HW, C1, C2, groups).small else "partial"
 
 
 GnShape = namedtuple("GnShape", "name B C1 C2 H W groups route16 why")
@@ -230,8 +218,8 @@ def _chunk_thread_terms(c):
     s = c["s"]
     assert s.C2 == 0
     C, HW = s.C1, s.H * s.W
-    nch, rpc = mirror_gn_plan(HW)
-    rif = 256 // min(C // 8, 256)
+    plan = gn_plan(c["dtype"], s.B, HW, C, 0, s.groups)
+    nch, rpc, rif = plan.nchunks, plan.rows_per_chunk, plan.rows_in_flight
     xr = _rows_nhwc(c)
     pad = nch * rpc - HW
     xr = F.pad(xr, (0, 0, 0, pad))

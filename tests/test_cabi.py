@@ -23,20 +23,32 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.rsvld_version()
 
 
-def test_conv_desc_matches_header_layout():
-    """Field order / count of the ctypes struct follows the C struct declaration."""
-    from rsvld_amd import _lib
+def _header_fields(name):
+    """(C type, field) of ``typedef struct name { ... } name;`` in the header, in order."""
     src = open(os.path.join(ROOT, "include", "rsvld_hip.h")).read()
-    start = src.index("typedef struct rsvld_conv_desc {") + len("typedef struct rsvld_conv_desc {")
-    body = re.sub(r"/\*.*?\*/", "", src[start:src.index("} rsvld_conv_desc;")], flags=re.S)
+    start = src.index(f"typedef struct {name} {{") + len(f"typedef struct {name} {{")
+    body = re.sub(r"/\*.*?\*/", "", src[start:src.index(f"}} {name};")], flags=re.S)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if not decl:
             continue
-        for nm in decl.split(","):
-            fields.append(nm.strip().split()[-1].lstrip("*"))
-    assert fields == [f[0] for f in _lib.ConvDesc._fields_]
+        first, *more = decl.split(",")
+        ctype = " ".join(first.split()[:-1])
+        for nm in [first.split()[-1]] + more:
+            fields.append((ctype, nm.strip().lstrip("*")))
+    return fields
+
+
+def test_conv_desc_matches_header_layout():
+    """Field order / count of the ctypes struct follows the C struct declaration."""
+    import ctypes
+    from rsvld_amd import _lib
+    assert [f for _, f in _header_fields("rsvld_conv_desc")] == [f[0] for f in _lib.ConvDesc._fields_]
+    # the outputs of the host-only plan queries: field order AND integer width (Python reads them)
+    widths = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+    for name, struct in (("rsvld_conv_plan", _lib.ConvPlan), ("rsvld_groupnorm_plan", _lib.GroupnormPlan)):
+        assert [(f, widths[t]) for t, f in _header_fields(name)] == list(struct._fields_), name
 
 
 def test_constants_match_header():

@@ -20,6 +20,7 @@ import torch
 
 import guarded as G
 from test_gpu_kernels import CONV_CASES, GEMM_CASES, GN_CASES, HALO_CASES
+from test_gpu_matrix_exact import linear_desc, plan_conv
 from test_gpu_split import CONV_CASES as SPLIT_CONV_CASES, LINEAR_CASES as SPLIT_LINEAR_CASES, Q8_CASES, W2_CONV_CASES, W2_LINEAR_CASES
 from test_gpu_f32 import CONV_CASES as F32_CONV_CASES, MODES as F32_MODES
 
@@ -253,8 +254,8 @@ def _linear_spec(dev, dt, M, K, N, act, use_res, *, mode="16", alpha=1.0, beta=1
         x = ops.to_planes(x)
     a = {0: L.ACT_NONE, 1: L.ACT_SILU, 2: L.ACT_GEGLU}[act]
     fn = _under(*ctx)(lambda x, pc, residual: ops.linear(x, pc, residual=residual, act=a, alpha=alpha, beta=beta, **kw))
-    # (ops.conv2d's own mirror of rsvld_gemm256_try: smaller problems run the implicit-GEMM kernel of the same dtype)
-    big = M >= 4096 and K % 32 == 0 and pc.cout_p >= 256 and ((M + 255) // 256) * ((pc.cout_p + 255) // 256) >= 128
+    # (the library's plan of the layer, rsvld_plan_conv: smaller problems run the implicit-GEMM kernel of the same dtype)
+    big = plan_conv(linear_desc(M, K, pc.cout_p, 0)).gemm256 != 0
     return dict(fn=fn, operands=dict(x=x, pc=G.Op(pc, forms=forms), residual=res), expect="gemm_256x256" + sfx if big else None,
                 prefix=None if big else "conv_igemm")
 
@@ -277,7 +278,7 @@ _gemm("half_tiles_lower_half_beyond_m", GEMM_CASES[10], (F16, BF16))   # the las
 _gemm("one_tile_form_alpha_beta_residual", (8448, 384, 2304, 0, True), mode="one_tile", alpha=0.5, beta=2.0)
 _gemm("persistent_alpha_beta_residual", (8448, 384, 2304, 0, True), alpha=0.5, beta=2.0)
 _gemm("one_tile_form_no_bias", (8192, 640, 2048, 0, False), mode="one_tile", bias=False)
-# (8 269 x 2 560 -> 640 is 99 tiles: under ops.conv2d's mirror of the gemm256 threshold the label is the implicit-GEMM kernel's; either way the ragged last row tile)
+# (8 269 x 2 560 -> 640 is 99 tiles, below the gemm256 threshold: the implicit-GEMM kernel runs and the label says so; either way the ragged last row tile)
 _gemm("w1_fp32_residual_8269_rows", (W2_LINEAR_CASES[1][0], W2_LINEAR_CASES[1][1], W2_LINEAR_CASES[1][2], 0, True), mode="w1", alpha=0.5)
 _gemm("w1_ragged_rows_and_column_tile", (20000, 640, 640, 0, True), mode="w1", alpha=0.5)
 _gemm("w2_pairs_8269_rows", (W2_LINEAR_CASES[1][0], W2_LINEAR_CASES[1][1], W2_LINEAR_CASES[1][2], 0, True), mode="w2", alpha=0.5)

@@ -13,8 +13,9 @@ suite runs without a GPU: tests/test_matrix_exact_cases.py walks the same tables
   * the fp32 CPU product equals the fp64 one;
   * K * max|x| * max|w| in units of the operands' last bit stays below 2^24: no order of fp32 accumulation can round;
   * (halo statistics) every per-tile sum and sum of squares is an integer below 2^24.
-Which instantiation a row lands in is arithmetic on its shape; ``mirror_dispatch_conv2`` / ``mirror_dispatch_halo`` restate the two
-dispatch functions and every row is checked against its claim (on the CPU as well).
+Which instantiation a row lands in is arithmetic on its shape: the library's own planner (rsvld_plan_conv, a host-only query) is asked
+about every row's descriptor and checked against the row's claim on the CPU, and the profiler label of ops.conv2d -- made from the same
+plan -- is asserted on the GPU for every row, so a forced tile is proven to have run by name.
 
 A tolerance case per instantiation (random normal operands as test_gpu_kernels.test_conv2d builds them, SiLU and GEGLU epilogues)
 uses that module's ``_close`` unchanged."""
@@ -41,75 +42,41 @@ ST2, ST3, ST4 = 2 << 3, 3 << 3, 4 << 3
 NO_KSPLIT, REG, NW4, NW8, NO_GEMM256, ONE_TILE = 1 << 6, 1 << 7, 1 << 8, 1 << 9, 1 << 10, 1 << 12
 
 
-# ============================================================================= mirrors of the dispatch functions
+# ============================================================================= the library's plan of a case
 Inst = namedtuple("Inst", "bm bn stages ks staging")     # one instantiation of conv_igemm_kernel
+_TENSOR = 1 << 12     # the plan queries compare a descriptor's pointers with NULL only: any other value stands for a tensor
 
 
-def mirror_dispatch_conv2(M_plan, Cout, nk, tune):
-    """dispatch_conv / dispatch_conv2 of csrc/conv_igemm.hip, line by line."""
-    glds = not (tune & REG)
-    staging = "lds" if glds else "reg"
-    if Cout <= 32:
-        return Inst(256, 32, 2, 1, staging)
-    ov = tune & 7
-    st = ((tune >> 3) & 7) if glds else 2
-    ksplit = not (tune & NO_KSPLIT)
-    if Cout <= 64:
-        if ov == 1:
-            return Inst(256, 64, 2, 1, staging)
-        if glds and st in (3, 4):
-            return Inst(128, 64, st, 1, staging)
-        return Inst(128, 64, 2, 1, staging)
-    wg128 = ((M_plan + 127) // 128) * ((Cout + 127) // 128)
-    wg64x128 = ((M_plan + 63) // 64) * ((Cout + 127) // 128)
-    if glds and ov == 0 and wg64x128 < 256:
-        wg64 = ((M_plan + 63) // 64) * ((Cout + 63) // 64)
-        if ksplit and st == 0 and wg64 <= 256 and nk >= 16:
-            return Inst(64, 64, 4, 2, staging)
-        return Inst(64, 64, 4, 1, staging)
-    if ov == 4 or (ov == 0 and wg128 < 256):
-        if glds:
-            if ksplit and st == 0 and wg64x128 <= 256 and nk >= 16:
-                return Inst(64, 128, 3, 2, staging)
-            if st in (3, 0):
-                return Inst(64, 128, 3, 1, staging)
-            if st == 4:
-                return Inst(64, 128, 4, 1, staging)
-        return Inst(64, 128, 2, 1, staging)
-    if glds and st in (3, 4):
-        return Inst(128, 128, st, 1, staging)
-    return Inst(128, 128, 2, 1, staging)
+def plan_conv(desc):
+    """rsvld_plan_conv of an ``L.ConvDesc`` -> L.ConvPlan; the descriptor must be one rsvld_conv2d_nhwc accepts."""
+    from rsvld_amd import _lib as L
+    import ctypes
+    plan = L.ConvPlan()
+    rc = L.load().rsvld_plan_conv(ctypes.byref(desc), ctypes.byref(plan))
+    assert rc == 0, L.ERRORS.get(rc, rc)
+    return plan
 
 
-def mirror_dispatch_halo(B_plan, H, W, Ctot, Cout, tune):
-    """dispatch_halo of csrc/conv_halo.hip -> (BN, waves)."""
-    if Cout <= 64:
-        return (64, 4)
-    wg16 = ((W + 31) // 32) * ((H + 15) // 16) * B_plan * ((Cout + 127) // 128)
-    use8 = True if tune & NW8 else False if tune & NW4 else (wg16 >= 192 and Ctot >= 192)
-    return (128, 8 if use8 else 4)
+def planned_inst(desc):
+    """The implicit-GEMM instantiation the library plans for ``desc`` (gemm256 must not take it)."""
+    p = plan_conv(desc)
+    assert p.gemm256 == 0
+    return Inst(p.bm, p.bn, p.stages, p.ks, "reg" if p.reg_staging else "lds")
 
 
-def mirror_gemm256(M, K, N, tune, n_cu=256):
-    """rsvld_gemm256_try of csrc/gemm.hip for a 16-bit Linear with a 16-bit output (the mirror tests/test_gpu_guarded.py keeps decides
-    eligibility only) -> None (the implicit-GEMM kernel takes it) or (form, whole tiles, half tiles) of the launch."""
-    if tune & NO_GEMM256 or K % 32 or N < 256 or M < 4096:
-        return None
+def persistent_tiles(M, N, n_cu=256):
+    """The tile enumeration of gemm256_kernel<PERSIST> (device code: nothing to query) -> (whole tiles, half tiles) of the launch."""
     nmt, nnt = (M + 255) // 256, (N + 255) // 256
-    if nmt * nnt < 128:
-        return None
-    if tune & ONE_TILE or K < 128:
-        return ("one_tile", nmt * nnt, 0)
     grid, ntiles, whole, halves = min(nmt * nnt, n_cu), nmt * nnt, 0, 0
     q, r = ntiles >> 3, ntiles & 7
-    for xcd in range(8):       # the tile enumeration of gemm256_kernel<PERSIST>
+    for xcd in range(8):
         qx, step = q + (1 if xcd < r else 0), (grid - xcd + 7) >> 3
         rem = qx % step
         if 0 < rem and 2 * rem <= step:
             whole, halves = whole + qx - rem, halves + 2 * rem
         else:
             whole += qx
-    return ("persistent", whole, halves)
+    return whole, halves
 
 
 # ============================================================================= shapes
@@ -129,6 +96,24 @@ def geometry(s):
 
 def nk_of(s, seg=1):
     return (seg * geometry(s)[3] + 7) // 8
+
+
+def conv_desc(s, tune, dtype=0, out_f32=0, cout_p=None):
+    """The rsvld_conv_desc ops.conv2d builds for case shape ``s`` (``dtype`` / ``out_f32``: RSVLD_* operand form and output code), without
+    tensors: for the plan queries.  A rowvec is set, as in every exact case."""
+    from rsvld_amd import _lib as L
+    Ho, Wo, _, _ = geometry(s)
+    pad = 0 if s.mode == "s2" else s.k // 2
+    return L.ConvDesc(x=_TENSOR, x2=_TENSOR if s.C2 else None, w=_TENSOR, rowvec=_TENSOR, out=_TENSOR, B=s.B, H=s.H, W=s.W, Cin=s.C1,
+                      Cin2=s.C2, Cout=cout_p or s.Cout, KH=s.k, KW=s.k, stride=2 if s.mode == "s2" else 1, pad_t=pad, pad_l=pad, Ho=Ho,
+                      Wo=Wo, upsample=int(s.mode == "up"), dtype=dtype, out_f32=out_f32, alpha=1.0, beta=1.0, tune=tune)
+
+
+def linear_desc(M, K, N, tune):
+    """ops.linear's descriptor of an [M, K] x [N, K] layer with a 16-bit output (no rowvec)."""
+    from rsvld_amd import _lib as L
+    return L.ConvDesc(x=_TENSOR, w=_TENSOR, out=_TENSOR, B=1, H=1, W=M, Cin=K, Cout=N, KH=1, KW=1, stride=1, Ho=1, Wo=M, alpha=1.0,
+                      beta=1.0, tune=tune)
 
 
 def conv_kwargs(s):
@@ -151,13 +136,12 @@ def shape_b(cout, mode, k):
 
 
 # ============================================================================= the instantiation table
-# One row per instantiation of dispatch_conv2 (both 16-bit types run every row).  ``label``: the profiler label of ops.conv2d follows
-# the DEFAULT routing (by Cout, then by the grid of M_plan), not the forced tile -- it is asserted where the two coincide: every row
-# whose tile family is the default one of its shape (256x32, 128x64 at any ring depth or staging, 64x64, and the three large rows
-# at the end that are routed by their grid alone).  Forced 256x64 / 64x128 / 128x128 rows on the small shapes carry label None.
+# One row per instantiation of conv_igemm.hip's launch table (both 16-bit types run every row).  ``label``: the profiler label of
+# ops.conv2d names the tile family of the kernel that ran, forced tiles included; it is asserted for every row.
 # ``b``: (mode, k) of exact case B, stride 2 and up-sampling alternating down the table; None: the row runs case A only.
 Row = namedtuple("Row", "name tune cout inst label b a_shape")
 L32, L64, L6464, L64128, L128 = ("conv_igemm_256x32", "conv_igemm_128x64", "conv_igemm_64x64", "conv_igemm_64x128", "conv_igemm_128x128")
+L25664 = "conv_igemm_256x64"
 
 
 def _row(name, tune, cout, inst, label, b, a_shape=None):
@@ -169,8 +153,8 @@ ROWS = [
     _row("256x32", 0, 24, (256, 32, 2, 1, "lds"), L32, ("s2", 3)),
     _row("256x32_reg", REG, 24, (256, 32, 2, 1, "reg"), L32, ("up", 3)),
     # Cout 48 <= 64: tile mask 1 -> 256x64; otherwise 128x64 at the ring depth of the stage bits (2 = default; mask 2 names the default)
-    _row("256x64", T256x64, 48, (256, 64, 2, 1, "lds"), None, ("s2", 3)),
-    _row("256x64_reg", T256x64 | REG, 48, (256, 64, 2, 1, "reg"), None, ("up", 3)),
+    _row("256x64", T256x64, 48, (256, 64, 2, 1, "lds"), L25664, ("s2", 3)),
+    _row("256x64_reg", T256x64 | REG, 48, (256, 64, 2, 1, "reg"), L25664, ("up", 3)),
     _row("128x64", 0, 48, (128, 64, 2, 1, "lds"), L64, ("s2", 3)),
     _row("128x64_mask2", T128x64, 48, (128, 64, 2, 1, "lds"), L64, ("up", 3)),
     _row("128x64_st3", ST3, 48, (128, 64, 3, 1, "lds"), L64, ("s2", 3)),
@@ -181,17 +165,17 @@ ROWS = [
     _row("64x64_ks2", 0, 176, (64, 64, 4, 2, "lds"), L6464, ("up", 3)),
     _row("64x64", NO_KSPLIT, 176, (64, 64, 4, 1, "lds"), L6464, ("s2", 1)),
     # tile mask 4 -> 64x128: wg64x128 <= 256 and nk >= 16 -> two K groups; NO_KSPLIT or stage bits 3 -> 3 stages; 4 -> 4; 2 -> the double buffer
-    _row("64x128_ks2", T64x128, 176, (64, 128, 3, 2, "lds"), None, ("up", 3)),
-    _row("64x128_st3", T64x128 | NO_KSPLIT, 176, (64, 128, 3, 1, "lds"), None, ("s2", 3)),
-    _row("64x128_st4", T64x128 | ST4, 176, (64, 128, 4, 1, "lds"), None, ("up", 3)),
-    _row("64x128_st2", T64x128 | ST2, 176, (64, 128, 2, 1, "lds"), None, ("s2", 3)),
-    _row("64x128_reg", T64x128 | REG, 176, (64, 128, 2, 1, "reg"), None, ("up", 3)),
+    _row("64x128_ks2", T64x128, 176, (64, 128, 3, 2, "lds"), L64128, ("up", 3)),
+    _row("64x128_st3", T64x128 | NO_KSPLIT, 176, (64, 128, 3, 1, "lds"), L64128, ("s2", 3)),
+    _row("64x128_st4", T64x128 | ST4, 176, (64, 128, 4, 1, "lds"), L64128, ("up", 3)),
+    _row("64x128_st2", T64x128 | ST2, 176, (64, 128, 2, 1, "lds"), L64128, ("s2", 3)),
+    _row("64x128_reg", T64x128 | REG, 176, (64, 128, 2, 1, "reg"), L64128, ("up", 3)),
     # tile mask 3 -> 128x128 (the 64x64 / 64x128 re-tiling of small grids is for mask 0 / 4 only); case B of the first row is 1 x 1
-    _row("128x128", T128x128, 176, (128, 128, 2, 1, "lds"), None, ("s2", 1)),
-    _row("128x128_st3", T128x128 | ST3, 176, (128, 128, 3, 1, "lds"), None, ("up", 3)),
-    _row("128x128_st4", T128x128 | ST4, 176, (128, 128, 4, 1, "lds"), None, ("s2", 3)),
-    _row("128x128_reg", T128x128 | REG, 176, (128, 128, 2, 1, "reg"), None, ("up", 3)),
-    # the same three tiles reached by the DEFAULT routing (tune 0), so that their labels are asserted.  Sources 24 | 16: 45 pieces, nk = 6.
+    _row("128x128", T128x128, 176, (128, 128, 2, 1, "lds"), L128, ("s2", 1)),
+    _row("128x128_st3", T128x128 | ST3, 176, (128, 128, 3, 1, "lds"), L128, ("up", 3)),
+    _row("128x128_st4", T128x128 | ST4, 176, (128, 128, 4, 1, "lds"), L128, ("s2", 3)),
+    _row("128x128_reg", T128x128 | REG, 176, (128, 128, 2, 1, "reg"), L128, ("up", 3)),
+    # the same three tiles reached by the DEFAULT routing (tune 0): routed by their grid alone.  Sources 24 | 16: 45 pieces, nk = 6.
     # 2 x 63 x 66 = 8316 rows: wg64x128 = 130 * 2 = 260 >= 256 (no 64x64, no K groups), wg128 = 65 * 2 = 130 < 256 -> 64x128, 3 stages
     _row("64x128_default", 0, 176, (64, 128, 3, 1, "lds"), L64128, None, Shape(2, 63, 66, 24, 16, 176, 3, "p1")),
     # 2 x 63 x 65 = 8190 rows, sources 72 | 48 (nk = 17): wg64x128 = 128 * 2 = 256 exactly -> 64x128 with two K groups
@@ -457,9 +441,7 @@ def _run_row(ops, dev, dtype, row, s, c, **extra):
     rec = _Names()
     with ops.tuning(tune=row.tune, use_halo=False, profiler=rec):
         got = run_conv_exact(ops, dev, dtype, s, c, **extra)
-    assert len(rec.names) == 1 and rec.names[0].startswith("conv_igemm"), rec.names
-    if row.label is not None:
-        assert rec.names[0] == row.label, f"{row.name} drifted to {rec.names[0]}"
+    assert rec.names == [row.label], f"{row.name} ran {rec.names}"
     return got
 
 
@@ -497,7 +479,7 @@ def test_conv_tolerance_silu_geglu(cuda, dtype, row):
         with ops.tuning(tune=row.tune, use_halo=False, profiler=rec):
             got = ops.conv2d(_nhwc(c["x"], dtype, cuda), ops.pack_conv(c["w"], c["b"], dtype, cuda, geglu=geglu), pad=1,
                              act=L.ACT_GEGLU if geglu else L.ACT_SILU)
-        assert rec.names == [row.label or rec.names[0]] and rec.names[0].startswith("conv_igemm")
+        assert rec.names == [row.label], rec.names
         assert got.shape[-1] == (cout // 2 if geglu else cout)
         _close(got.permute(0, 3, 1, 2), c["want"], dtype)
 
@@ -557,7 +539,8 @@ def test_conv_multi_segment_exact(cuda, row, mode, side):
     with ops.tuning(tune=row.tune, use_halo=False, profiler=rec):
         got = _seg_call(ops, cuda, mode, c)
     label = [n for n in rec.names if n.startswith("conv_igemm")]
-    assert len(label) == 1 and label[0].endswith({"split3": "_split", "pair2": "_w2", "w1": "_w1"}[mode]), rec.names
+    tile = f"conv_igemm_{row.inst.bm}x{row.inst.bn}"       # (the split path's label names no tile)
+    assert label == [{"split3": "conv_igemm_split", "pair2": tile + "_w2", "w1": tile + "_w1"}[mode]], rec.names
     assert got.dtype == F32
     assert torch.equal(got.cpu().double(), c["want"])
 

@@ -1,17 +1,13 @@
 """The case tables of tests/test_gpu_norm_offset.py, walked on the CPU (tests/norm_offset_cases.py): every case must be FAIR (ideal
 statistics through the kernels' own fp32 affine and output rounding stay within half the bound the GPU test applies), must land in
-the route it names (mirrors of gn_small_ok / gn_plan), and must have TEETH (fp32 (sum, sum of squares) partials in
+the route it names (the library's planner, rsvld_plan_groupnorm), and must have TEETH (fp32 (sum, sum of squares) partials in
 gn_partial_kernel's order, the arithmetic these kernels had, break the fp32-input bound at mean / sigma = 64)."""
-import re
-from pathlib import Path
-
 import pytest
 import torch
 
 import norm_offset_cases as NC
 
 F16, BF16, F32 = NC.F16, NC.BF16, NC.F32
-CSRC = Path(__file__).resolve().parents[1] / "remote-sensing-vision-language-diffusion-model_amd" / "csrc"
 SHAPES = NC.GN_SHAPES + [NC.WIDE_SHAPE]
 
 
@@ -101,29 +97,23 @@ def test_cases_land_in_the_routes_they_name():
         assert (s.C1 + s.C2) % s.groups == 0 and s.C1 % 8 == 0 and s.C2 % 8 == 0
     by = NC.GN_BY_NAME
     w = NC.WIDE_SHAPE                                                     # sums + pivots above 64 KiB of LDS, sums alone below
-    assert (256 // min(w.C1 // 8, 256)) * w.C1 * 8 <= 65536 < (256 // min(w.C1 // 8, 256)) * w.C1 * 8 + w.C1 * 4
+    rif = NC.gn_plan(F32, w.B, w.H * w.W, w.C1, 0, w.groups).rows_in_flight
+    assert rif * w.C1 * 8 <= 65536 < rif * w.C1 * 8 + w.C1 * 4
     assert NC.gn_route(F32, w.H * w.W, w.C1, 0, w.groups) == "partial"
-    assert NC.mirror_gn_plan(48 * 48) == (36, 64) and NC.mirror_gn_plan(9 * 33) == (5, 64) and 9 * 33 % 64 == 41
-    assert NC.mirror_gn_plan(512 * 512) == (512, 512)                     # a chunk is 512 rows
-    assert NC.mirror_gn_plan(19 * 23)[0] > 1                              # more than one block on the partial route too
+
+    def chunks(HW):                                                       # the chunking depends on the image size alone
+        p = NC.gn_plan(F32, 1, HW, 64, 0, 32)
+        return p.nchunks, p.rows_per_chunk
+
+    assert chunks(48 * 48) == (36, 64) and chunks(9 * 33) == (5, 64) and 9 * 33 % 64 == 41
+    assert chunks(512 * 512) == (512, 512)                                # a chunk is 512 rows
+    assert chunks(19 * 23)[0] > 1                                         # more than one block on the partial route too
     st = by["straddle"]
     gs = (st.C1 + st.C2) // st.groups
     assert st.C1 % gs != 0 and gs % 8 != 0                                # a group lies across the two sources, and across vectors
     assert (by["gs2"].C1 // by["gs2"].groups) == 2
     # the odd sizes: rows that are no multiple of the rows in flight
     assert (19 * 23) % 32 and (9 * 33) % 32
-
-
-def test_mirrors_follow_the_source():
-    src = (CSRC / "norm.hip").read_text()
-    assert f"constexpr int GN_SMALL_MAXV = {NC.GN_SMALL_MAXV};" in src
-    plan = src[src.index("GnPlan gn_plan("):src.index("bool gn_dims_ok(")]
-    assert f"const int max_chunks = {NC.GN_MAX_CHUNKS};" in plan and f"if (rpc < {NC.GN_MIN_ROWS}) rpc = {NC.GN_MIN_ROWS};" in plan
-    small = src[src.index("bool gn_small_ok("):src.index("struct GnPlan")]
-    for line in ("if (gs % 8) return false;", "if (gs8 > 256 || (gs8 & (gs8 - 1))) return false;", "if (C2 > 0 && C1 % gs) return false;",
-                 "if ((int64_t)HW * gs8 > (int64_t)256 * GN_SMALL_MAXV) return false;", "return groups >= 32;"):
-        assert line in small, line
-    assert re.search(r"TPR = C8 < 256 \? C8 : 256;\s+rif = 256 / TPR;", src)
 
 
 def test_fp32_sum_sumsq_partials_break_the_fp32_input_bound_at_64():
