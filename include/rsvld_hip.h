@@ -277,9 +277,28 @@ int rsvld_attention_tuned(const void* q, const void* k, const void* v, void* out
                           int64_t v_batch_stride, int64_t v_tok_stride,
                           int64_t o_batch_stride, int64_t o_tok_stride,
                           float scale, int dtype, int plan_div, void* ws, void* stream, int tune);
-/* bytes of `ws` the call above needs (0 = none, ws may be NULL): the D = 512 kernel splits the keys over
- * workgroups when the query tiles of B / plan_div batch rows alone cannot fill the chip and merges the partial
- * results from ws (plan_div: independent units stacked along B, see the conventions; 0 or 1 = plan on B). */
+/* The launch plan of rsvld_attention_tuned, as a HOST-ONLY query: integer arithmetic, no device, no pointer.  shared_kv != 0: keys and
+ * values are one tensor (k == v and equal strides); k_tok_stride / v_tok_stride as in the call (read for D = 64 only: attn_d64c forms
+ * 32-bit offsets of 64 key rows).  Returns what the call returns for these arguments before it looks at pointers, dtype and stride
+ * alignment: RSVLD_EINVAL / RSVLD_EUNSUPPORTED, else RSVLD_OK with
+ *   row             the kernel (RSVLD_ATTN_ROW_*: one row of the launch table of csrc/attention.hip, per 16-bit type);
+ *   nsplit          key ranges (1 = no split; D = 512 splits the keys over workgroups when the query tiles of B / plan_div batch rows
+ *                   alone cannot fill the chip, or beyond 98 304 keys, and merges the partial results from ws);
+ *   keys_per_split  keys of a range;   ws_bytes  bytes of `ws` the call needs (0 = none, ws may be NULL);   grid_*  its workgroups. */
+#define RSVLD_ATTN_ROW_D64B_NW4 1     /* attn_d64b, 4 waves: 128 query rows per workgroup */
+#define RSVLD_ATTN_ROW_D64B_NW8 2     /* attn_d64b, 8 waves: 256 query rows */
+#define RSVLD_ATTN_ROW_D64C 3         /* attn_d64c: 512 query rows */
+#define RSVLD_ATTN_ROW_D512B 4        /* attn_d512b, keys and values two tensors */
+#define RSVLD_ATTN_ROW_D512B_SHARED 5 /* attn_d512b, shared tile (RSVLD_ATTN_D512_ROWS) */
+#define RSVLD_ATTN_ROW_D512D 6        /* attn_d512d, shared tile */
+typedef struct rsvld_attention_plan {
+    int64_t ws_bytes;
+    int32_t row, nsplit, keys_per_split;
+    int32_t grid_x, grid_y, grid_z;
+} rsvld_attention_plan;
+int rsvld_plan_attention(int B, int heads, int Nq, int Nk, int D, int plan_div, int tune, int shared_kv,
+                         int64_t k_tok_stride, int64_t v_tok_stride, rsvld_attention_plan* plan);
+/* ws_bytes of that plan (0 also where the plan is refused) */
 int64_t rsvld_attention_ws_bytes(int B, int heads, int Nq, int Nk, int D, int plan_div);
 
 /* ---------------------------------------------------------------------------------------

@@ -64,6 +64,15 @@ class GroupnormPlan(C.Structure):
     _fields_ = [("small", C.c_int32), ("nchunks", C.c_int32), ("rows_per_chunk", C.c_int32), ("rows_in_flight", C.c_int32)]
 
 
+class AttentionPlan(C.Structure):
+    """rsvld_attention_plan (rsvld_plan_attention, host only); ``row``: an ATTN_ROW value."""
+    _fields_ = [("ws_bytes", C.c_int64), ("row", C.c_int32), ("nsplit", C.c_int32), ("keys_per_split", C.c_int32),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32)]
+
+
+# rsvld_attention_plan.row (RSVLD_ATTN_ROW_*): the rows of the launch table of csrc/attention.hip
+ATTN_ROW = {"d64b_nw4": 1, "d64b_nw8": 2, "d64c": 3, "d512b": 4, "d512b_shared": 5, "d512d": 6}
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every symbol include/rsvld_hip.h declares
@@ -85,6 +94,7 @@ SIGNATURES = {
                              _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _i, _i, _vp, _vp]),
     "rsvld_attention_tuned": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                              _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _i, _i, _vp, _vp, _i]),
+    "rsvld_plan_attention": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, C.POINTER(AttentionPlan)]),
     "rsvld_attention_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "rsvld_linear_small_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rsvld_sinusoidal_embedding": (_i, [_vp, _vp, _i, _i, _i, _vp]),

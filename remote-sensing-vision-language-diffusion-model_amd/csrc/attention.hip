@@ -7,6 +7,7 @@
 // register-local, and use the converted score tile in place as the B operand of O^T += V^T P^T.  The forms that were measured
 // against these and lost are recorded in docs/HISTORY_r01-r05.md and DESIGN.md, not here.
 #include "rsvld_common.h"
+#include "rsvld_plan.h"
 #include <type_traits>
 #include <utility>
 
@@ -474,11 +475,7 @@ __device__ __forceinline__ void a6_store_o(char* wbuf, const f32x16 (&oacc)[2], 
 // NW = waves per workgroup: 4 (128 query rows) or 8 (256 query rows).  The 64-key K / V tile is filled once per workgroup,
 // so with 8 waves every wave issues ONE LDS-DMA piece per tensor per tile instead of two and there is one barrier per 256
 // query rows: the in-loop DMA + barrier cost (ablation: +13 % without it at 65 536 tokens) is halved per MFMA.  Two
-// 8-wave workgroups per CU keep the four waves per SIMD.  Chosen for long query sequences (A6B_NW8_MIN); the gain is small: the kernel is not bound by that term alone.
-#ifndef A6B_NW8_MIN
-#define A6B_NW8_MIN 16384   // round 2 (one box, 2 x 10 heads): +1.5 % at 65 536 tokens, -0.5 % (noise) at 16 384; with the bias step
-                            // (round 3, 2 x 20 heads at 16 384 tokens): +1.3 % (880 -> 891 TFLOP/s), so 16 384 tokens take it too
-#endif
+// 8-wave workgroups per CU keep the four waves per SIMD.  Chosen for long query sequences (A6B_NW8_MIN, rsvld_plan.h); the gain is small: the kernel is not bound by that term alone.
 template <typename T, int NW>
 __global__ __launch_bounds__(64 * NW, 4) void attn_d64b_kernel(AttnArgs p) {
     constexpr int D = 64;
@@ -797,43 +794,56 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_d64b_kernel(AttnArgs p) {
 
 }  // namespace
 
-// split-KV plan of the D = 512 kernel: key ranges per workgroup
-//   (a) so that the grid fills the 256 CUs when the query tiles alone cannot;
-//   (b) so that ONE key range stays resident in the 256 MiB Infinity Cache while every query tile streams it.  At
-//       N = 262 144 the key/value tensor is 268 MB (shared tile) or 537 MB: every workgroup re-streamed it from HBM
-//       (rocprofv3 FETCH_SIZE: ~400 GB per launch, ~3 TB/s for the whole 131 ms).  Workgroups are dispatched range-major
-//       (blockIdx.y), so with ranges of A5B_MALL_KEYS keys (64 MiB shared / 128 MiB as two tensors) all the query tiles in
-//       flight read the same range out of the cache; the price is one fp32 partial (O, m, l) per range and the merge pass.
-//       Measured on one box (N = 262 144, shared tile): 1036 TFLOP/s with 64 Ki-key ranges, 1041 without, 1026 with 32 Ki:
-//       the kernel is NOT bound by that HBM stream (its LDS-DMA requests are two tiles ahead), so this buys no time; it is
-//       kept because it takes ~3 TB/s of needless HBM traffic (and its power) out of the dominant Stage-1 kernel.
-#ifndef A5B_MALL_KEYS
-#define A5B_MALL_KEYS 65536
-#endif
-static void attn512_plan(int B, int heads, int Nq, int Nk, int* nsplit, int* keys_per_split) {
-    const int64_t base = (int64_t)((Nq + 127) / 128) * B * heads;
-    int ns = 1;
-    if (base < 192) {
-        ns = (int)((256 + base - 1) / base);
-        const int cap = Nk / 256 > 1 ? Nk / 256 : 1;   // at least 8 key tiles per range
-        if (ns > cap) ns = cap;
-        if (ns > 16) ns = 16;
-    }
-    if (A5B_MALL_KEYS > 0 && Nk > A5B_MALL_KEYS + A5B_MALL_KEYS / 2) {
-        const int nm = (Nk + A5B_MALL_KEYS - 1) / A5B_MALL_KEYS;
-        if (nm > ns) ns = nm;
-    }
-    int kps = ((Nk + ns - 1) / ns + 31) / 32 * 32;
-    *keys_per_split = kps;
-    *nsplit = (Nk + kps - 1) / kps;
+// ---------------------------------------------------------------------------------------
+// entry points: validate -> plan (rsvld_plan.h) -> launch the plan's row of ATTN_TABLE
+// ---------------------------------------------------------------------------------------
+namespace {
+struct AttnLaunch {
+    AttnArgs a;
+    rsvld_plan::AttnPlan pl;
+    float *part_o, *part_ml;   // the split-KV partials in ws (D = 512)
+    hipStream_t s;
+    dim3 grid() const { return dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z); }
+};
+template <auto KERN, int THREADS, int SMEM> int attn_go64(const AttnLaunch& l) {
+    if constexpr (SMEM > 0)
+        if (rsvld_smem_once<KERN>(SMEM) != hipSuccess) return RSVLD_ELAUNCH;
+    hipLaunchKernelGGL(KERN, l.grid(), dim3(THREADS), SMEM, l.s, l.a);
+    return rsvld_check_launch();
+}
+template <auto KERN, auto COMBINE, int SMEM> int attn_go512(const AttnLaunch& l) {
+    if (rsvld_smem_once<KERN>(SMEM) != hipSuccess) return RSVLD_ELAUNCH;
+    hipLaunchKernelGGL(KERN, l.grid(), dim3(256), SMEM, l.s, l.a, l.pl.keys_per_split, l.part_o, l.part_ml);
+    if (l.pl.nsplit > 1)
+        hipLaunchKernelGGL(COMBINE, dim3((unsigned)l.a.Nq, (unsigned)(l.a.B * l.a.heads)), dim3(128), 0, l.s, l.a, l.pl.nsplit, l.part_o, l.part_ml);
+    return rsvld_check_launch();
+}
+// the launch table, indexed [RSVLD_ATTN_ROW_* - 1][dtype]: every instantiation is named here and nowhere else
+#define ATTN_ROW64(KERN, THREADS, SMEM) {attn_go64<KERN<f16>, THREADS, SMEM>, attn_go64<KERN<bf16>, THREADS, SMEM>}
+#define ATTN_ROW512(SMEM, ...) {attn_go512<__VA_ARGS__<f16>, attn_combine_kernel<f16>, SMEM>, attn_go512<__VA_ARGS__<bf16>, attn_combine_kernel<bf16>, SMEM>}
+template <typename T> constexpr auto attn_d64b_nw4 = attn_d64b_kernel<T, 4>;
+template <typename T> constexpr auto attn_d64b_nw8 = attn_d64b_kernel<T, 8>;
+template <typename T> constexpr auto attn_d512b_two = attn_d512b_kernel<T, false>;
+template <typename T> constexpr auto attn_d512b_shared = attn_d512b_kernel<T, true>;
+int (*const ATTN_TABLE[6][2])(const AttnLaunch&) = {
+    ATTN_ROW64(attn_d64b_nw4, 256, 0),                  // RSVLD_ATTN_ROW_D64B_NW4 (static LDS)
+    ATTN_ROW64(attn_d64b_nw8, 512, 0),                  // RSVLD_ATTN_ROW_D64B_NW8
+    ATTN_ROW64(attn_d64c_kernel, 512, A6C_SMEM),        // RSVLD_ATTN_ROW_D64C
+    ATTN_ROW512(A5B_SMEM, attn_d512b_two),              // RSVLD_ATTN_ROW_D512B
+    ATTN_ROW512(A5B_SMEM_SH, attn_d512b_shared),        // RSVLD_ATTN_ROW_D512B_SHARED
+    ATTN_ROW512(A5D_SMEM, attn_d512d_kernel),           // RSVLD_ATTN_ROW_D512D
+};
+}  // namespace
+
+extern "C" int rsvld_plan_attention(int B, int heads, int Nq, int Nk, int D, int plan_div, int tune, int shared_kv, int64_t k_tok_stride,
+                                    int64_t v_tok_stride, rsvld_attention_plan* plan) {
+    if (plan == nullptr) return RSVLD_EINVAL;
+    return rsvld_plan::plan_attention(B, heads, Nq, Nk, D, plan_div, tune, shared_kv != 0, k_tok_stride, v_tok_stride, plan);
 }
 
 extern "C" int64_t rsvld_attention_ws_bytes(int B, int heads, int Nq, int Nk, int D, int plan_div) {
-    if (D != 512 || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return 0;
-    int ns, kps;
-    attn512_plan(plan_div > 1 ? (B + plan_div - 1) / plan_div : B, heads, Nq, Nk, &ns, &kps);
-    if (ns == 1) return 0;
-    return (int64_t)ns * B * heads * Nq * (512 + 2) * 4;
+    rsvld_plan::AttnPlan pl;
+    return rsvld_plan::plan_attention(B, heads, Nq, Nk, D, plan_div, 0, false, 0, 0, &pl) == RSVLD_OK ? pl.ws_bytes : 0;
 }
 
 extern "C" int rsvld_attention_tuned(const void* q, const void* k, const void* v, void* out, int B, int heads, int Nq, int Nk,
@@ -847,69 +857,25 @@ extern "C" int rsvld_attention_tuned(const void* q, const void* k, const void* v
     if ((q_tok_stride | k_tok_stride | v_tok_stride | o_tok_stride | q_batch_stride | k_batch_stride | v_batch_stride |
          o_batch_stride) & 7)
         return RSVLD_EINVAL;
-    if (heads > 65535 || B > 65535) return RSVLD_EINVAL;
-    AttnArgs a;
+    AttnLaunch l;
+    AttnArgs& a = l.a;
     a.q = q; a.k = k; a.v = v; a.out = out;
     a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.D = D;
     a.q_bs = q_batch_stride; a.q_ts = q_tok_stride; a.k_bs = k_batch_stride; a.k_ts = k_tok_stride;
     a.v_bs = v_batch_stride; a.v_ts = v_tok_stride; a.o_bs = o_batch_stride; a.o_ts = o_tok_stride;
     a.scale_log2e = scale * 1.4426950408889634f;
     a.dbg = (A6B_STAMP && D == 64) ? (unsigned long long*)ws : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    if (D == 512) {
-        int ns, kps;   // the key split (an accumulation-order choice) is planned on ONE of the plan_div stacked units
-        attn512_plan(plan_div > 1 ? (B + plan_div - 1) / plan_div : B, heads, Nq, Nk, &ns, &kps);
-        if (ns > 1 && ws == nullptr) return RSVLD_EINVAL;
-        float* part_o = (float*)ws;
-        float* part_ml = ns > 1 ? part_o + (int64_t)ns * B * heads * Nq * 512 : nullptr;
-        dim3 grid((unsigned)((Nq + 127) / 128), (unsigned)ns, (unsigned)(B * heads));
-        // keys and values are one tensor (see the SH note above): the shared-tile instantiation
-        const bool shared = k == v && k_batch_stride == v_batch_stride && k_tok_stride == v_tok_stride;
-        auto go = [&](auto kern, auto comb, int smem) -> int {
-            static const hipError_t attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (attr != hipSuccess) return RSVLD_ELAUNCH;
-            hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a, kps, part_o, part_ml);
-            if (ns > 1) hipLaunchKernelGGL(comb, dim3((unsigned)Nq, (unsigned)(B * heads)), dim3(128), 0, s, a, ns, part_o, part_ml);
-            return rsvld_check_launch();
-        };
-        // shared tile: the head-dimension split of PV (attn_d512d) unless tune asks for the row-owning form; the two agree bit
-        // for bit (tests/test_gpu_attn_d512_dsplit.py)
-        if (shared && tune != RSVLD_ATTN_D512_ROWS)
-            return dtype == RSVLD_F16 ? go(attn_d512d_kernel<f16>, attn_combine_kernel<f16>, A5D_SMEM)
-                                      : go(attn_d512d_kernel<bf16>, attn_combine_kernel<bf16>, A5D_SMEM);
-        if (shared)
-            return dtype == RSVLD_F16 ? go(attn_d512b_kernel<f16, true>, attn_combine_kernel<f16>, A5B_SMEM_SH)
-                                      : go(attn_d512b_kernel<bf16, true>, attn_combine_kernel<bf16>, A5B_SMEM_SH);
-        return dtype == RSVLD_F16 ? go(attn_d512b_kernel<f16, false>, attn_combine_kernel<f16>, A5B_SMEM)
-                                  : go(attn_d512b_kernel<bf16, false>, attn_combine_kernel<bf16>, A5B_SMEM);
-    }
-    if (D == 64) {
-        // tune (RSVLD_ATTN_D64_*: tests and A/B runs) overrides the choice between the two d = 64 kernels, which agree bit for
-        // bit on every shape; 0 = by grid size
-        const char force = tune == RSVLD_ATTN_D64_FOUR_WAVE ? 'b' : tune == RSVLD_ATTN_D64_PINGPONG ? 'c' : 0;
-        const int64_t wg_c = (int64_t)((Nq + 511) / 512) * heads * B;
-        // attn_d64c forms 32-bit lane offsets of up to 64 key rows: a token stride of ~16 M elements or more would wrap
-        const bool c_strides_ok = 64 * k_tok_stride * 2 < ((int64_t)1 << 32) && 64 * v_tok_stride * 2 < ((int64_t)1 << 32);
-        if (force == 'c' && !c_strides_ok) return RSVLD_EUNSUPPORTED;
-        if (c_strides_ok && (a.dbg == nullptr || force == 'c') && force != 'b' && Nk > 64 && ((wg_c >= A6C_MIN_WG && Nk >= A6C_MIN_KEYS) || force == 'c')) {   // long query sequences: the ping-pong kernel
-            dim3 grid((unsigned)((Nq + 511) / 512), (unsigned)heads, (unsigned)B);
-            static const hipError_t attr16 = hipFuncSetAttribute((const void*)attn_d64c_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, A6C_SMEM);
-            static const hipError_t attrbf = hipFuncSetAttribute((const void*)attn_d64c_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, A6C_SMEM);
-            if (attr16 != hipSuccess || attrbf != hipSuccess) return RSVLD_ELAUNCH;
-            if (dtype == RSVLD_F16) hipLaunchKernelGGL((attn_d64c_kernel<f16>), grid, dim3(512), A6C_SMEM, s, a);
-            else hipLaunchKernelGGL((attn_d64c_kernel<bf16>), grid, dim3(512), A6C_SMEM, s, a);
-        } else if (Nq >= A6B_NW8_MIN) {   // long query sequences: 8 waves (256 query rows) share each K / V tile
-            dim3 grid((unsigned)((Nq + 255) / 256), (unsigned)heads, (unsigned)B);
-            if (dtype == RSVLD_F16) hipLaunchKernelGGL((attn_d64b_kernel<f16, 8>), grid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((attn_d64b_kernel<bf16, 8>), grid, dim3(512), 0, s, a);
-        } else {
-            dim3 grid((unsigned)((Nq + 127) / 128), (unsigned)heads, (unsigned)B);
-            if (dtype == RSVLD_F16) hipLaunchKernelGGL((attn_d64b_kernel<f16, 4>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_d64b_kernel<bf16, 4>), grid, dim3(256), 0, s, a);
-        }
-        return rsvld_check_launch();
-    }
-    return RSVLD_EUNSUPPORTED;
+    // the stamped diagnostic build runs attn_d64b (the kernel that writes the stamps) unless attn_d64c is forced
+    if (a.dbg != nullptr && tune != RSVLD_ATTN_D64_PINGPONG) tune = RSVLD_ATTN_D64_FOUR_WAVE;
+    // keys and values are one tensor (see the SH note above): the shared-tile instantiations
+    const bool shared = k == v && k_batch_stride == v_batch_stride && k_tok_stride == v_tok_stride;
+    const int rc = rsvld_plan::plan_attention(B, heads, Nq, Nk, D, plan_div, tune, shared, k_tok_stride, v_tok_stride, &l.pl);
+    if (rc != RSVLD_OK) return rc;
+    if (l.pl.nsplit > 1 && ws == nullptr) return RSVLD_EINVAL;
+    l.part_o = (float*)ws;
+    l.part_ml = l.pl.nsplit > 1 ? l.part_o + (int64_t)l.pl.nsplit * B * heads * Nq * 512 : nullptr;
+    l.s = (hipStream_t)stream;
+    return ATTN_TABLE[l.pl.row - 1][dtype == RSVLD_F16 ? 0 : 1](l);
 }
 
 extern "C" int rsvld_attention(const void* q, const void* k, const void* v, void* out, int B, int heads, int Nq, int Nk,

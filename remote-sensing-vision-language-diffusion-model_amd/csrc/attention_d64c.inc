@@ -15,19 +15,12 @@
 //     (PV, redo); its landing is waited for with a counted vmcnt at the end of period i + 1; the buffer it overwrites held tile
 //     i - 1, last read in period i - 1;
 //   * arithmetic IDENTICAL to attn_d64b (same MFMA chains, same exp2 / row-sum order, same sum check and redo), so the two
-//     kernels agree bit for bit and the choice between them (A6C_MIN_WG) is not a numerics decision.
+//     kernels agree bit for bit and the choice between them (A6C_MIN_WG, rsvld_plan.h) is not a numerics decision.
 // ---------------------------------------------------------------------------------------
 #ifndef A6C_ABL
 #define A6C_ABL 0   // diagnostic builds (results WRONG, timing only): 1 no in-loop LDS-DMA request, 2 no exponentials, 4 no row sums,
                     // 8 no softmax at all (V segment = V reads only), 16 no MFMAs in the M segment
 #endif
-#ifndef A6C_MIN_WG
-#define A6C_MIN_WG 1024   // the ping-pong kernel is used when its grid (512 query rows per workgroup, one workgroup per CU) has at
-#endif                    // least this many workgroups (4 rounds of the 256 CUs): measured +2.3 % at 2 x 20 heads x 16 384 tokens (1 280
-                          // workgroups), +4.5 % at 2 x 10 x 65 536 (2 560); 25 % SLOWER at 2 x 10 x 4 096 (160 workgroups)
-#ifndef A6C_MIN_KEYS
-#define A6C_MIN_KEYS 512   // ... and at least this many keys: on the 77-key cross-attention of the same token counts attn_d64b is faster
-#endif                     // (70 vs 89 us at 2 x 20 x 16 384 queries, 158 vs 178 at 2 x 10 x 65 536: prologue and tail are all there is)
 // MODE 0: C = 0 (first step of a chain, behind a VALU write), 1: accumulate, 2: accumulate behind a VALU write
 template <typename T, int MODE>
 __device__ __forceinline__ void a6c_mma(f32x16& acc, const typename Mfma<T>::v8& a, const typename Mfma<T>::v8& b) {

@@ -859,12 +859,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_halo32_kernel(HaloArgs p) {
     halo_epilogue<T, BN, TM, TN, NW, SEG>(p, smem, acc, tid, wm, wn, l31, lh, x0, y0, n0, img, tx, ty);
 }
 
-// one-time registration of a kernel's dynamic LDS size, keyed on the KERNEL (see conv_igemm.hip: a generic lambda's static is shared by
-// every kernel of one function type -- here the NORM and the K-segment variants of a tile)
-template <auto KERN> hipError_t halo_smem_once(int smem) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return attr;
-}
 #define HALO_K(...) std::integral_constant<void (*)(HaloArgs), &__VA_ARGS__>{}
 
 template <typename T, int BN, int NW>
@@ -880,7 +874,7 @@ int launch_halo32(HaloArgs a, hipStream_t s) {
     if (nwg >= ((int64_t)1 << 31)) return RSVLD_EUNSUPPORTED;
     auto go = [&](auto kern_c) -> int {
         constexpr auto kern = decltype(kern_c)::value;
-        if (halo_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;   // one-time, thread-safe, per KERNEL
+        if (rsvld_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;   // per KERNEL: the NORM and the K-segment variants of a tile share a function type
         hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * NW), smem, s, a);
         return rsvld_check_launch();
     };
@@ -910,7 +904,7 @@ int launch_halo(const HaloArgs& a, hipStream_t s) {
     if (nwg >= ((int64_t)1 << 31)) return RSVLD_EUNSUPPORTED;
     auto go = [&](auto kern_c) -> int {
         constexpr auto kern = decltype(kern_c)::value;
-        if (halo_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;
+        if (rsvld_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;
         hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), smem, s, a);
         return rsvld_check_launch();
     };

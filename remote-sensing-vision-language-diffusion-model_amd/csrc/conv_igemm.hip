@@ -475,13 +475,6 @@ __global__ __launch_bounds__(256 * KS) void conv_igemm_kernel(ConvArgs p) {
     }
 }
 
-// one-time registration of a kernel's dynamic LDS size: a function-local static of an instantiation keyed on the KERNEL (a generic
-// lambda's static would be shared by every kernel of one function type: the plain and the multi-segment instantiations of a tile)
-template <auto KERN> hipError_t conv_smem_once(int smem) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return attr;
-}
-
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, bool GLDS, int STAGES = 2, int KS = 1>
 int launch_conv(const ConvArgs& a, hipStream_t s) {
     constexpr int stage = KS * STAGES * (BM + BN) * BK_BYTES;
@@ -490,7 +483,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
     dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)((a.Cout + BN - 1) / BN));
     auto go = [&](auto kern_c) -> int {
         constexpr auto kern = decltype(kern_c)::value;
-        if (conv_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;   // one-time, thread-safe (C++11 magic static), per KERNEL
+        if (rsvld_smem_once<kern>(smem) != hipSuccess) return RSVLD_ELAUNCH;   // per KERNEL: the plain and the multi-segment instantiations of a tile share a function type
         hipLaunchKernelGGL(kern, grid, dim3(256 * KS), smem, s, a);
         return rsvld_check_launch();
     };

@@ -579,9 +579,8 @@ static int attention_f32_launch(bool split, const float* q, const float* k, cons
     a.v_bs = v_batch_stride; a.v_ts = v_tok_stride; a.o_bs = o_batch_stride; a.o_ts = o_tok_stride;
     a.scale = scale;
     const int smem = (32 * (D + 1) + 4 * 16 * 64) * (int)sizeof(float);   // 81 KiB at D = 512
-    static const hipError_t attr0 = hipFuncSetAttribute((const void*)attn_f32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (32 * 513 + 4096) * 4);
-    static const hipError_t attr1 = hipFuncSetAttribute((const void*)attn_f32_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (32 * 513 + 4096) * 4);
-    if (attr0 != hipSuccess || attr1 != hipSuccess) return RSVLD_ELAUNCH;
+    constexpr int smem_max = (32 * 513 + 4096) * 4;   // registered once per kernel, for D = 512
+    if ((split ? rsvld_smem_once<attn_f32_kernel<true>>(smem_max) : rsvld_smem_once<attn_f32_kernel<false>>(smem_max)) != hipSuccess) return RSVLD_ELAUNCH;
     dim3 grid((unsigned)((Nq + 31) / 32), (unsigned)heads, (unsigned)B);
     if (split) hipLaunchKernelGGL(attn_f32_kernel<true>, grid, dim3(256), smem, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(attn_f32_kernel<false>, grid, dim3(256), smem, (hipStream_t)stream, a);

@@ -1063,12 +1063,10 @@ extern "C" int rsvld_debug_gemm_stamps(void* dst, size_t bytes) {
 // Eligibility + launch, called from rsvld_conv2d_nhwc for 1x1 / stride-1 / single-source layers.
 // Returns RSVLD_EUNSUPPORTED when the shape should stay on the implicit-GEMM kernel.
 namespace {
-// one launch helper per KERNEL (a non-type template parameter): the one-time registration of the dynamic LDS size is a
-// function-local static of THIS instantiation (a generic lambda's static would be shared by every kernel of one function type)
+// one launch helper per KERNEL (a non-type template parameter, as rsvld_smem_once wants it)
 template <auto KERN, int SMEM>
 int gemm_go(dim3 grid, hipStream_t s, const GemmArgs& a) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (attr != hipSuccess) return RSVLD_ELAUNCH;
+    if (rsvld_smem_once<KERN>(SMEM) != hipSuccess) return RSVLD_ELAUNCH;
     hipLaunchKernelGGL(KERN, grid, dim3(512), SMEM, s, a);
     return rsvld_check_launch();
 }

@@ -718,11 +718,8 @@ bool launch_partials(const void* x, const void* x2, typename In::part* part, int
                      hipStream_t s) {
     typedef typename In::in T;
     const size_t lds = GnGeom(C1, C2).lds_bytes(In::PIVOT);
-    if (lds > 65536) {   // C > 5 460 with pivots: more than the 64 KiB of dynamic LDS a kernel gets unasked
-        static const hipError_t lds_attr = hipFuncSetAttribute((const void*)gn_partial_kernel<In>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                               (int)GnGeom(8192, 0).lds_bytes(In::PIVOT));
-        if (lds_attr != hipSuccess) return false;
-    }
+    // C > 5 460 with pivots: more than the 64 KiB of dynamic LDS a kernel gets unasked; registered once, with the maximum (C = 8192)
+    if (lds > 65536 && rsvld_smem_once<gn_partial_kernel<In>>((int)GnGeom(8192, 0).lds_bytes(In::PIVOT)) != hipSuccess) return false;
     hipLaunchKernelGGL(gn_partial_kernel<In>, dim3(pl.nchunks, B), dim3(256), lds, s, (const T*)x,
                        (const T*)x2, part, HW, C1, C2, groups, pl.rows_per_chunk, pl.nchunks);
     return true;

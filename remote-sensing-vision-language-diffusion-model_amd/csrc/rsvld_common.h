@@ -175,4 +175,12 @@ static inline int rsvld_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? RSVLD_OK : RSVLD_ELAUNCH;
 }
+// One-time registration of a kernel's dynamic LDS size (above the 64 KiB a kernel gets unasked), the only hipFuncSetAttribute of the
+// library: a function-local static (thread-safe, C++11) of an instantiation keyed on the KERNEL, a non-type template parameter.  A
+// static inside a generic lambda or a function that takes the kernel as an ARGUMENT is shared by every kernel of one function type,
+// so only the first of them launched in a process would ever be registered.
+template <auto KERN> hipError_t rsvld_smem_once(int smem) {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    return attr;
+}
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -1,7 +1,7 @@
 // rsvld_plan.h — which kernel runs for a layer, decided in ONE place: the planners of conv_igemm.hip (implicit GEMM), gemm.hip (gemm256),
-// conv_halo.hip and norm.hip (GroupNorm).  Plain host C++: integer arithmetic on a descriptor, no HIP call, no device query, no pointer
+// conv_halo.hip, norm.hip (GroupNorm) and attention.hip.  Plain host C++: integer arithmetic on a descriptor, no HIP call, no device query, no pointer
 // dereference beyond the descriptor (its pointers are compared with NULL only).  Each entry point validates, plans here and launches
-// the plan through a flat table of instantiations; rsvld_plan_conv / rsvld_plan_groupnorm (include/rsvld_hip.h) hand the same plans to the
+// the plan through a flat table of instantiations; rsvld_plan_conv / rsvld_plan_groupnorm / rsvld_plan_attention (include/rsvld_hip.h) hand the same plans to the
 // caller, so that nothing outside this header restates a threshold.
 #pragma once
 #include <stdint.h>
@@ -270,6 +270,85 @@ inline int plan_groupnorm(int dtype, int B, int HW, int C1, int C2, int groups, 
     out->small = gn_small_route(dtype, B, HW, C1, C2, groups) ? 1 : 0;
     out->nchunks = pl.nchunks, out->rows_per_chunk = pl.rows_per_chunk;
     out->rows_in_flight = 256 / gn_threads_per_row((C1 + C2) / 8);
+    return RSVLD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// attention (attention.hip): the kernel, its grid, the split-KV ranges and the workspace of one launch
+// ---------------------------------------------------------------------------------------
+typedef rsvld_attention_plan AttnPlan;
+
+// 8 waves (256 query rows) of attn_d64b share each K / V tile from this many query rows on; the gain is small
+#ifndef A6B_NW8_MIN
+#define A6B_NW8_MIN 16384   // round 2 (one box, 2 x 10 heads): +1.5 % at 65 536 tokens, -0.5 % (noise) at 16 384; with the bias step
+                            // (round 3, 2 x 20 heads at 16 384 tokens): +1.3 % (880 -> 891 TFLOP/s), so 16 384 tokens take it too
+#endif
+#ifndef A6C_MIN_WG
+#define A6C_MIN_WG 1024   // the ping-pong kernel is used when its grid (512 query rows per workgroup, one workgroup per CU) has at
+#endif                    // least this many workgroups (4 rounds of the 256 CUs): measured +2.3 % at 2 x 20 heads x 16 384 tokens (1 280
+                          // workgroups), +4.5 % at 2 x 10 x 65 536 (2 560); 25 % SLOWER at 2 x 10 x 4 096 (160 workgroups)
+#ifndef A6C_MIN_KEYS
+#define A6C_MIN_KEYS 512   // ... and at least this many keys: on the 77-key cross-attention of the same token counts attn_d64b is faster
+#endif                     // (70 vs 89 us at 2 x 20 x 16 384 queries, 158 vs 178 at 2 x 10 x 65 536: prologue and tail are all there is)
+// split-KV plan of the D = 512 kernels: key ranges per workgroup
+//   (a) so that the grid fills the 256 CUs when the query tiles alone cannot;
+//   (b) so that ONE key range stays resident in the 256 MiB Infinity Cache while every query tile streams it.  At
+//       N = 262 144 the key/value tensor is 268 MB (shared tile) or 537 MB: every workgroup re-streamed it from HBM
+//       (rocprofv3 FETCH_SIZE: ~400 GB per launch, ~3 TB/s for the whole 131 ms).  Workgroups are dispatched range-major
+//       (blockIdx.y), so with ranges of A5B_MALL_KEYS keys (64 MiB shared / 128 MiB as two tensors) all the query tiles in
+//       flight read the same range out of the cache; the price is one fp32 partial (O, m, l) per range and the merge pass.
+//       Measured on one box (N = 262 144, shared tile): 1036 TFLOP/s with 64 Ki-key ranges, 1041 without, 1026 with 32 Ki:
+//       the kernel is NOT bound by that HBM stream (its LDS-DMA requests are two tiles ahead), so this buys no time; it is
+//       kept because it takes ~3 TB/s of needless HBM traffic (and its power) out of the dominant Stage-1 kernel.
+#ifndef A5B_MALL_KEYS
+#define A5B_MALL_KEYS 65536
+#endif
+
+// shared: keys and values are ONE tensor (same pointer and strides); k_ts / v_ts: the token strides of k and v in elements (D = 64 only).
+// RSVLD_OK with *p filled; RSVLD_EINVAL / RSVLD_EUNSUPPORTED as rsvld_attention_tuned returns them for these arguments
+inline int plan_attention(int B, int heads, int Nq, int Nk, int D, int plan_div, int tune, bool shared, int64_t k_ts, int64_t v_ts, AttnPlan* p) {
+    *p = AttnPlan{};
+    if (B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || heads > 65535 || B > 65535) return RSVLD_EINVAL;
+    if (D == 512) {
+        // the key split (an accumulation-order choice) is planned on ONE of the plan_div stacked units
+        const int64_t base = (int64_t)((Nq + 127) / 128) * plan_unit(B, plan_div) * heads;
+        int ns = 1;
+        if (base < 192) {
+            ns = (int)((256 + base - 1) / base);
+            const int cap = Nk / 256 > 1 ? Nk / 256 : 1;   // at least 8 key tiles per range
+            if (ns > cap) ns = cap;
+            if (ns > 16) ns = 16;
+        }
+        if (A5B_MALL_KEYS > 0 && Nk > A5B_MALL_KEYS + A5B_MALL_KEYS / 2) {
+            const int nm = (Nk + A5B_MALL_KEYS - 1) / A5B_MALL_KEYS;
+            if (nm > ns) ns = nm;
+        }
+        p->keys_per_split = ((Nk + ns - 1) / ns + 31) / 32 * 32;
+        p->nsplit = (Nk + p->keys_per_split - 1) / p->keys_per_split;
+        if (p->nsplit > 1) p->ws_bytes = (int64_t)p->nsplit * B * heads * Nq * (512 + 2) * 4;   // fp32 partials (O | m, l) per range
+        // shared tile: the head-dimension split of PV (attn_d512d) unless tune asks for the row-owning form; the two agree bit
+        // for bit (tests/test_gpu_attn_d512_dsplit.py)
+        p->row = !shared ? RSVLD_ATTN_ROW_D512B : tune == RSVLD_ATTN_D512_ROWS ? RSVLD_ATTN_ROW_D512B_SHARED : RSVLD_ATTN_ROW_D512D;
+        p->grid_x = (Nq + 127) / 128, p->grid_y = p->nsplit, p->grid_z = B * heads;
+        return RSVLD_OK;
+    }
+    if (D != 64) return RSVLD_EUNSUPPORTED;
+    // tune (RSVLD_ATTN_D64_*: tests and A/B runs) overrides the choice between the two d = 64 kernels, which agree bit for
+    // bit on every shape; 0 = by grid size
+    const char force = tune == RSVLD_ATTN_D64_FOUR_WAVE ? 'b' : tune == RSVLD_ATTN_D64_PINGPONG ? 'c' : 0;
+    const int64_t wg_c = (int64_t)((Nq + 511) / 512) * heads * B;
+    // attn_d64c forms 32-bit lane offsets of up to 64 key rows: a token stride of ~16 M elements or more would wrap
+    const bool c_strides_ok = 64 * k_ts * 2 < ((int64_t)1 << 32) && 64 * v_ts * 2 < ((int64_t)1 << 32);
+    if (force == 'c' && !c_strides_ok) return RSVLD_EUNSUPPORTED;
+    p->nsplit = 1, p->keys_per_split = Nk;
+    int rows = 128;
+    if (c_strides_ok && force != 'b' && Nk > 64 && ((wg_c >= A6C_MIN_WG && Nk >= A6C_MIN_KEYS) || force == 'c'))
+        p->row = RSVLD_ATTN_ROW_D64C, rows = 512;         // long query sequences: the ping-pong kernel
+    else if (Nq >= A6B_NW8_MIN)
+        p->row = RSVLD_ATTN_ROW_D64B_NW8, rows = 256;     // long query sequences: 8 waves (256 query rows) share each K / V tile
+    else
+        p->row = RSVLD_ATTN_ROW_D64B_NW4;
+    p->grid_x = (Nq + rows - 1) / rows, p->grid_y = heads, p->grid_z = B;
     return RSVLD_OK;
 }
 

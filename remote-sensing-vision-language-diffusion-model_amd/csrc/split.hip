@@ -907,8 +907,7 @@ extern "C" int rsvld_attention_split_d64(const void* q, const void* k, const voi
     a.v_bs = v_batch_stride; a.v_ts = v_tok_stride; a.v_pl = v_plane; a.o_bs = o_batch_stride; a.o_ts = o_tok_stride; a.o_pl = o_plane;
     a.scale_log2e = scale * 1.44269504088896340736f;
     a.out_f32 = (out_f32 & 1) ? 1 : 0;
-    static const hipError_t attr = hipFuncSetAttribute((const void*)attn_split_d64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AS_SMEM);
-    if (attr != hipSuccess) return RSVLD_ELAUNCH;
+    if (rsvld_smem_once<attn_split_d64_kernel>(AS_SMEM) != hipSuccess) return RSVLD_ELAUNCH;
     dim3 grid((unsigned)((Nq + 127) / 128), (unsigned)heads, (unsigned)B);
     hipLaunchKernelGGL(attn_split_d64_kernel, grid, dim3(256), AS_SMEM, (hipStream_t)stream, a);
     return rsvld_check_launch();
@@ -929,8 +928,7 @@ extern "C" int rsvld_attention_split_d512_shared(const void* q, const void* x, v
     a.o_bs = o_batch_stride; a.o_ts = o_tok_stride; a.o_pl = o_plane;
     a.scale_log2e = scale * 1.44269504088896340736f;
     a.out_f32 = out_f32 ? 1 : 0;
-    static const hipError_t attr = hipFuncSetAttribute((const void*)attn_split_d512_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, A5S_SMEM);
-    if (attr != hipSuccess) return RSVLD_ELAUNCH;
+    if (rsvld_smem_once<attn_split_d512_kernel>(A5S_SMEM) != hipSuccess) return RSVLD_ELAUNCH;
     hipLaunchKernelGGL(attn_split_d512_kernel, dim3((unsigned)((Nq + 63) / 64), (unsigned)B), dim3(256), A5S_SMEM, (hipStream_t)stream, a);
     return rsvld_check_launch();
 }

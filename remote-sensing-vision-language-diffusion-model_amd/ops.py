@@ -1187,10 +1187,11 @@ def attention(q, k, v, heads, scale=None):
     D = HD // heads
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    for t in (q, k, v):
-        if t.stride(2) != 1:
-            raise L.RsvldError("attention: last dim must be contiguous")
+    (qb, qt, q1), (kb, kt, k1), (vb, vt, v1) = q.stride(), k.stride(), v.stride()    # read once: checks, plan and launch
+    if q1 != 1 or k1 != 1 or v1 != 1:
+        raise L.RsvldError("attention: last dim must be contiguous")
     out = torch.empty((B, Nq, HD), device=q.device, dtype=q.dtype)
+    ob, ot, _ = out.stride()
     lib = L.load()
     flops = 4.0 * B * heads * Nq * Nk * D
     nbytes = (q.shape[0] * Nq * HD * 2 + 2 * B * Nk * HD) * q.element_size()
@@ -1199,19 +1200,24 @@ def attention(q, k, v, heads, scale=None):
             raise L.RsvldError("attention (fp32): q, k, v must all be fp32")
         fn = lib.rsvld_attention_f32_split if _policy() is not None else lib.rsvld_attention_f32
         _launch(f"attention_f32{'_split' if _policy() is not None else ''}_d{D}", flops, nbytes, lambda: L.check(
-            fn(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D,
-               q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-               out.stride(0), out.stride(1), scale, _stream()), "rsvld_attention_f32"))
+            fn(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, qb, qt, kb, kt, vb, vt, ob, ot, scale, _stream()),
+            "rsvld_attention_f32"))
         return out
-    ws_bytes = lib.rsvld_attention_ws_bytes(B, heads, Nq, Nk, D, _CTX.get().plan_div)   # split-KV partials (D = 512, small grids)
+    ctx = _CTX.get()
+    tune = ctx.d64_kernel if D == 64 else ctx.d512_kernel
+    # The library's plan of this launch, asked once: the split-KV partials (D = 512, small grids) are the caller's allocation; a
+    # refused plan asks for no workspace, and the launch below reports the refusal.  Keys and values that are ONE tensor (same
+    # pointer and strides) get the shared-tile kernels.
+    pk, pv = k.data_ptr(), v.data_ptr()
+    plan = L.AttentionPlan()                    # (ctypes passes the structure by reference)
+    lib.rsvld_plan_attention(B, heads, Nq, Nk, D, ctx.plan_div, tune, pk == pv and kb == vb and kt == vt, kt, vt, plan)
+    ws_bytes = plan.ws_bytes
     ws = torch.empty(ws_bytes, device=q.device, dtype=torch.uint8) if ws_bytes > 0 else None
-    tune = _CTX.get().d64_kernel if D == 64 else _CTX.get().d512_kernel
     # (profiler group: the short cross-attention launches -- 77 text keys -- are a different kernel and a different regime than
     #  the self-attention of the same layer: kept apart so that the roofline of the dominant group describes ONE kind of launch)
     _launch(f"attention_d{D}" + ("_cross" if (D == 64 and Nk != Nq) else ""), flops, nbytes, lambda: L.check(
-        lib.rsvld_attention_tuned(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D,
-                                  q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                  out.stride(0), out.stride(1), scale, _dt(q), _CTX.get().plan_div, _ptr(ws), _stream(), tune),
+        lib.rsvld_attention_tuned(_ptr(q), C.c_void_p(pk), C.c_void_p(pv), _ptr(out), B, heads, Nq, Nk, D, qb, qt, kb, kt, vb, vt,
+                                  ob, ot, scale, _dt(q), ctx.plan_div, _ptr(ws), _stream(), tune),
         "rsvld_attention"))
     if _split_fast() and not f16_group("attn_out"):   # a split-precision network whose to_out wants planes (exact: 11 bits fit hi + lo)
         return _f16_to_planes(out)

@@ -47,7 +47,8 @@ def test_conv_desc_matches_header_layout():
     assert [f for _, f in _header_fields("rsvld_conv_desc")] == [f[0] for f in _lib.ConvDesc._fields_]
     # the outputs of the host-only plan queries: field order AND integer width (Python reads them)
     widths = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
-    for name, struct in (("rsvld_conv_plan", _lib.ConvPlan), ("rsvld_groupnorm_plan", _lib.GroupnormPlan)):
+    for name, struct in (("rsvld_conv_plan", _lib.ConvPlan), ("rsvld_groupnorm_plan", _lib.GroupnormPlan),
+                         ("rsvld_attention_plan", _lib.AttentionPlan)):
         assert [(f, widths[t]) for t, f in _header_fields(name)] == list(struct._fields_), name
 
 
@@ -66,6 +67,8 @@ def test_constants_match_header():
             "RSVLD_TUNE_REG_STAGING": _lib.TUNE_REG_STAGING, "RSVLD_TUNE_HALO_NW4": _lib.TUNE_HALO_NW4,
             "RSVLD_TUNE_HALO_NW8": _lib.TUNE_HALO_NW8, "RSVLD_TUNE_NO_GEMM256": _lib.TUNE_NO_GEMM256,
             "RSVLD_TUNE_GEMM_ONE_TILE": _lib.TUNE_GEMM_ONE_TILE, "RSVLD_TUNE_F32_SPLIT": _lib.TUNE_F32_SPLIT}
+    want.update({"RSVLD_ATTN_ROW_" + k.upper(): v for k, v in _lib.ATTN_ROW.items()})
+    assert sum(k.startswith("RSVLD_ATTN_ROW_") for k in defs) == len(_lib.ATTN_ROW)
     for k, v in want.items():
         assert defs.get(k) == v, (k, defs.get(k), v)
     flags = [v for k, v in defs.items() if k.startswith("RSVLD_TUNE_") and k not in ("RSVLD_TUNE_TILE_MASK", "RSVLD_TUNE_STAGES_SHIFT")]

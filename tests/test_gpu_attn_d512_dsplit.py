@@ -6,6 +6,8 @@ rescale factors and row sums, so which one runs is a speed decision only (includ
 import pytest
 import torch
 
+from test_gpu_kernels import attn_plan
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
@@ -14,13 +16,14 @@ DTYPES = [torch.float16, torch.bfloat16]
 # per image; split-KV (small query grids) and unsplit (>= 192 query tiles); spike = a key block of large norm in the middle of
 # the sequence, so that the deferred running max of the rows that see it moves there (alpha != 1 on a late tile)
 CASES = [
-    (1, 4096, 4096, 1, False),          # split-KV, 8 ranges
+    (1, 4096, 4096, 1, False),          # split-KV
     (1, 65536, 65536, 1, True),         # unsplit (512 query tiles), late max move
-    (1, 1000, 262144, 1, True),         # 262 144 keys in 16 ranges, Nq % 128 != 0
+    (1, 1000, 262144, 1, True),         # 262 144 keys, Nq % 128 != 0
     (1, 300, 4096 + 17, 1, True),       # ragged last tile in the last range
     (1, 24576 + 77, 2048 + 5, 1, False),  # unsplit with a ragged last tile and a partial query tile
     (2, 640, 8192 + 31, 2, True),       # B = 2 planned per image (plan_div 2)
 ]
+RANGES = [8, 1, 16, 15, 1, 16]          # key ranges of each case: what the library's plan must say (asked in the test)
 
 
 @pytest.fixture
@@ -44,6 +47,9 @@ def _run(q, x, kernel, plan_div):
 @pytest.mark.parametrize("B,Nq,Nk,plan_div,spike", CASES)
 def test_attention_d512_dsplit_equals_rows_kernel_bit_for_bit(cuda, dtype, B, Nq, Nk, plan_div, spike):
     D = 512
+    for tune, row in ((0, "d512d"), (5, "d512d"), (4, "d512b_shared")):     # RSVLD_ATTN_D512_*: default, dsplit, rows
+        plan = attn_plan(B, 1, Nq, Nk, D, plan_div=plan_div, tune=tune, shared=True)
+        assert (plan.name, plan.nsplit) == (row, RANGES[CASES.index((B, Nq, Nk, plan_div, spike))])
     g = torch.Generator().manual_seed(Nq * 7 + Nk)
     q = torch.randn(B, Nq, D, generator=g)
     x = torch.randn(B, Nk, D, generator=g)

@@ -11,8 +11,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from test_gpu_kernels import attn_plan
+
 pytestmark = pytest.mark.gpu
 TOL = 4e-3
+D64_PINGPONG_SHAPE = (1, 8, 65536, 65536)    # (B, heads, Nq, Nk) of the d = 64 test below
 
 
 def _host_attention_rows(q_rows, k, v, scale):
@@ -28,6 +31,8 @@ def test_attention_d512_262144_keys_vs_host_fp32(cuda, shared):
     + combine; two-tensor and shared-tile instantiations."""
     from rsvld_amd import ops
     N, D = 262144, 512
+    plan = attn_plan(1, 1, N, N, D, shared=shared)
+    assert (plan.name, plan.nsplit, plan.keys_per_split) == ("d512d" if shared else "d512b", 4, 65536)
     g = torch.Generator(device="cuda").manual_seed(17 + int(shared))
     # (amplitude 1.5: scores of standard deviation 2.25, i.e. a softmax that a few hundred of the 262 144 keys dominate -- with
     #  near-uniform weights every output would be the mean of V and any kernel would pass)
@@ -47,7 +52,8 @@ def test_attention_d64_65536_tokens_pingpong_grid_vs_host_fp32(cuda):
     """Stage 2 at latent 512, first transformer level: 65 536 tokens; 8 heads x 128 workgroups = the 1 024-workgroup grid from which
     the un-forced dispatch runs the ping-pong kernel attn_d64c (rsvld_attention: tune = 0)."""
     from rsvld_amd import ops
-    N, heads, D = 65536, 8, 64
+    (_, heads, N, _), D = D64_PINGPONG_SHAPE, 64
+    assert attn_plan(1, heads, N, N, D, k_ts=3 * heads * D, v_ts=3 * heads * D).name == "d64c"
     g = torch.Generator(device="cuda").manual_seed(23)
     qkv = (torch.randn(1, N, 3 * heads * D, device=cuda, generator=g) * 1.7).half()    # scores of standard deviation ~2.9: a peaked softmax
     HD = heads * D

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 import guarded as G
-from test_gpu_kernels import CONV_CASES, GEMM_CASES, GN_CASES, HALO_CASES
+from test_gpu_kernels import CONV_CASES, GEMM_CASES, GN_CASES, HALO_CASES, attn_plan
 from test_gpu_matrix_exact import linear_desc, plan_conv
 from test_gpu_split import CONV_CASES as SPLIT_CONV_CASES, LINEAR_CASES as SPLIT_LINEAR_CASES, Q8_CASES, W2_CONV_CASES, W2_LINEAR_CASES
 from test_gpu_f32 import CONV_CASES as F32_CONV_CASES, MODES as F32_MODES
@@ -335,8 +335,12 @@ def _attn_fn(heads, *ctx, scale=None):
     return _under(*ctx)(lambda q, k, v: ops.attention(q, k, v, heads, scale))
 
 
+ATTN64, ATTN512 = [], []     # (form, shape) / (name, shape, kernel, plan_div, shared): walked on the CPU by tests/test_attn_plan_cases.py
+
+
 def _attn64(form, shape, dtypes=(F16,)):
     B, heads, Nq, Nk = shape
+    ATTN64.append((form, shape))
     @case("attention", f"d64{form}_B{B}h{heads}_{Nq}x{Nk}", ("attention",), dtypes)
     def build(dev, dt):
         return dict(fn=_attn_fn(heads, lambda: _d64(form)), operands=_attn_operands(dev, dt, B, heads, Nq, Nk, 64), prefix="attention_d64")
@@ -350,21 +354,34 @@ for _form in ("b", "c"):       # the two bit-identical d = 64 forms: each has it
     _attn64(_form, (1, 2, 256, 256))               # exact tiles, q | k | v slices of one fused tensor
 
 
-def _attn512(name, shape, dtypes=(F16,), kernel="", plan=1, workspace=False, **okw):
+def attn512_plan(name, shape, kernel, plan, shared):
+    """The library's plan of an ``_attn512`` case, checked against what the case's NAME claims: ``split_kv`` = key ranges merged from a
+    workspace, ``unsplit`` = one range and no workspace."""
     B, Nq, Nk = shape
+    pl = attn_plan(B, 1, Nq, Nk, 512, plan_div=plan, tune={"rows": 4, "dsplit": 5, "": 0}[kernel], shared=shared)
+    assert (pl.nsplit > 1) == (pl.ws_bytes > 0)
+    if "split_kv" in name or "unsplit" in name:
+        assert (pl.nsplit > 1) == ("split_kv" in name), (name, pl.nsplit)
+    return pl
+
+
+def _attn512(name, shape, dtypes=(F16,), kernel="", plan=1, shared=False, **okw):
+    B, Nq, Nk = shape
+    ATTN512.append((name, shape, kernel, plan, shared))
     @case("attention", f"d512_{name}_B{B}_{Nq}x{Nk}", ("attention",), dtypes)
     def build(dev, dt):
         from rsvld_amd import ops
-        return dict(fn=_attn_fn(1, lambda: _d512(kernel), lambda: ops.plan_units(plan)), operands=_attn_operands(dev, dt, B, 1, Nq, Nk, 512, **okw),
-                    expect="attention_d512", workspace=workspace)
+        # a plan with key ranges is a case about its workspace as well: the partials are a guarded allocation
+        return dict(fn=_attn_fn(1, lambda: _d512(kernel), lambda: ops.plan_units(plan)), operands=_attn_operands(dev, dt, B, 1, Nq, Nk, 512, shared=shared, **okw),
+                    expect="attention_d512", workspace=attn512_plan(name, shape, kernel, plan, shared).ws_bytes > 0)
 
 
 _attn512("two_tensor_fused_qkv", (2, 144, 144), (F16, BF16))             # q | k | v slices, token stride 1536
 _attn512("two_tensor_ragged", (1, 100, 333), (F16, BF16))                # k | v fused, 13 keys in the last tile
-_attn512("two_tensor_split_kv_ragged_last_range", (1, 300, 2500), workspace=True)        # split-KV: the partials workspace is a guarded allocation, the last key range is short
+_attn512("two_tensor_split_kv_ragged_last_range", (1, 300, 2500))        # split-KV: the partials workspace is a guarded allocation, the last key range is short
 _attn512("one_query_one_key", (1, 1, 1))
 _attn512("shared_tile_ragged", (1, 33, 95), (F16, BF16), shared=True)    # attn_d512b with the shared K = V tile, read row-wise and transposed
-_attn512("shared_tile_split_kv_ragged_last_range", (1, 300, 2500), shared=True, workspace=True)
+_attn512("shared_tile_split_kv_ragged_last_range", (1, 300, 2500), shared=True)
 _attn512("shared_tile_rows_kernel", (1, 300, 4096 + 17), shared=True, kernel="rows")
 _attn512("shared_tile_dsplit_kernel", (1, 300, 4096 + 17), (F16, BF16), shared=True, kernel="dsplit")   # attn_d512d: P exchanged through LDS
 _attn512("shared_tile_dsplit_unsplit_partial_query_tile", (1, 24576 + 77, 2048 + 5), shared=True, kernel="dsplit")

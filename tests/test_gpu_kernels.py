@@ -387,13 +387,29 @@ def test_layer_norm(cuda, dtype, Cc):
     _close(got, F.layer_norm(x, (Cc,), gamma, beta, 1e-5), dtype)
 
 
+def attn_plan(B, heads, Nq, Nk, D, plan_div=1, tune=0, shared=False, k_ts=0, v_ts=0):
+    """The library's own plan of a 16-bit attention launch (rsvld_plan_attention: host code, no device) -> L.AttentionPlan, with the
+    name of its ``row`` in L.ATTN_ROW as ``name``.  ``shared``: keys = values = one tensor; ``k_ts`` / ``v_ts``: their token strides."""
+    from rsvld_amd import _lib as L
+    plan = L.AttentionPlan()
+    rc = L.load().rsvld_plan_attention(B, heads, Nq, Nk, D, plan_div, tune, shared, k_ts, v_ts, plan)
+    assert rc == 0, rc
+    plan.name = {v: k for k, v in L.ATTN_ROW.items()}[plan.row]
+    return plan
+
+
+# (B, Nq, Nk) of one d = 512 head -> key ranges of the split-KV plan (1: no split); the last range of (1, 300, 2500) is ragged
+ATTN_D512_SHAPES = {(1, 64, 64): 1, (2, 144, 144): 1, (1, 1, 1): 1, (1, 100, 333): 1, (2, 1024, 1024): 4, (24, 1000, 160): 1, (1, 300, 2500): 9}
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [(1, 64, 64), (2, 144, 144), (1, 1, 1), (1, 100, 333), (2, 1024, 1024), (24, 1000, 160),
-                                   (1, 300, 2500)])   # split-KV (4 and 9 key ranges), no split, ragged last range
+@pytest.mark.parametrize("shape", list(ATTN_D512_SHAPES))
 def test_attention_d512(cuda, dtype, shape):
     from rsvld_amd import ops
     B, Nq, Nk = shape
     D = 512
+    plan = attn_plan(B, 1, Nq, Nk, D)
+    assert (plan.name, plan.nsplit) == ("d512b", ATTN_D512_SHAPES[shape])
     g = torch.Generator().manual_seed(Nq * 7 + Nk)
     qkv = _rt(torch.randn(B, max(Nq, Nk), 3 * D, generator=g), dtype)
     q, k, v = qkv[:, :Nq, :D], qkv[:, :Nk, D:2 * D], qkv[:, :Nk, 2 * D:]
@@ -404,9 +420,12 @@ def test_attention_d512(cuda, dtype, shape):
     _close(got, want, dtype)
 
 
+ATTN_D512_SHARED_SHAPES = [(1, 64, 64), (2, 144, 144), (1, 1, 1), (1, 100, 333), (2, 1024, 1024), (3, 1000, 160),
+                           (1, 300, 2500), (1, 2048, 4096), (1, 33, 95)]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [(1, 64, 64), (2, 144, 144), (1, 1, 1), (1, 100, 333), (2, 1024, 1024), (3, 1000, 160),
-                                   (1, 300, 2500), (1, 2048, 4096), (1, 33, 95)])
+@pytest.mark.parametrize("shape", ATTN_D512_SHARED_SHAPES)
 def test_attention_d512_shared_kv_tile(cuda, dtype, shape):
     """Keys and values are ONE tensor (k is v): the shared-tile instantiation -- one LDS image read row-wise for S and
     transposed for P V, three-buffer ring (1, 2, 3+ tiles; ragged tails; split-KV ranges)."""
@@ -418,6 +437,7 @@ def test_attention_d512_shared_kv_tile(cuda, dtype, shape):
     x = _rt(torch.randn(B, Nk, D, generator=g), dtype)
     scale = 1.0 / math.sqrt(D)
     want = torch.softmax(q @ x.transpose(1, 2) * scale, -1) @ x
+    assert attn_plan(B, 1, Nq, Nk, D, shared=True).name == "d512d" and attn_plan(B, 1, Nq, Nk, D).name == "d512b"
     dx = x.to(cuda, dtype)
     got = ops.attention(q.to(cuda, dtype), dx, dx, heads=1, scale=scale)
     _close(got, want, dtype)
@@ -436,9 +456,12 @@ def d64_kernel(request):
     devtools.d64_kernel("")
 
 
+ATTN_D64_SHAPES = [(2, 10, 256, 256), (1, 20, 64, 77), (2, 5, 100, 333), (1, 10, 4096, 4096), (3, 2, 1, 1),
+                   (1, 2, 700, 64), (1, 1, 513, 129), (1, 2, 1100, 192)]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [(2, 10, 256, 256), (1, 20, 64, 77), (2, 5, 100, 333), (1, 10, 4096, 4096), (3, 2, 1, 1),
-                                   (1, 2, 700, 64), (1, 1, 513, 129), (1, 2, 1100, 192)])
+@pytest.mark.parametrize("shape", ATTN_D64_SHAPES)
 def test_attention_d64_multihead(cuda, dtype, shape, d64_kernel):
     """SDXL self / cross attention and ZeroCrossAttn: heads x d=64, keys 77 (text), ragged, 4096 tokens; one, two, three and
     four key tiles (the ping-pong kernel's prologue requests three and its ring holds four)."""
@@ -454,6 +477,38 @@ def test_attention_d64_multihead(cuda, dtype, shape, d64_kernel):
     dkv = kv.to(cuda, dtype)
     got = ops.attention(q.to(cuda, dtype), dkv[..., :heads * D], dkv[..., heads * D:], heads=heads)
     _close(got, want, dtype)
+
+
+# The un-forced d = 64 dispatch at the sizes where it leaves the 4-wave attn_d64b: (B, heads, Nq, Nk), the row of the launch table
+# the library's plan names at tune 0, and the forced form it must equal bit for bit.  The headline's 77-key cross-attention runs the
+# first row; the second case is 26 x 40 = 1 040 workgroups of 512 query rows on 512 keys, just past what attn_d64c asks for.
+ATTN_D64_DEFAULT_CASES = [((1, 1, 16384, 77), "d64b_nw8", "c"), ((2, 20, 13312, 512), "d64c", "b")]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape,row,other", ATTN_D64_DEFAULT_CASES)
+def test_attention_d64_default_route(cuda, dtype, shape, row, other):
+    """The kernel the library chooses by itself (tune 0) against an fp64 softmax on the host -- every query row where that is small,
+    else every 61st -- and against the other d = 64 form, forced: the two agree bit for bit (include/rsvld_hip.h)."""
+    from rsvld_amd import devtools, ops
+    B, heads, Nq, Nk = shape
+    D = 64
+    assert attn_plan(B, heads, Nq, Nk, D, k_ts=2 * heads * D, v_ts=2 * heads * D).name == row
+    g = torch.Generator().manual_seed(Nq + 3 * Nk + heads)
+    q = torch.randn(B, Nq, heads * D, generator=g).to(dtype)
+    kv = torch.randn(B, Nk, 2 * heads * D, generator=g).to(dtype)          # fused k|v projection output
+    rows = torch.arange(0, Nq, 1 if B * heads * Nq * Nk <= 1 << 22 else 61)
+    qh, kh, vh = (t.double().view(B, -1, heads, D).transpose(1, 2) for t in (q[:, rows], kv[..., :heads * D], kv[..., heads * D:]))
+    want = (torch.softmax(qh @ kh.transpose(-1, -2) / 8.0, -1) @ vh).transpose(1, 2).reshape(B, len(rows), heads * D)
+    dq, dkv = q.to(cuda), kv.to(cuda)
+    got = ops.attention(dq, dkv[..., :heads * D], dkv[..., heads * D:], heads=heads)
+    _close(got[:, rows.to(cuda)], want, dtype)
+    try:
+        devtools.d64_kernel(other)
+        forced = ops.attention(dq, dkv[..., :heads * D], dkv[..., heads * D:], heads=heads)
+    finally:
+        devtools.d64_kernel("")
+    assert torch.equal(got, forced)
 
 
 def test_attention_d64_rescale_path(cuda, d64_kernel):

@@ -20,16 +20,17 @@ for (B, heads, N) in [(2, 20, 16384), (2, 10, 65536)]:
     qkv = torch.randn(B, N, 3 * heads * D, device=dev, dtype=torch.float16)
     q, k, v = qkv[..., :heads * D], qkv[..., heads * D:2 * heads * D], qkv[..., 2 * heads * D:]
     out = torch.empty(B, N, heads * D, device=dev, dtype=torch.float16)
-    nw = 8 if N >= 16384 else 4      # A6B_NW8_MIN
-    rows = 64 if PINGPONG else 32
-    nw = 8 if PINGPONG else nw
-    nwg = (N + rows * nw - 1) // (rows * nw) * heads * B
+    tune = 2 if PINGPONG else 1      # RSVLD_ATTN_D64_*: the stamped build runs attn_d64b unless attn_d64c is forced
+    plan = L.AttentionPlan()         # the library's own plan of the launch
+    assert lib.rsvld_plan_attention(B, heads, N, N, D, 1, tune, False, k.stride(1), v.stride(1), plan) == 0
+    nw = {L.ATTN_ROW["d64b_nw4"]: 4, L.ATTN_ROW["d64b_nw8"]: 8, L.ATTN_ROW["d64c"]: 8}[plan.row]
+    nwg = plan.grid_x * plan.grid_y * plan.grid_z
     dbg = torch.zeros(nwg * nw * 8, device=dev, dtype=torch.int64)
     p = lambda t: C.c_void_p(t.data_ptr())
     for _ in range(3):   # the last launch's stamps are read (clock settled)
         rc = lib.rsvld_attention_tuned(p(q), p(k), p(v), p(out), B, heads, N, N, D, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
                                        v.stride(0), v.stride(1), out.stride(0), out.stride(1), C.c_float(D ** -0.5), L.F16, 1, p(dbg),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream), 2 if PINGPONG else 1)
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream), tune)
         assert rc == 0, rc
     torch.cuda.synchronize()
     d = dbg.view(-1, 8).cpu().double()
