@@ -447,6 +447,20 @@ int rsvld_gemv(const void* w, const void* x, const void* bias, void* y, int N, i
  * the unfused sequence has them. */
 int rsvld_gemv_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
                      void* y, int N, int K, int dtype, void* stream);
+/* The weights of those products as OCP e4m3 bytes with ONE power-of-two scale per output row (the opt-in "e4m3" mode of the same token
+ * loop: the loop is bound by weight bytes alone, and these are half of them).  w [N][K] 16-bit (dtype) -> q [N][K] uint8, scale [N] fp32 =
+ * 2^e[n]; e[n] = the smallest integer with amax[n] 2^-e <= 448, amax over the row's finite elements: amax = m 2^x with m in [0.5, 1) gives
+ * e = x - 9 if m <= 0.875, else x - 8 (448 = 0.875 x 2^9); 0 for an all-zero row; clamped to [-126, 127].  q[n][k] = e4m3(w[n][k] 2^-e[n]),
+ * round to nearest even: the scaling is exact and nothing saturates; a non-finite weight becomes 0x7F (e4m3 NaN), so that a corrupt
+ * checkpoint shows as NaN logits.  K % 16 == 0; w and q 16-byte aligned.  Packs the q|k|v, o, gate|up, down projections and lm_head behind
+ * models/util.py:17-66 (llava/model/language_model/llava_llama.py:118-137), once per model. */
+int rsvld_pack_rows_e4m3(const void* w, void* q, float* scale, int N, int K, int dtype, void* stream);
+/* rsvld_gemv_fused on such weights (the same reference call sites): y[n] = T(scale[n] * sum_k q[n][k] x'[k] + bias[n]), then the residual;
+ * x' = x after norm_w / glu exactly as rsvld_gemv_fused stages it (16-bit), fp32 accumulation, the same roundings to the 16-bit type T.
+ * x, bias, norm_w, residual, y are 16-bit (dtype); q [N][K] uint8 and scale [N] fp32 as rsvld_pack_rows_e4m3 writes them.
+ * K % 16 == 0, K <= 32768; q, x and norm_w 16-byte aligned. */
+int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                        const void* residual, int glu, void* y, int N, int K, int dtype, void* stream);
 /* One decode step of grouped-query attention over a static cache (LlamaAttention.forward with ONE new token, llava_llama.py:118-137 ->
  * transformers' Llama decode): qkv [ (n_q + 2 n_kv) x head_dim ] = the new token's q | k | v rows; cos, sin [head_dim] (half-split rotary
  * embedding, 16-bit); *pos (DEVICE int64: the step is replayed from a hipGraph) = the token's position; kcache / vcache

@@ -30,13 +30,15 @@ template <typename T> __device__ __forceinline__ float dot8(const u32x4& w, cons
 //   norm_w != nullptr   x <- T( x * rsqrt(mean(x^2) + eps) * norm_w )         (the RMSNorm in front of q|k|v, gate|up and lm_head)
 //   glu                 x has 2 K elements [gate | up]: x <- T( T(silu(gate)) * up )   (the SwiGLU in front of down_proj)
 //   residual != nullptr y <- T( residual + T(W x + b) )                        (h + o_proj(...), h + down_proj(...))
-// with the roundings of the unfused torch sequence (F.rms_norm, silu(g) * u, h + linear) kept where they were.
-template <typename T, int KS>
-__global__ __launch_bounds__(64 * GV_WAVES) void gemv_kernel(const T* __restrict__ W, const T* __restrict__ x, const T* __restrict__ bias,
-                                                              T* __restrict__ y, int N, int K, const T* __restrict__ norm_w, float eps,
-                                                              const T* __restrict__ residual, int glu) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // x: K elements (+ KS = 4: 4 x GV_RPW partial sums) + 16 floats of reduction scratch
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+// with the roundings of the unfused torch sequence (F.rms_norm, silu(g) * u, h + linear) kept where they were.  gv_stage_x / gv_store are
+// shared by the 16-bit kernel and the e4m3 one (gemv_w8_kernel): one statement of these roundings.
+// gv_stage_x: the activation row into LDS as K elements of T (4 floats of reduction scratch ``red_off`` bytes behind it), closed by a barrier.
+// (Thread indices come from the kernel and the pointers carry no __restrict__: in this form the 16-bit kernels' weight-streaming loops and
+// epilogues compile to the instructions they had with the staging written out in the kernel -- only address arithmetic of the staging itself
+// is ordered differently -- and they time the same; with __restrict__ parameters the row route measured 1 % slower.)
+template <typename T>
+__device__ __forceinline__ void gv_stage_x(char* smem, int red_off, const T* x, const T* norm_w, float eps, int K, int glu,
+                                           const int tid, const int lane, const int w) {
     if (glu) {
         for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) {
             float g[8], u[8];
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(64 * GV_WAVES) void gemv_kernel(const T* __restrict
             *(u32x4*)(smem + i * 2) = pack8<T>(g);
         }
     } else if (norm_w != nullptr) {
-        float* red = (float*)(smem + (size_t)K * 2 + (KS == 4 ? 4 * GV_RPW * sizeof(float) : 0));
+        float* red = (float*)(smem + (size_t)K * 2 + red_off);
         float ss = 0.f;
         for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) {
             float f[8];
@@ -75,11 +77,23 @@ __global__ __launch_bounds__(64 * GV_WAVES) void gemv_kernel(const T* __restrict
         for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) *(u32x4*)(smem + i * 2) = *(const u32x4*)(x + i);
     }
     __syncthreads();
-    auto store = [&](int row, float v) __attribute__((always_inline)) {
-        T r = (T)(v + (bias != nullptr ? (float)bias[row] : 0.f));
-        if (residual != nullptr) r = (T)((float)residual[row] + (float)r);
-        y[row] = r;
-    };
+}
+// gv_store: y[row] = T(v + bias[row]), then the residual
+template <typename T>
+__device__ __forceinline__ void gv_store(T* y, const T* bias, const T* residual, int row, float v) {
+    T r = (T)(v + (bias != nullptr ? (float)bias[row] : 0.f));
+    if (residual != nullptr) r = (T)((float)residual[row] + (float)r);
+    y[row] = r;
+}
+
+template <typename T, int KS>
+__global__ __launch_bounds__(64 * GV_WAVES) void gemv_kernel(const T* __restrict__ W, const T* __restrict__ x, const T* __restrict__ bias,
+                                                              T* __restrict__ y, int N, int K, const T* __restrict__ norm_w, float eps,
+                                                              const T* __restrict__ residual, int glu) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // x: K elements (+ KS = 4: 4 x GV_RPW partial sums) + 16 floats of reduction scratch
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    gv_stage_x<T>(smem, KS == 4 ? 4 * GV_RPW * (int)sizeof(float) : 0, x, norm_w, eps, K, glu, tid, lane, w);
+    auto store = [&](int row, float v) __attribute__((always_inline)) { gv_store<T>(y, bias, residual, row, v); };
     if constexpr (KS == 4) {
         // wave w owns K range [w K/4, (w + 1) K/4) (K % 2048 == 0: whole 512-element steps per wave) of the workgroup's GV_RPW rows
         const int row0 = blockIdx.x * GV_RPW;
@@ -154,6 +168,149 @@ __global__ __launch_bounds__(64 * GV_WAVES) void gemv_kernel(const T* __restrict
     for (int r = 0; r < GV_RPW; ++r) {
         const float v = wave_sum(acc[r]);
         if (lane == 0 && row0 + r < N) store(row0 + r, v);
+    }
+}
+
+// ---- the same product on OCP e4m3 weights with one power-of-two scale per output row (rsvld_gemv_w8_fused): half the bytes of the loop
+// that is bound by nothing else.  y[n] = T(scale[n] * sum_k q[n][k] x'[k] + bias[n]), then the residual; x' is staged exactly as above
+// (gv_stage_x) and the result leaves through gv_store, so the three fused forms round where gemv_kernel rounds them.  A 16-byte piece is
+// now 16 weights: a wave step covers 1 024 elements of K (64 lanes x 16), two steps are in flight per lane and row as above.  Pieces
+// past the end of a wave's K range are skipped per lane (K % 16 == 0: a piece is inside or outside as a whole), which is how both the
+// ragged K of the row route and a K quarter that is no whole number of steps (down_proj: 14 336 / 4 = 3.5 steps) are walked.
+// (Eight rows per wave instead of GV_RPW = 4 -- twice the loads in flight, half the x' staging per weight byte -- measured 2-8 % SLOWER on
+// every decoder shape, A-B-A on one device: the row count stays the 16-bit kernel's.)
+template <typename T> __device__ __forceinline__ float dot16_w8(const u32x4& w, const u32x4& x0, const u32x4& x1, float acc) {
+    float xf[16];
+    unpack8<T>(x0, *(float(*)[8])xf);
+    unpack8<T>(x1, *(float(*)[8])(xf + 8));
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {     // byte j of dword d = element 4 d + j; v_cvt_pk_f32_fp8 takes the low or the high byte pair
+        const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[d], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[d], true);
+        acc = __builtin_fmaf(lo[0], xf[4 * d], acc);
+        acc = __builtin_fmaf(lo[1], xf[4 * d + 1], acc);
+        acc = __builtin_fmaf(hi[0], xf[4 * d + 2], acc);
+        acc = __builtin_fmaf(hi[1], xf[4 * d + 3], acc);
+    }
+    return acc;
+}
+
+// KS = 1: a wave owns GV_RPW rows over all of K; KS = 4: the four waves of a workgroup split K for the workgroup's GV_RPW rows (K % 64 == 0)
+template <typename T, int KS>
+__global__ __launch_bounds__(64 * GV_WAVES) void gemv_w8_kernel(const uint8_t* __restrict__ W, const float* __restrict__ scale, const T* __restrict__ x,
+                                                                 const T* __restrict__ bias, T* __restrict__ y, int N, int K,
+                                                                 const T* __restrict__ norm_w, float eps, const T* __restrict__ residual, int glu) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // as gemv_kernel: x' (K x 16 bit) (+ KS = 4: partial sums) + reduction scratch
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    gv_stage_x<T>(smem, KS == 4 ? 4 * GV_RPW * (int)sizeof(float) : 0, x, norm_w, eps, K, glu, tid, lane, w);
+    const int row0 = KS == 4 ? blockIdx.x * GV_RPW : (blockIdx.x * GV_WAVES + w) * GV_RPW;
+    if (KS == 1 && row0 >= N) return;
+    const uint8_t* wr[GV_RPW];
+#pragma unroll
+    for (int r = 0; r < GV_RPW; ++r) wr[r] = W + (int64_t)min(row0 + r, N - 1) * K;   // rows past N re-read the last row, never stored
+    float acc[GV_RPW];
+#pragma unroll
+    for (int r = 0; r < GV_RPW; ++r) acc[r] = 0.f;
+    const int kq = K >> 2, kend = KS == 4 ? (w + 1) * kq : K;
+    int kb = KS == 4 ? w * kq : 0;
+    for (; kb + 2048 <= kend; kb += 2048) {                     // two whole steps per iteration: 2 x RPW loads in flight per lane
+        const int kk = kb + lane * 16;
+        u32x4 wv[2][GV_RPW];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < GV_RPW; ++r) wv[u][r] = __builtin_nontemporal_load((const u32x4*)(wr[r] + kk + u * 1024));
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const u32x4 x0 = *(const u32x4*)(smem + (kk + u * 1024) * 2), x1 = *(const u32x4*)(smem + (kk + u * 1024) * 2 + 16);
+#pragma unroll
+            for (int r = 0; r < GV_RPW; ++r) acc[r] = dot16_w8<T>(wv[u][r], x0, x1, acc[r]);
+        }
+    }
+    for (; kb < kend; kb += 1024) {                             // the odd step and / or the ragged tail, piece by piece
+        const int kk = kb + lane * 16;
+        if (kk < kend) {
+            u32x4 wv[GV_RPW];
+#pragma unroll
+            for (int r = 0; r < GV_RPW; ++r) wv[r] = __builtin_nontemporal_load((const u32x4*)(wr[r] + kk));
+            const u32x4 x0 = *(const u32x4*)(smem + kk * 2), x1 = *(const u32x4*)(smem + kk * 2 + 16);
+#pragma unroll
+            for (int r = 0; r < GV_RPW; ++r) acc[r] = dot16_w8<T>(wv[r], x0, x1, acc[r]);
+        }
+    }
+    if constexpr (KS == 4) {
+        float* part = (float*)(smem + (size_t)K * 2);
+#pragma unroll
+        for (int r = 0; r < GV_RPW; ++r) {
+            const float v = wave_sum(acc[r]);
+            if (lane == 0) part[w * GV_RPW + r] = v;
+        }
+        __syncthreads();
+        if (tid < GV_RPW && row0 + tid < N) {   // fixed order: wave 0 .. 3
+            const float v = ((part[tid] + part[GV_RPW + tid]) + part[2 * GV_RPW + tid]) + part[3 * GV_RPW + tid];
+            gv_store<T>(y, bias, residual, row0 + tid, v * scale[row0 + tid]);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < GV_RPW; ++r) {
+            const float v = wave_sum(acc[r]);
+            if (lane == 0 && row0 + r < N) gv_store<T>(y, bias, residual, row0 + r, v * scale[row0 + r]);
+        }
+    }
+}
+
+// ---- the quantiser of those weights (rsvld_pack_rows_e4m3): a wave owns a row.  Pass 1: amax over the row's FINITE elements (wave
+// reduction); e = the smallest integer with amax 2^-e <= 448 = 0.875 x 2^9, read off amax's exponent and mantissa bits (amax = m 2^x,
+// m in [0.5, 1): e = x - 9 if m <= 0.875, else x - 8; no logarithm), 0 for an all-zero row, clamped to [-126, 127].  Pass 2 (the row
+// comes back from L2): q = e4m3_rne(w 2^-e) -- an exact scaling, nothing saturates -- and byte 0x7F (e4m3 NaN) for a non-finite weight.
+template <typename T>
+__global__ __launch_bounds__(64 * GV_WAVES) void pack_rows_e4m3_kernel(const T* __restrict__ W, uint8_t* __restrict__ q, float* __restrict__ scale,
+                                                                        int N, int K) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * GV_WAVES + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const T* wr = W + (int64_t)row * K;
+    uint8_t* qr = q + (int64_t)row * K;
+    float amax = 0.f;
+    for (int kk = lane * 16; kk < K; kk += 1024) {
+        float f[16];
+        unpack8<T>(*(const u32x4*)(wr + kk), *(float(*)[8])f);
+        unpack8<T>(*(const u32x4*)(wr + kk + 8), *(float(*)[8])(f + 8));
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float a = fabsf(f[e]);
+            amax = a < INFINITY ? fmaxf(amax, a) : amax;        // (NaN and Inf compare false)
+        }
+    }
+    amax = wave_max(amax);
+    int e = 0;
+    if (amax > 0.f) {
+        const uint32_t b = __builtin_bit_cast(uint32_t, amax);
+        int E = (int)(b >> 23);
+        uint32_t man = b & 0x7FFFFFu;
+        if (E == 0) {                                           // an fp32 subnormal (a bf16 one): normalise
+            const int sh = __builtin_clz(man) - 8;
+            man = (man << sh) & 0x7FFFFFu;
+            E = 1 - sh;
+        }
+        // amax = (1 + man 2^-23) 2^(E - 127) = m 2^x with x = E - 126; m <= 0.875 <=> man <= 0.75 x 2^23
+        e = (E - 126) - (man <= 0x600000u ? 9 : 8);
+        e = min(max(e, -126), 127);
+    }
+    const float inv = e < 127 ? __builtin_bit_cast(float, (uint32_t)(127 - e) << 23) : __builtin_bit_cast(float, 0x00400000u);   // 2^-e
+    if (lane == 0) scale[row] = __builtin_bit_cast(float, (uint32_t)(127 + e) << 23);
+    for (int kk = lane * 16; kk < K; kk += 1024) {
+        float f[16];
+        unpack8<T>(*(const u32x4*)(wr + kk), *(float(*)[8])f);
+        unpack8<T>(*(const u32x4*)(wr + kk + 8), *(float(*)[8])(f + 8));
+        u32x4 out;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            uint32_t v = cvt4_e4m3(f[4 * d] * inv, f[4 * d + 1] * inv, f[4 * d + 2] * inv, f[4 * d + 3] * inv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (!(fabsf(f[4 * d + j]) < INFINITY)) v = (v & ~(0xFFu << (8 * j))) | (0x7Fu << (8 * j));
+            out[d] = v;
+        }
+        *(u32x4*)(qr + kk) = out;
     }
 }
 
@@ -360,6 +517,43 @@ extern "C" int rsvld_gemv(const void* w, const void* x, const void* bias, void* 
 extern "C" int rsvld_gemv_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
                                 void* y, int N, int K, int dtype, void* stream) {
     return gemv_launch(w, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, dtype, stream);
+}
+
+extern "C" int rsvld_pack_rows_e4m3(const void* w, void* q, float* scale, int N, int K, int dtype, void* stream) {
+    if (!w || !q || !scale || N <= 0 || K <= 0) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % 16 != 0) return RSVLD_EUNSUPPORTED;   // 16-byte pieces of q
+    if ((((uintptr_t)w | (uintptr_t)q) & 15) || ((uintptr_t)scale & 3)) return RSVLD_EINVAL;
+    const dim3 grid((unsigned)((N + GV_WAVES - 1) / GV_WAVES));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == RSVLD_F16) hipLaunchKernelGGL((pack_rows_e4m3_kernel<f16>), grid, dim3(64 * GV_WAVES), 0, s, (const f16*)w, (uint8_t*)q, scale, N, K);
+    else hipLaunchKernelGGL((pack_rows_e4m3_kernel<bf16>), grid, dim3(64 * GV_WAVES), 0, s, (const bf16*)w, (uint8_t*)q, scale, N, K);
+    return rsvld_check_launch();
+}
+
+extern "C" int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                                   const void* residual, int glu, void* y, int N, int K, int dtype, void* stream) {
+    if (!q || !scale || !x || !y || N <= 0 || K <= 0) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % 16 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // 16-byte pieces of 16 weights; x' + scratch as gemv_launch
+    if ((((uintptr_t)q | (uintptr_t)x | (uintptr_t)norm_w) & 15) || ((uintptr_t)scale & 3)) return RSVLD_EINVAL;
+    if (glu && (norm_w != nullptr || (((uintptr_t)x + (uintptr_t)K * 2) & 15))) return RSVLD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    // as gemv_launch: few rows (fewer than ~4 row-split workgroups per CU) split K over the four waves -- here for every K whose quarter is
+    // whole 16-element pieces (K % 64 == 0) and at least two wave steps long in all (K >= 2 048)
+    const bool ksplit = K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024;
+    const dim3 grid(ksplit ? (unsigned)((N + GV_RPW - 1) / GV_RPW) : (unsigned)((N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW)));
+    const size_t smem = (size_t)K * 2 + (ksplit ? 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
+    const uint8_t* qw = (const uint8_t*)q;
+    glu = glu ? 1 : 0;
+    if (dtype == RSVLD_F16) {
+        if (ksplit) hipLaunchKernelGGL((gemv_w8_kernel<f16, 4>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const f16*)x, (const f16*)bias, (f16*)y, N, K, (const f16*)norm_w, norm_eps, (const f16*)residual, glu);
+        else hipLaunchKernelGGL((gemv_w8_kernel<f16, 1>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const f16*)x, (const f16*)bias, (f16*)y, N, K, (const f16*)norm_w, norm_eps, (const f16*)residual, glu);
+    } else {
+        if (ksplit) hipLaunchKernelGGL((gemv_w8_kernel<bf16, 4>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const bf16*)x, (const bf16*)bias, (bf16*)y, N, K, (const bf16*)norm_w, norm_eps, (const bf16*)residual, glu);
+        else hipLaunchKernelGGL((gemv_w8_kernel<bf16, 1>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const bf16*)x, (const bf16*)bias, (bf16*)y, N, K, (const bf16*)norm_w, norm_eps, (const bf16*)residual, glu);
+    }
+    return rsvld_check_launch();
 }
 
 extern "C" size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len) {

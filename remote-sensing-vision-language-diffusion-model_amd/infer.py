@@ -71,8 +71,11 @@ class PipelineConfig:
     allow_random_init: bool = False   # tests / benchmarks only: run without checkpoints on seeded random weights
     overlap_vae_with_caption: bool = True   # Stage 2's opening VAE passes on a second HIP stream beside the live caption pass
     device_io: bool = False           # resize / crop / 8-bit conversions around both stages on the GPU (rsvld_amd.imageops) instead of PIL + numpy + CPU torch
+    caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8)
 
     def __post_init__(self):
+        if self.caption_weights not in ("native", "e4m3"):
+            raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected 'native' or 'e4m3'")
         self.output_dir = Path(self.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
         self.input_path = Path(self.input_img)
@@ -162,7 +165,8 @@ class SuperResolutionPipeline:
         # depend on how many tokens were sampled); --seed < 0 means "random run": the caption samples from the current state
         seed = None if self.cfg.seed < 0 else self.cfg.seed
         return LN.get_img_describe(image_tensor=views, image=sr_image, model=self.llava_model, tokenizer=self.llava_tokenizer,
-                                   prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed)[0]
+                                   prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed,
+                                   decode_weights=self.cfg.caption_weights)[0]
 
     def _stage2_input(self, sr_image):
         if self.cfg.device_io:
@@ -223,7 +227,7 @@ class SuperResolutionPipeline:
         return self.run_stage3_refinement(sr3, self.run_stage2_captioning(sr3), front=front)
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description="MI355X-native two-stage super-resolution pipeline")
     p.add_argument("--input_img", type=str, required=True)
     p.add_argument("--output_dir", type=str, default="./results")
@@ -250,11 +254,18 @@ def main(argv=None):
                                                          "inputs: rsvld_amd.ops.UNET_POLICY; fp16 x weight pairs, two MFMAs)")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (the shipped fp16 UNets): "
                                                              "+3 %% time, Stage-2 distance from the CPU path 3e-3 instead of 3e-2")
-    a = p.parse_args(argv)
+    p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
+                   "the checkpoint's 16-bit ones, or e4m3 bytes with one power-of-two scale per output row (half the bytes of a loop bound "
+                   "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights)")
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     cfg = PipelineConfig(input_img=a.input_img, output_dir=a.output_dir, upscale_factor=a.upscale_factor, seed=a.seed,
                          img_threshold=a.img_threshold, edm_steps=a.edm_steps, sr3_steps=a.sr3_steps, caption=a.caption,
                          no_llava=a.no_llava, llava_path=a.llava_path, llava_adapter=a.llava_adapter, use_tile_vae=a.use_tile_vae,
-                         device_io=a.device_io,
+                         device_io=a.device_io, caption_weights=a.caption_weights,
                          **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if a.fp32 else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if a.tolerance else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if a.split else

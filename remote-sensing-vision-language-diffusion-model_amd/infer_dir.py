@@ -22,14 +22,14 @@ EXTS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 
 class ImageBatchProcessor:
     def __init__(self, image_dir, save_dir, upscale=8, num_steps=50, seed=42, img_threshold=0.3, sr3_steps=0, device="cuda:0",
-                 no_llava=False, fp32=False, split=False, vae_split=False, tolerance=False, device_io=False):
+                 no_llava=False, fp32=False, split=False, vae_split=False, tolerance=False, device_io=False, caption_weights="native"):
         self.files = sorted(p for p in Path(image_dir).iterdir() if p.suffix.lower() in EXTS)
         self.save_dir, self.seed = Path(save_dir), seed
         self.save_dir.mkdir(parents=True, exist_ok=True)
         self.pipe = None
         self.kw = dict(output_dir=str(self.save_dir), upscale_factor=upscale, edm_steps=num_steps, seed=seed,
                        img_threshold=img_threshold, sr3_steps=sr3_steps, sr_model_device=device, base_model_device=device,
-                       no_llava=no_llava, device_io=device_io, **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if fp32 else
+                       no_llava=no_llava, device_io=device_io, caption_weights=caption_weights, **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if fp32 else
                                                 dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if tolerance else
                                                 dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if split else
                                                 dict(ae_dtype="split") if vae_split else {}))
@@ -59,7 +59,7 @@ class ImageBatchProcessor:
         return done, failed
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description="Batch two-stage super-resolution over a folder")
     p.add_argument("--image_dir", type=str, required=True)
     p.add_argument("--save_dir", type=str, required=True)
@@ -78,12 +78,18 @@ def main(argv=None):
                    "fp16 x weight pairs for the layer inputs of rsvld_amd.ops.UNET_POLICY): inside 1e-3 of the reference's CPU path; see INTEGRATION.md")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (+3 %% time, 10x closer to the CPU path)")
     p.add_argument("--device_io", action="store_true", help="the image steps around both stages on the GPU (rsvld_amd.imageops)")
-    a = p.parse_args(argv)
+    p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
+                   "the checkpoint's 16-bit ones, or e4m3 bytes with a scale per row (opt-in; see INTEGRATION.md)")
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(local)
     proc = ImageBatchProcessor(a.image_dir, a.save_dir, a.upscale, a.num_steps, a.seed, a.img_threshold, a.sr3_steps,
                                device=f"cuda:{local}", no_llava=a.no_llava, fp32=a.fp32, split=a.split, vae_split=a.vae_split,
-                               tolerance=a.tolerance, device_io=a.device_io)
+                               tolerance=a.tolerance, device_io=a.device_io, caption_weights=a.caption_weights)
     done, failed = proc.run(rank, world)
     print(f"[rank {rank}] wrote {len(done)} images, {len(failed)} failures")
 

@@ -304,9 +304,21 @@ class FastDecoder:
     and addresses and can be captured once (``torch.cuda.CUDAGraph`` = hipGraph) and replayed per token.  Sampling follows
     ``generate`` exactly (temperature, then one ``torch.multinomial`` per step; greedy = argmax), which is what
     tests/test_llava_next.py pins token for token against the reference's generations.  On the CPU (tests) the same code
-    runs eagerly."""
+    runs eagerly.
 
-    def __init__(self, model, max_len):
+    ``weights``: "native" (default) streams the checkpoint's 16-bit weights.  "e4m3" (opt-in) packs the fused q|k|v, ``o_proj``,
+    gate|up, ``down_proj`` and ``lm_head`` once as OCP e4m3 bytes with one power-of-two scale per output row (``rsvld_amd.w8``) and the
+    fused decode step streams THOSE -- half the bytes of a loop bound by nothing else; activations, the KV cache, accumulation, the
+    fused neighbours and sampling are unchanged.  The prefill keeps the 16-bit weights, so the packs come ON TOP of them: 8 GB beside
+    the 16 GB that stay resident for the 8 B decoder.  The mode needs the fused decode step (``_fused_ok``) and ``K % 16 == 0`` in
+    every packed product; where either fails the decoder raises -- it never falls back to the native weights silently."""
+
+    WEIGHTS = ("native", "e4m3")
+
+    def __init__(self, model, max_len, weights="native"):
+        if weights not in self.WEIGHTS:
+            raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
+        self.weights = weights
         cfg = model.config
         self.model, self.max_len = model, int(max_len)
         self.layers = list(model.model.layers)
@@ -333,6 +345,36 @@ class FastDecoder:
             if mlp.gate_proj.bias is not None:
                 raise NotImplementedError("FastDecoder: biased MLP projections")
             self.wgu.append(self._fuse([mlp.gate_proj, mlp.up_proj], "weight"))
+        self._packs = self._pack_e4m3() if weights == "e4m3" else None
+
+    def _pack_sources(self):
+        """The 16-bit tensors the e4m3 mode packs, in pack order: per layer q|k|v, o_proj, gate|up, down_proj; then lm_head."""
+        src = []
+        for i, layer in enumerate(self.layers):
+            src += [self.wqkv[i], layer.self_attn.o_proj.weight, self.wgu[i], layer.mlp.down_proj.weight]
+        return src + [self.model.lm_head.weight]
+
+    @staticmethod
+    def _identity(t):
+        """(storage address, in-place version) of a packed source; an inference-mode tensor counts no versions."""
+        try:
+            return t.data_ptr(), t._version
+        except RuntimeError:
+            return t.data_ptr(), 0
+
+    def _pack_e4m3(self):
+        """-> per layer ``(qkv, o, gu, down)`` and last the ``lm_head``, each a ``(q, scale)`` of ``w8.pack_rows_e4m3``."""
+        from . import w8
+        src = self._pack_sources()
+        for t in src:
+            if t.dim() != 2 or t.shape[1] % 16 or t.dtype not in (torch.float16, torch.bfloat16) or not t.is_cuda:
+                raise ValueError(f"FastDecoder(weights='e4m3'): a {t.dtype} weight of shape {tuple(t.shape)} on {t.device} cannot be "
+                                 f"packed (16-bit weights on the GPU with K % 16 == 0 are required; there is no fallback to 'native')")
+        with torch.no_grad():
+            packs = [w8.pack_rows_e4m3(t.contiguous()) for t in src]
+        # what ``stale`` compares: a pack is a COPY, so an in-place update of its source (a LoRA merge) must be seen too
+        self._pack_state = [self._identity(t) for t in src]
+        return [tuple(packs[4 * i:4 * i + 4]) for i in range(len(self.layers))] + [packs[-1]]
 
     def stale(self):
         """The fused q | k | v and gate | up tensors are VIEWED by the model's own modules; ``model.to()`` / ``.half()`` / a LoRA merge /
@@ -343,6 +385,10 @@ class FastDecoder:
             g = self.layers[i].mlp.gate_proj.weight
             if (q.data_ptr() != self.wqkv[i].data_ptr() or g.data_ptr() != self.wgu[i].data_ptr() or q.device != self.wqkv[i].device
                     or q.dtype != self.wqkv[i].dtype):
+                return True
+        if self._packs is not None:      # the e4m3 packs are copies: same storage, not written since, and on the weights' device
+            src = self._pack_sources()
+            if [self._identity(t) for t in src] != self._pack_state or self._packs[-1][0].device != src[-1].device:
                 return True
         return False
 
@@ -381,6 +427,9 @@ class FastDecoder:
         g = nq // nkv
         if T == 1 and self._fused_ok(embeds):
             return self._forward_fused(embeds, pos)
+        if T == 1 and self._packs is not None:
+            raise RuntimeError("FastDecoder(weights='e4m3'): the fused decode step is not available for this model / input "
+                               "(see _fused_ok) and the e4m3 weights have no other path; use weights='native'")
         cos, sin = m.rotary_emb(embeds, pos[None])                                 # [1, T, hd]
         cos, sin = cos[0][:, None], sin[0][:, None]                                # [T, 1, hd]
         bias = torch.zeros((T, self.max_len), device=self.dev, dtype=torch.float32)
@@ -408,7 +457,8 @@ class FastDecoder:
 
     def _fused_ok(self, embeds):
         """The decode step as the library's fused kernels (rsvld_gemv_fused, rsvld_llama_decode_attention): 16-bit tensors on the GPU, head_dim
-        128, at most eight query heads per kv head, unbiased MLP, 16-byte aligned rows."""
+        128, at most eight query heads per kv head, unbiased MLP, 16-byte aligned rows (``weights="e4m3"``: of e4m3 too, K % 16 == 0 in every
+        product -- checked when the packs are made)."""
         return (self.fused and embeds.is_cuda and embeds.dtype in (torch.float16, torch.bfloat16) and self.hd == 128
                 and self.n_q % self.n_kv == 0 and self.n_q // self.n_kv <= 8 and embeds.shape[-1] % 8 == 0)
 
@@ -427,16 +477,26 @@ class FastDecoder:
             lib = ops.L.load()
             self._ws = torch.empty(int(lib.rsvld_llama_decode_attention_ws_bytes(self.n_q, self.n_kv, self.max_len)) // 4, device=self.dev,
                                    dtype=torch.float32)          # (per-chunk partial results: written before they are read, no initial state)
+        if self._packs is not None:
+            from . import w8
+
+            def gemv(which, w, *a, **kw):        # the same call on the pack of ``w``
+                return w8.gemv_w8(*which, *a, **kw)
+        else:
+            def gemv(which, w, *a, **kw):
+                return ops.gemv_fused(w, *a, **kw)
+        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
         for i, layer in enumerate(self.layers):
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
-            qkv = ops.gemv_fused(self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
+            p_qkv, p_o, p_gu, p_down = packs[i]
+            qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
             o = ops.llama_decode_attention(qkv, cos, sin, pos, self.k[i][0], self.v[i][0], self.n_q, self.n_kv, scale, ws=self._ws)
             op = layer.self_attn.o_proj
-            h = ops.gemv_fused(op.weight, o, op.bias, residual=h)
-            gu = ops.gemv_fused(self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
-            h = ops.gemv_fused(layer.mlp.down_proj.weight, gu, None, glu=True, residual=h)
+            h = gemv(p_o, op.weight, o, op.bias, residual=h)
+            gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
+            h = gemv(p_down, layer.mlp.down_proj.weight, gu, None, glu=True, residual=h)
         head = self.model.lm_head
-        return ops.gemv_fused(head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))[None]
+        return gemv(packs[-1], head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))[None]
 
     def _pick(self, logits, do_sample, temperature, top_k=0, top_p=1.0):
         """``generate``'s sampling chain (transformers' TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial).
@@ -656,14 +716,19 @@ def _eos_ids(model, tokenizer):
 
 def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templates=conv_templates,
                      image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
-                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None):
+                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None):
     """models/util.py:17-66 -> ``[caption]``.  ``seed`` (an addition) makes the caption a function of (image, prompt,
     weights, seed): sampling then runs inside ``torch.random.fork_rng`` with the CPU and the model's device generator seeded
     THERE, so the caller's generators -- which Stage 2 draws its noise from right afterwards, and in the reference live on
     another device (infer.py:145-166: LLaVA on cuda:1) -- are exactly where they were, however many tokens were sampled.
     ``seed=None`` samples from the current generator state without touching any seed.
     ``fast`` (default: on a GPU, with one beam): the token loop runs through ``FastDecoder`` (static cache, decode step
-    replayed from a hipGraph) instead of ``transformers``' ``generate``; same tokens (tests/test_llava_next.py)."""
+    replayed from a hipGraph) instead of ``transformers``' ``generate``; same tokens (tests/test_llava_next.py).
+    ``decode_weights`` (None = "native"): "e4m3" streams the token loop's weights as e4m3 bytes (``FastDecoder(weights=...)``, opt-in:
+    other logits than the 16-bit weights give); it needs the fast path, anything else raises."""
+    decode_weights = "native" if decode_weights is None else decode_weights
+    if decode_weights not in FastDecoder.WEIGHTS:
+        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
     if conv_template != "llava_llama_3":
         raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
     system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
@@ -678,12 +743,15 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
         warnings.warn("llava_next: the checkpoint's generation_config asks for logits processors FastDecoder does not implement; "
                       "captioning through transformers' generate()")
         fast = False
+    if decode_weights != "native" and not fast:
+        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r} needs the FastDecoder token loop (a GPU model, one beam, no "
+                         f"logits processors beyond temperature / top_k / top_p)")
 
     def run():
         if fast:   # (no_grad, not inference_mode: tensors made in inference mode cannot be updated in place by a later call
             with torch.no_grad():   # outside it, and a hipGraph capture that fails on that leaves the generator in capture state)
                 return caption_tokens_fast(model, input_ids, image_tensor, [image.size], max_new_tokens, do_sample, temperature,
-                                           _eos_ids(model, tokenizer))
+                                           _eos_ids(model, tokenizer), weights=decode_weights)
         with torch.inference_mode():
             return model.generate(input_ids, images=image_tensor, image_sizes=[image.size], do_sample=do_sample,
                                   temperature=temperature, num_beams=num_beams, max_new_tokens=max_new_tokens,
@@ -713,14 +781,18 @@ def _has_logits_warpers(model):
             or bool(getattr(g, "suppress_tokens", None)))
 
 
-def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None):
-    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model and cache size)."""
+def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native"):
+    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size and weight mode:
+    asking for the other mode rebuilds the decoder, its packs and its captured graph)."""
     embeds = model.multimodal_embeds(input_ids, images, image_sizes)
     need = embeds.shape[1] + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
     if dec is not None and dec.stale():     # the model was moved / cast / reloaded since the decoder fused its weights: rebuild
         dec = None
+    if dec is not None and dec.weights != weights:
+        dec = None
     if dec is None or dec.max_len < need:
-        dec = FastDecoder(model, -(-need // 256) * 256)
+        model.__dict__.pop("_fast_decoder", None)      # (the old decoder's cache and packs go before the new ones are allocated)
+        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights)
         model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)

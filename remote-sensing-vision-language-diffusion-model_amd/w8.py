@@ -1,0 +1,86 @@
+"""Weight-streaming products on OCP e4m3 weights with one power-of-two scale per output row (rsvld_pack_rows_e4m3, rsvld_gemv_w8_fused):
+the opt-in ``weights="e4m3"`` mode of the caption pass's token loop (``llava_next.FastDecoder``), which is bound by weight bytes alone.
+
+The quantiser, exactly (``pack_rows_e4m3_host`` is this paragraph in torch, bit for bit what the kernel writes): for a 16-bit row
+``w[n, :]`` take ``amax`` over its finite elements; ``e[n]`` is the smallest integer with ``amax * 2^-e <= 448``, computed from
+``amax = m * 2^x`` (``frexp``, ``m`` in [0.5, 1)) and ``448 = 0.875 * 2^9`` as ``e = x - 9`` if ``m <= 0.875`` else ``x - 8``; 0 for an
+all-zero row; clamped to [-126, 127].  ``q[n, k] = e4m3_rne(w[n, k] * 2^-e[n])``: the scaling is exact and nothing saturates.  A
+non-finite weight becomes byte 0x7F (e4m3 NaN), so a corrupt checkpoint shows as NaN logits.  Storage: ``q`` uint8 ``[N, K]``
+(``K % 16 == 0``: 16-byte rows), ``scale`` float32 ``[N]`` = ``2^e``.
+
+Like every wrapper of ``ops``, the two device functions check their operands before anything is allocated or launched, raise on a CPU
+tensor (there is no CPU path) and launch through ``ops._launch`` so the profiler sees them."""
+import torch
+
+from . import _lib as L
+from . import ops
+from .ops import _HALF, _arg, _bad, _launch, _need_gpu, _ptr, _stream
+
+E4M3_NAN = 0x7F
+
+
+def pack_rows_e4m3(w):
+    """16-bit ``w [N, K]`` (contiguous, ``K % 16 == 0``) -> ``(q uint8 [N, K], scale float32 [N])`` on the device (rsvld_pack_rows_e4m3)."""
+    _arg("pack_rows_e4m3", "w", w, _HALF, shape=(None, None))
+    N, K = w.shape
+    if N == 0 or K == 0 or K % 16:
+        _bad("pack_rows_e4m3", "w", f"has shape {tuple(w.shape)}: rows of whole 16-byte pieces of e4m3 (K % 16 == 0) expected")
+    _need_gpu(w)
+    q = ops.torch.empty((N, K), device=w.device, dtype=torch.uint8)        # (through ``ops.torch``, like every output of ops.py)
+    scale = ops.torch.empty(N, device=w.device, dtype=torch.float32)
+    lib = L.load()
+    _launch("pack_rows_e4m3", 0.0, N * K * 3 + N * 4, lambda: L.check(
+        lib.rsvld_pack_rows_e4m3(_ptr(w), _ptr(q), _ptr(scale), N, K, ops._dt(w), _stream()), "rsvld_pack_rows_e4m3"))
+    return q, scale
+
+
+def gemv_w8(q, scale, x, bias=None, *, norm=None, residual=None, glu=False):
+    """``ops.gemv_fused`` on packed weights (rsvld_gemv_w8_fused): ``q [N, K]`` uint8 and ``scale [N]`` float32 from ``pack_rows_e4m3``,
+    ONE 16-bit activation row ``x`` (``[K]``, or ``[2 K]`` = gate | up with ``glu``) -> ``T(scale * (q x') + bias)``, then the residual,
+    in ``x``'s type.  ``norm`` / ``glu`` / ``residual`` as in ``ops.gemv_fused``, with its roundings."""
+    _arg("gemv_w8", "q", q, torch.uint8, shape=(None, None))
+    N, K = q.shape
+    if N == 0 or K == 0 or K % 16:
+        _bad("gemv_w8", "q", f"has shape {tuple(q.shape)}: rows of whole 16-byte pieces of e4m3 (K % 16 == 0) expected")
+    nw, eps = (None, 0.0) if norm is None else norm
+    _arg("gemv_w8", "scale", scale, torch.float32, numel=N)
+    _arg("gemv_w8", "x", x, _HALF, numel=2 * K if glu else K)
+    _arg("gemv_w8", "bias", bias, x.dtype, numel=N, optional=True)
+    _arg("gemv_w8", "norm weight", nw, x.dtype, numel=x.numel(), optional=True)
+    _arg("gemv_w8", "residual", residual, x.dtype, numel=N, optional=True)
+    if glu and nw is not None:
+        _bad("gemv_w8", "norm weight", "cannot be combined with glu")
+    _need_gpu(q, scale, x, bias, nw, residual)
+    y = ops.torch.empty(N, device=x.device, dtype=x.dtype)
+    lib = L.load()
+    _launch("gemv_w8", 2.0 * N * K, N * K + N * 4 + (K + N) * 2, lambda: L.check(
+        lib.rsvld_gemv_w8_fused(_ptr(q), _ptr(scale), _ptr(x), _ptr(bias), _ptr(nw), float(eps), _ptr(residual), int(glu), _ptr(y), N, K,
+                                ops._dt(x), _stream()), "rsvld_gemv_w8_fused"))
+    return y
+
+
+# ----------------------------------------------------------------------------- host model (what the tests compare the kernels with)
+def row_exponents_host(w):
+    """``e [N]`` (int32) of the rule above, from ``torch.frexp``."""
+    wf = w.detach().to(device="cpu", dtype=torch.float32)
+    amax = torch.where(torch.isfinite(wf), wf.abs(), torch.zeros(())).amax(dim=1)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    return torch.where(amax == 0, torch.zeros_like(e), e).clamp(-126, 127).to(torch.int32)
+
+
+def pack_rows_e4m3_host(w):
+    """The quantiser on the host: 16-bit ``w [N, K]`` -> ``(q uint8 [N, K], scale float32 [N])`` on the CPU.  torch's cast to
+    ``float8_e4m3fn`` rounds to nearest even, as the hardware conversion does."""
+    wf = w.detach().to(device="cpu", dtype=torch.float32)
+    e = row_exponents_host(w)
+    one = torch.ones(e.shape, dtype=torch.float32)
+    q = (wf * torch.ldexp(one, -e)[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    q[~torch.isfinite(wf)] = E4M3_NAN
+    return q, torch.ldexp(one, e)
+
+
+def dequant(q, scale):
+    """``(q, scale)`` -> the float32 ``[N, K]`` the kernel multiplies with: exact (e4m3 has 4 significant bits, the scale is a power of
+    two)."""
+    return q.view(torch.float8_e4m3fn).to(torch.float32) * scale.to(torch.float32)[:, None]
