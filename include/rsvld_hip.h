@@ -471,6 +471,28 @@ size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len);
 int rsvld_llama_decode_attention(const void* qkv, const void* cos, const void* sin, const int64_t* pos, void* kcache, void* vcache, void* out,
                                  float* ws, int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype, void* stream);
 
+/* The batched token loop (--caption_batch: the captions of several images' Stage-1 outputs in ONE loop; the reference captions image after
+ * image, models/util.py:39-60 called from infer_dir.py:196-201): the three operators above for B <= RSVLD_DECODE_MAX_ROWS independent
+ * sequences, the weights streamed once for all of them.  CONTRACT: row b of every result is bit for bit what the single-row entry point
+ * gives for row b alone -- the same lane-to-k mapping, step order, wave reduction, fixed K-split partial order and roundings per row, the
+ * same row / K-split route for (N, K) whatever B is -- so a caption does not depend on which sequences share its batch, or on how many. */
+#define RSVLD_DECODE_MAX_ROWS 8
+/* rsvld_gemv_fused for B rows: x [B][K] ([B][2K] with glu), residual and y [B][N], contiguous; w, bias, norm_w are shared by the rows.
+ * Every K rsvld_gemv_fused takes, at every B in 1..8 (rows whose staged form does not fit the CU's 160 KiB of LDS together are walked in
+ * groups, one weight pass per group).  B outside 1..RSVLD_DECODE_MAX_ROWS: RSVLD_EINVAL. */
+int rsvld_gemv_rows_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
+                          void* y, int N, int K, int B, int dtype, void* stream);
+/* rsvld_gemv_w8_fused for B rows, as above (q [N][K] e4m3 bytes and scale [N] fp32 of rsvld_pack_rows_e4m3). */
+int rsvld_gemv_w8_rows_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                             const void* residual, int glu, void* y, int N, int K, int B, int dtype, void* stream);
+/* rsvld_llama_decode_attention for B sequences with a position each: qkv [B][(n_q + 2 n_kv) x head_dim], cos / sin [B][head_dim],
+ * pos [B] (DEVICE int64), kcache / vcache [B][n_kv][max_len][head_dim] UPDATED at pos[b] in sequence b's slice only (no byte of another
+ * sequence's cache is written), out [B][n_q x head_dim]; ws: rsvld_llama_decode_attention_rows_ws_bytes = B x the single workspace. */
+size_t rsvld_llama_decode_attention_rows_ws_bytes(int n_q, int n_kv, int max_len, int B);
+int rsvld_llama_decode_attention_rows(const void* qkv, const void* cos, const void* sin, const int64_t* pos, void* kcache, void* vcache,
+                                      void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Split-operand product path (round 4): the producers / consumers of bf16 PLANES around the RSVLD_SPLIT convolutions.
  * "planes [rows][2C]" = per row lo(C) | hi(C) of an fp32 [rows][C] tensor (see RSVLD_SPLIT above); C % 8 == 0.

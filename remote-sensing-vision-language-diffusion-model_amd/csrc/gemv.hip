@@ -8,6 +8,8 @@
 // Round 5, KS = 4: layers with few output rows (o_proj / down_proj / q|k|v of the 8 B decoder: 4 096 .. 6 144 rows = 256 .. 384 workgroups
 // of 16 rows, ONE per CU with 32 KiB of weight loads in flight where ~64 KiB per CU are needed to keep HBM busy) run with the four waves
 // of a workgroup SPLITTING K for the same GV_RPW rows: four times the workgroups, partial sums through LDS.
+// gemv_rows_kernel (behind the decode attention): the same products for up to RSVLD_DECODE_MAX_ROWS activation rows per weight pass (the
+// batched token loop), every row bit-identical to the single-row kernels.
 #include "rsvld_common.h"
 #include <type_traits>
 
@@ -348,7 +350,16 @@ __global__ __launch_bounds__(256) void da_kernel(const T* __restrict__ qkv, cons
     __shared__ float ml[DA_GMAX][2];
     const int kvh = blockIdx.x, c = blockIdx.y, nchunk = gridDim.y;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int G = n_q / n_kv, p = (int)min(max(*pos_p, 0ll), (long long)max_len - 1), half = DA_HD / 2;   // (a position outside the cache is clamped, never written past it)
+    // blockIdx.z: the sequence (rsvld_llama_decode_attention_rows; one sequence = the single entry point).  Every operand of a sequence is a
+    // whole slice, so the code below is the single-sequence step on offset pointers: no byte of another sequence is read or written.
+    const size_t seq = blockIdx.z;
+    qkv += seq * (size_t)(n_q + 2 * n_kv) * DA_HD;
+    cosv += seq * DA_HD;
+    sinv += seq * DA_HD;
+    kc += seq * (size_t)n_kv * max_len * DA_HD;
+    vc += seq * (size_t)n_kv * max_len * DA_HD;
+    ws += seq * (size_t)n_q * nchunk * (DA_HD + 2);
+    const int G = n_q / n_kv, p = (int)min(max(pos_p[seq], 0ll), (long long)max_len - 1), half = DA_HD / 2;   // (a position outside the cache is clamped, never written past it)
     float* out = ws + ((size_t)(kvh * nchunk + c) * G) * (DA_HD + 2);
     const int j0 = c * DA_CH, nkeys = min(DA_CH, p + 1 - j0);
     const bool owner = p >= j0 && p < j0 + DA_CH;
@@ -452,6 +463,8 @@ template <typename T>
 __global__ __launch_bounds__(DA_HD) void da_combine_kernel(const float* __restrict__ ws, T* __restrict__ out, int n_q, int n_kv, int nchunk) {
     __shared__ float wsh[64];
     const int h = blockIdx.x, G = n_q / n_kv, kvh = h / G, g = h % G, d = threadIdx.x;
+    ws += (size_t)blockIdx.y * n_q * nchunk * (DA_HD + 2);     // blockIdx.y: the sequence, as in da_kernel
+    out += (size_t)blockIdx.y * n_q * DA_HD;
     const float* base = ws + ((size_t)kvh * nchunk * G + g) * (DA_HD + 2);
     const size_t cs = (size_t)G * (DA_HD + 2);
     float l = 0.f, acc = 0.f;
@@ -484,7 +497,127 @@ __global__ __launch_bounds__(DA_HD) void da_combine_kernel(const float* __restri
     out[(size_t)h * DA_HD + d] = (T)(acc / l);
 }
 
+// ---- the same products for NB activation rows at once (rsvld_gemv_rows_fused, rsvld_gemv_w8_rows_fused): the batched token loop streams a
+// weight piece ONCE into registers and uses it for every row.  Per activation row the arithmetic is gemv_kernel's / gemv_w8_kernel's, operation
+// for operation: the row is staged by gv_stage_x (its own K elements of LDS), lane l of a wave accumulates the same k in the same ascending
+// order with the same fmaf chain (dot8 / dot16_w8) into an accumulator of its own, the 64 partial sums meet in the same wave_sum, the K-split
+// route adds its four partials in the same fixed order, and the result leaves through gv_store -- so row b of the result is bit for bit what
+// the single-row kernel gives for x[b], whatever NB is and whatever the other rows hold (a NaN row stays in its own accumulators).  What may
+// differ is only WHICH workgroup computes an output row: a workgroup keeps its staged rows and walks output-row blocks blk, blk + gridDim.x, ..
+// (the staging of NB rows is paid once per workgroup, not once per 16 output rows).  The conversions of a weight piece to fp32 are written
+// inside dot8 / dot16_w8 per row; unrolled, the compiler keeps one copy per piece.
+// LDS: [NB][K] x' | KS = 4: [NB][4][GV_RPW] partial sums | 16 floats of reduction scratch.
+// (at least two waves per SIMD: left alone, the compiler spends 512 registers per lane on the eight-row form -- one workgroup per CU, nothing
+// to hide a weight load behind)
+constexpr int GVR_MIN_WAVES = 2;
+// rows up to which two weight steps are in flight per lane, as in the single-row kernels; with more rows the converted pieces of two steps
+// and the accumulators no longer fit the registers of two waves per SIMD (spills), and the loop is bound by its arithmetic anyway
+constexpr int GVR_TWO_STEP_ROWS = 2;
+template <typename T, int KS, int NB, bool W8>
+__global__ __launch_bounds__(64 * GV_WAVES, GVR_MIN_WAVES) void gemv_rows_kernel(const void* __restrict__ Wv, const float* __restrict__ scale, const T* __restrict__ x,
+                                                                   const T* __restrict__ bias, T* __restrict__ y, int N, int K,
+                                                                   const T* __restrict__ norm_w, float eps, const T* __restrict__ residual, int glu,
+                                                                   int nblocks) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using W = std::conditional_t<W8, uint8_t, T>;
+    constexpr int PIECE = W8 ? 16 : 8, STEP = 64 * PIECE;      // elements of K per 16-byte piece / per wave step
+    const W* Wm = (const W*)Wv;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const size_t xrow = (size_t)K * 2;                          // bytes of one staged row
+    const int part_bytes = KS == 4 ? NB * 4 * GV_RPW * (int)sizeof(float) : 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)                                // (red_off: every row's reduction scratch is the one behind the partial sums)
+        gv_stage_x<T>(smem + b * xrow, (NB - 1 - b) * (int)xrow + part_bytes, x + (size_t)b * (glu ? 2 * K : K), norm_w, eps, K, glu, tid, lane, w);
+    float* part = (float*)(smem + NB * xrow);
+    for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const int row0 = KS == 4 ? blk * GV_RPW : (blk * GV_WAVES + w) * GV_RPW;
+        if (KS == 1 && row0 >= N) continue;
+        const W* wr[GV_RPW];
+#pragma unroll
+        for (int r = 0; r < GV_RPW; ++r) wr[r] = Wm + (int64_t)min(row0 + r, N - 1) * K;   // rows past N re-read the last row, never stored
+        float acc[NB][GV_RPW];
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int r = 0; r < GV_RPW; ++r) acc[b][r] = 0.f;
+        // one piece of each of the GV_RPW weight rows against every staged row
+        auto fma_rows = [&](const u32x4 (&wv)[GV_RPW], int kk) __attribute__((always_inline)) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const char* xs = smem + b * xrow + (size_t)kk * 2;
+                if constexpr (W8) {
+                    const u32x4 x0 = *(const u32x4*)xs, x1 = *(const u32x4*)(xs + 16);
+#pragma unroll
+                    for (int r = 0; r < GV_RPW; ++r) acc[b][r] = dot16_w8<T>(wv[r], x0, x1, acc[b][r]);
+                } else {
+                    const u32x4 xv = *(const u32x4*)xs;
+#pragma unroll
+                    for (int r = 0; r < GV_RPW; ++r) acc[b][r] = dot8<T>(wv[r], xv, acc[b][r]);
+                }
+            }
+        };
+        // the K range of this wave and its lane's first piece: as gemv_kernel / gemv_w8_kernel
+        const int kq = K >> 2, kend = KS == 4 ? (w + 1) * kq : K;
+        int kk = (KS == 4 ? w * kq : 0) + lane * PIECE;
+        const int kbeg = kk - lane * PIECE;
+        // two whole steps per iteration (2 x GV_RPW loads in flight per lane), then step by step with pieces past the range skipped per
+        // lane: the same ascending k sequence per lane as the single-row loops, whose own two-step / tail split is not part of the result
+        int kb = kbeg;
+        if constexpr (NB <= GVR_TWO_STEP_ROWS) for (; kb + 2 * STEP <= kend; kb += 2 * STEP, kk += 2 * STEP) {
+            u32x4 wv[2][GV_RPW];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int r = 0; r < GV_RPW; ++r) wv[u][r] = __builtin_nontemporal_load((const u32x4*)(wr[r] + kk + u * STEP));
+#pragma unroll
+            for (int u = 0; u < 2; ++u) fma_rows(wv[u], kk + u * STEP);
+        }
+        for (; kb < kend; kb += STEP, kk += STEP) {
+            if (kk < kend) {
+                u32x4 wv[GV_RPW];
+#pragma unroll
+                for (int r = 0; r < GV_RPW; ++r) wv[r] = __builtin_nontemporal_load((const u32x4*)(wr[r] + kk));
+                fma_rows(wv, kk);
+            }
+        }
+        if constexpr (KS == 4) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < GV_RPW; ++r) {
+                    const float v = wave_sum(acc[b][r]);
+                    if (lane == 0) part[(b * 4 + w) * GV_RPW + r] = v;
+                }
+            __syncthreads();
+            if (tid < NB * GV_RPW && row0 + (tid % GV_RPW) < N) {   // fixed order: wave 0 .. 3
+                const int b = tid / GV_RPW, r = tid % GV_RPW;
+                const float* pb = part + b * 4 * GV_RPW;
+                float v = ((pb[r] + pb[GV_RPW + r]) + pb[2 * GV_RPW + r]) + pb[3 * GV_RPW + r];
+                if constexpr (W8) v = v * scale[row0 + r];
+                gv_store<T>(y + (size_t)b * N, bias, residual != nullptr ? residual + (size_t)b * N : nullptr, row0 + r, v);
+            }
+            __syncthreads();                                     // the partial sums are rewritten by the next block of rows
+        } else {
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < GV_RPW; ++r) {
+                    float v = wave_sum(acc[b][r]);
+                    if (lane == 0 && row0 + r < N) {
+                        if constexpr (W8) v = v * scale[row0 + r];
+                        gv_store<T>(y + (size_t)b * N, bias, residual != nullptr ? residual + (size_t)b * N : nullptr, row0 + r, v);
+                    }
+                }
+        }
+    }
+}
+
 }  // namespace
+
+// the row / K-split route of an (N, K) product: one statement for the single-row launches and the multi-row ones (which must not let the
+// number of activation rows into it: a row's summation order is the route's)
+static bool gemv_ksplit(int N, int K) { return K % 2048 == 0 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
+static bool gemv_w8_ksplit(int N, int K) { return K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
 
 static int gemv_launch(const void* w, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu, void* y,
                        int N, int K, int dtype, void* stream) {
@@ -495,7 +628,7 @@ static int gemv_launch(const void* w, const void* x, const void* bias, const voi
     if (glu && (norm_w != nullptr || (((uintptr_t)x + (uintptr_t)K * 2) & 15))) return RSVLD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     // few rows (fewer than ~4 row-split workgroups per CU of a 256-CU chip): the four waves of a workgroup split K instead
-    const bool ksplit = K % 2048 == 0 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024;
+    const bool ksplit = gemv_ksplit(N, K);
     const dim3 grid(ksplit ? (unsigned)((N + GV_RPW - 1) / GV_RPW) : (unsigned)((N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW)));
     const size_t smem = (size_t)K * 2 + (ksplit ? 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
     const f16* wh = (const f16*)w; const f16* xh = (const f16*)x; const f16* bh = (const f16*)bias;
@@ -541,7 +674,7 @@ extern "C" int rsvld_gemv_w8_fused(const void* q, const float* scale, const void
     hipStream_t s = (hipStream_t)stream;
     // as gemv_launch: few rows (fewer than ~4 row-split workgroups per CU) split K over the four waves -- here for every K whose quarter is
     // whole 16-element pieces (K % 64 == 0) and at least two wave steps long in all (K >= 2 048)
-    const bool ksplit = K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024;
+    const bool ksplit = gemv_w8_ksplit(N, K);
     const dim3 grid(ksplit ? (unsigned)((N + GV_RPW - 1) / GV_RPW) : (unsigned)((N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW)));
     const size_t smem = (size_t)K * 2 + (ksplit ? 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
     const uint8_t* qw = (const uint8_t*)q;
@@ -579,6 +712,115 @@ extern "C" int rsvld_llama_decode_attention(const void* qkv, const void* cosv, c
         hipLaunchKernelGGL((da_kernel<bf16>), dim3(n_kv, nchunk), dim3(256), 0, s, (const bf16*)qkv, (const bf16*)cosv, (const bf16*)sinv,
                            (const long long*)pos, (bf16*)kcache, (bf16*)vcache, ws, n_q, n_kv, max_len, scale);
         hipLaunchKernelGGL((da_combine_kernel<bf16>), dim3(n_q), dim3(DA_HD), 0, s, ws, (bf16*)out, n_q, n_kv, nchunk);
+    }
+    return rsvld_check_launch();
+}
+
+// ---- multi-row entry points (the batched token loop: B <= RSVLD_DECODE_MAX_ROWS activation rows per weight pass)
+namespace {
+constexpr int GVR_LDS = 160 * 1024;     // LDS of a CU: what one workgroup may hold (registered per kernel above 64 KiB)
+constexpr int GVR_CUS = 256;            // sizes the persistent grid only (any grid gives the same results)
+
+template <typename T, int KS, int NB, bool W8>
+int gvr_go(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
+           void* y, int N, int K, hipStream_t s) {
+    constexpr auto KERN = gemv_rows_kernel<T, KS, NB, W8>;
+    const size_t smem = (size_t)NB * K * 2 + (KS == 4 ? NB * 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
+    if (smem > 65536 && rsvld_smem_once<KERN>(GVR_LDS) != hipSuccess) return RSVLD_ELAUNCH;
+    const int nblocks = KS == 4 ? (N + GV_RPW - 1) / GV_RPW : (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW);
+    const int per_cu = (int)(GVR_LDS / smem) < 8 ? (int)(GVR_LDS / smem) : 8;     // workgroups of 4 waves a CU holds
+    const int grid = nblocks < GVR_CUS * per_cu ? nblocks : GVR_CUS * per_cu;
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64 * GV_WAVES), smem, s, w, scale, (const T*)x, (const T*)bias, (T*)y, N, K, (const T*)norm_w, eps,
+                       (const T*)residual, glu, nblocks);
+    return RSVLD_OK;
+}
+// One instantiation per row count: 2 types x 2 routes x 8 row counts x 2 weight kinds = 64 kernels, each unrolled over its rows.  Cost,
+// measured on this file: it compiles in ~30 s instead of ~4 s and its object grows from 0.12 to 1.4 MB.  The alternative -- only 2 / 4 / 8
+// rows, a group rounded up and the surplus rows masked at the store -- would spend the surplus rows' arithmetic, which is what binds from
+// four rows on (3 rows at the price of 4, 5 at the price of 8): not taken.  Every count is reachable: B itself, and the groups of gvr_launch.
+template <typename T, int KS, bool W8, typename... A> int gvr_nb(int nb, A... a) {
+    switch (nb) {
+        case 1: return gvr_go<T, KS, 1, W8>(a...);
+        case 2: return gvr_go<T, KS, 2, W8>(a...);
+        case 3: return gvr_go<T, KS, 3, W8>(a...);
+        case 4: return gvr_go<T, KS, 4, W8>(a...);
+        case 5: return gvr_go<T, KS, 5, W8>(a...);
+        case 6: return gvr_go<T, KS, 6, W8>(a...);
+        case 7: return gvr_go<T, KS, 7, W8>(a...);
+        case 8: return gvr_go<T, KS, 8, W8>(a...);
+    }
+    return RSVLD_EINVAL;
+}
+
+// B rows in groups of equal size whose staged rows fit the LDS (K <= 10 200: one group of eight; down_proj's K = 14 336: 2 x 4; the largest
+// K the single-row entry takes: 4 x 2) -- a group is one launch, and one pass over the weights
+template <bool W8>
+int gvr_launch(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
+               void* y, int N, int K, int B, int dtype, bool ksplit, void* stream) {
+    const size_t per_row = (size_t)K * 2 + 4 * GV_RPW * sizeof(float);
+    const int fit = (int)((GVR_LDS - 16 * sizeof(float)) / per_row);           // >= 2: a single row is <= 64 KiB
+    const int gmax = fit < RSVLD_DECODE_MAX_ROWS ? fit : RSVLD_DECODE_MAX_ROWS;
+    const int ngroups = (B + gmax - 1) / gmax, g = (B + ngroups - 1) / ngroups;
+    hipStream_t s = (hipStream_t)stream;
+    for (int b0 = 0; b0 < B; b0 += g) {
+        const int nb = B - b0 < g ? B - b0 : g;
+        const char* xg = (const char*)x + (size_t)b0 * (glu ? 2 : 1) * K * 2;
+        const char* rg = residual ? (const char*)residual + (size_t)b0 * N * 2 : nullptr;
+        char* yg = (char*)y + (size_t)b0 * N * 2;
+        int rc;
+        if (dtype == RSVLD_F16) rc = ksplit ? gvr_nb<f16, 4, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s)
+                                            : gvr_nb<f16, 1, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s);
+        else rc = ksplit ? gvr_nb<bf16, 4, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s)
+                         : gvr_nb<bf16, 1, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s);
+        if (rc != RSVLD_OK) return rc;
+    }
+    return rsvld_check_launch();
+}
+}  // namespace
+
+extern "C" int rsvld_gemv_rows_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual,
+                                     int glu, void* y, int N, int K, int B, int dtype, void* stream) {
+    if (!w || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % 8 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // as gemv_launch
+    if (((uintptr_t)w | (uintptr_t)x | (uintptr_t)norm_w) & 15) return RSVLD_EINVAL;
+    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
+    return gvr_launch<false>(w, nullptr, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, B, dtype, gemv_ksplit(N, K), stream);
+}
+
+extern "C" int rsvld_gemv_w8_rows_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                                        const void* residual, int glu, void* y, int N, int K, int B, int dtype, void* stream) {
+    if (!q || !scale || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % 16 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // as rsvld_gemv_w8_fused
+    if ((((uintptr_t)q | (uintptr_t)x | (uintptr_t)norm_w) & 15) || ((uintptr_t)scale & 3)) return RSVLD_EINVAL;
+    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
+    return gvr_launch<true>(q, scale, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, B, dtype, gemv_w8_ksplit(N, K), stream);
+}
+
+extern "C" size_t rsvld_llama_decode_attention_rows_ws_bytes(int n_q, int n_kv, int max_len, int B) {
+    if (B < 1 || B > RSVLD_DECODE_MAX_ROWS) return 0;
+    return (size_t)B * rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len);
+}
+
+extern "C" int rsvld_llama_decode_attention_rows(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
+                                                 void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
+                                                 void* stream) {
+    if (!qkv || !cosv || !sinv || !pos || !kcache || !vcache || !out || !ws) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (n_q <= 0 || n_kv <= 0 || max_len <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
+    if (head_dim != DA_HD || n_q % n_kv != 0 || n_q / n_kv > DA_GMAX) return RSVLD_EUNSUPPORTED;
+    if (((uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)qkv) & 15) return RSVLD_EINVAL;
+    const int nchunk = (max_len + DA_CH - 1) / DA_CH;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == RSVLD_F16) {
+        hipLaunchKernelGGL((da_kernel<f16>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const f16*)qkv, (const f16*)cosv, (const f16*)sinv,
+                           (const long long*)pos, (f16*)kcache, (f16*)vcache, ws, n_q, n_kv, max_len, scale);
+        hipLaunchKernelGGL((da_combine_kernel<f16>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (f16*)out, n_q, n_kv, nchunk);
+    } else {
+        hipLaunchKernelGGL((da_kernel<bf16>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const bf16*)qkv, (const bf16*)cosv, (const bf16*)sinv,
+                           (const long long*)pos, (bf16*)kcache, (bf16*)vcache, ws, n_q, n_kv, max_len, scale);
+        hipLaunchKernelGGL((da_combine_kernel<bf16>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (bf16*)out, n_q, n_kv, nchunk);
     }
     return rsvld_check_launch();
 }

@@ -168,6 +168,28 @@ class SuperResolutionPipeline:
                                    prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed,
                                    decode_weights=self.cfg.caption_weights)[0]
 
+    def run_stage2_captioning_batch(self, sr_images):
+        """``run_stage2_captioning`` for the Stage-1 images of several inputs in ONE token loop (``infer_dir --caption_batch``) -> a list
+        of caption strings, each the string ``run_stage2_captioning`` returns for that image alone (every row is seeded as the single
+        call seeds it; ``llava_next.FastDecoder.generate_batch``)."""
+        if self.cfg.caption:
+            return [self.cfg.caption] * len(sr_images)
+        if self.cfg.no_llava or self.llava_model is None:
+            return [""] * len(sr_images)
+        import yaml
+        from . import llava_next as LN
+        with open(self.cfg.prompt_yaml, "r", encoding="utf-8") as f:
+            img_prompt = yaml.safe_load(f)["img_prompt"].format(DEFAULT_IMAGE_TOKEN=LN.DEFAULT_IMAGE_TOKEN)
+        dev = self.cfg.base_model_device
+        views = []
+        for im in sr_images:
+            v = LN.process_images([im], self.llava_image_processor, self.llava_model.config)
+            views.append([t.to(dtype=torch.float16, device=dev) for t in v])
+        seeds = None if self.cfg.seed < 0 else [self.cfg.seed] * len(sr_images)
+        return LN.get_img_describe_batch(image_tensors=views, images=list(sr_images), model=self.llava_model, tokenizer=self.llava_tokenizer,
+                                         prompt=img_prompt, max_new_tokens=256, device=dev, seeds=seeds,
+                                         decode_weights=self.cfg.caption_weights)
+
     def _stage2_input(self, sr_image):
         if self.cfg.device_io:
             # Stage 1's own device copy when ``sr_image`` is its hand-off image; any other image is uploaded as uint8

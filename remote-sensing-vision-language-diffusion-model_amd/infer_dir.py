@@ -6,7 +6,11 @@ are loaded once.
 
 Multi-GPU: launch one process per GPU with ``python -m torch.distributed.run --nproc-per-node N -m rsvld_amd.infer_dir ...``;
 image i is processed by rank i mod N (rsvld_amd.parallel.shard_indices), no communication is needed because every
-rank writes its own PNGs."""
+rank writes its own PNGs.
+
+``--caption_batch N`` (1..8): a rank walks its images in groups of N -- Stage 1 of each image, ONE caption pass for the group (the
+captioner's weights are streamed once per token for all N captions), Stage 2 of each image with its caption; the same PNGs as N = 1
+for a fixed ``--seed``."""
 import argparse
 import gc
 import traceback
@@ -22,7 +26,11 @@ EXTS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 
 class ImageBatchProcessor:
     def __init__(self, image_dir, save_dir, upscale=8, num_steps=50, seed=42, img_threshold=0.3, sr3_steps=0, device="cuda:0",
-                 no_llava=False, fp32=False, split=False, vae_split=False, tolerance=False, device_io=False, caption_weights="native"):
+                 no_llava=False, fp32=False, split=False, vae_split=False, tolerance=False, device_io=False, caption_weights="native",
+                 caption_batch=1):
+        if not isinstance(caption_batch, int) or not 1 <= caption_batch <= 8:
+            raise ValueError(f"ImageBatchProcessor: caption_batch={caption_batch!r}, expected 1..8")
+        self.caption_batch = caption_batch
         self.files = sorted(p for p in Path(image_dir).iterdir() if p.suffix.lower() in EXTS)
         self.save_dir, self.seed = Path(save_dir), seed
         self.save_dir.mkdir(parents=True, exist_ok=True)
@@ -44,8 +52,62 @@ class ImageBatchProcessor:
             torch.manual_seed(self.seed)
         return self.pipe.process()
 
+    # ---- caption_batch > 1: Stage 1 of every image of a group, ONE batched caption pass, then Stage 2 of every image with its caption.
+    # The PNGs are those of the one-by-one loop, byte for byte, for a fixed seed: Stage 2 of an image starts from the generator state
+    # (host and device) its Stage 1 left -- the caption pass samples from generators of its own in either order -- and every caption row
+    # is seeded as the single call seeds it.
+    @staticmethod
+    def _rng_state():
+        return torch.get_rng_state(), (torch.cuda.get_rng_state() if torch.cuda.is_available() else None)
+
+    @staticmethod
+    def _set_rng_state(state):
+        torch.set_rng_state(state[0])
+        if state[1] is not None:
+            torch.cuda.set_rng_state(state[1])
+
+    def _process_group(self, paths, rank, done, failed):
+        staged = []
+        for path in paths:
+            try:
+                cfg = PipelineConfig(input_img=str(path), **self.kw)
+                if self.pipe is None:
+                    self.pipe = SuperResolutionPipeline(cfg)
+                else:
+                    self.pipe.cfg = cfg
+                if self.seed >= 0:
+                    torch.manual_seed(self.seed)
+                sr3 = self.pipe.run_stage1_sr3_upscale(cfg.input_path)
+                staged.append((path, cfg, sr3, self._rng_state(), getattr(self.pipe, "_handoff", None)))
+            except Exception:                                   # this image leaves the group
+                failed.append(path)
+                print(f"[rank {rank}] failed on {path}:\n{traceback.format_exc()}")
+        captions = None
+        if len(staged) > 1:
+            try:
+                captions = self.pipe.run_stage2_captioning_batch([s[2] for s in staged])
+            except Exception:                                   # one bad image must cost one image: caption them one by one below
+                print(f"[rank {rank}] the batched caption pass failed, captioning one by one:\n{traceback.format_exc()}")
+        for n, (path, cfg, sr3, rng, handoff) in enumerate(staged):
+            try:
+                self.pipe.cfg = cfg
+                self.pipe._handoff = handoff
+                self._set_rng_state(rng)
+                caption = captions[n] if captions is not None else self.pipe.run_stage2_captioning(sr3)
+                done += self.pipe.run_stage3_refinement(sr3, caption)
+            except Exception:
+                failed.append(path)
+                print(f"[rank {rank}] failed on {path}:\n{traceback.format_exc()}")
+        gc.collect()
+        torch.cuda.empty_cache()
+
     def run(self, rank=0, world=1):
         done, failed = [], []
+        if self.caption_batch > 1:
+            mine = [self.files[i] for i in parallel.shard_indices(len(self.files), rank, world)]
+            for g in range(0, len(mine), self.caption_batch):
+                self._process_group(mine[g:g + self.caption_batch], rank, done, failed)
+            return done, failed
         for i in parallel.shard_indices(len(self.files), rank, world):
             path = self.files[i]
             try:
@@ -80,6 +142,9 @@ def build_parser():
     p.add_argument("--device_io", action="store_true", help="the image steps around both stages on the GPU (rsvld_amd.imageops)")
     p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
                    "the checkpoint's 16-bit ones, or e4m3 bytes with a scale per row (opt-in; see INTEGRATION.md)")
+    p.add_argument("--caption_batch", type=int, default=1, choices=range(1, 9), metavar="N", help="caption the Stage-1 images of N (1..8) "
+                   "inputs in one token loop (the captioner's weights are streamed once per token for all of them); the same captions "
+                   "and PNGs as N = 1 for a fixed --seed")
     return p
 
 
@@ -89,7 +154,8 @@ def main(argv=None):
     torch.cuda.set_device(local)
     proc = ImageBatchProcessor(a.image_dir, a.save_dir, a.upscale, a.num_steps, a.seed, a.img_threshold, a.sr3_steps,
                                device=f"cuda:{local}", no_llava=a.no_llava, fp32=a.fp32, split=a.split, vae_split=a.vae_split,
-                               tolerance=a.tolerance, device_io=a.device_io, caption_weights=a.caption_weights)
+                               tolerance=a.tolerance, device_io=a.device_io, caption_weights=a.caption_weights,
+                               caption_batch=a.caption_batch)
     done, failed = proc.run(rank, world)
     print(f"[rank {rank}] wrote {len(done)} images, {len(failed)} failures")
 

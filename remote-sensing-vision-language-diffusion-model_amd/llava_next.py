@@ -311,14 +311,26 @@ class FastDecoder:
     fused decode step streams THOSE -- half the bytes of a loop bound by nothing else; activations, the KV cache, accumulation, the
     fused neighbours and sampling are unchanged.  The prefill keeps the 16-bit weights, so the packs come ON TOP of them: 8 GB beside
     the 16 GB that stay resident for the 8 B decoder.  The mode needs the fused decode step (``_fused_ok``) and ``K % 16 == 0`` in
-    every packed product; where either fails the decoder raises -- it never falls back to the native weights silently."""
+    every packed product; where either fails the decoder raises -- it never falls back to the native weights silently.
+
+    ``batch``: 1 (default) is the decoder described above.  ``batch=B`` (<= 8, opt-in) allocates ``[B, kv_heads, max_len, head_dim]`` caches
+    and adds ``generate_batch``: up to ``B`` captions in ONE token loop, the weights streamed once per step for all of them
+    (``rsvld_amd.decode_rows``), each caption token for token what ``generate`` gives for its prompt alone; ``generate`` itself keeps
+    working on such a decoder (in cache row 0)."""
 
     WEIGHTS = ("native", "e4m3")
 
-    def __init__(self, model, max_len, weights="native"):
+    MAX_BATCH = 8            # RSVLD_DECODE_MAX_ROWS
+
+    def __init__(self, model, max_len, weights="native", batch=1):
         if weights not in self.WEIGHTS:
             raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
-        self.weights = weights
+        if not isinstance(batch, int) or not 1 <= batch <= self.MAX_BATCH:
+            raise ValueError(f"FastDecoder: batch={batch!r}, expected 1..{self.MAX_BATCH}")
+        self.weights, self.batch = weights, batch
+        self._row = 0            # the cache row ``forward`` reads and writes (``generate_batch`` prefills row after row)
+        self._rows = {}          # generate_batch: number of sequences -> the captured step (static buffers + graph)
+        self._ws_rows = None
         cfg = model.config
         self.model, self.max_len = model, int(max_len)
         self.layers = list(model.model.layers)
@@ -326,7 +338,7 @@ class FastDecoder:
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         p = next(model.parameters())
         self.dev, self.dt = p.device, p.dtype
-        shape = (1, self.n_kv, self.max_len, self.hd)
+        shape = (batch, self.n_kv, self.max_len, self.hd)
         self.k = [torch.zeros(shape, device=self.dev, dtype=self.dt) for _ in self.layers]
         self.v = [torch.zeros(shape, device=self.dev, dtype=self.dt) for _ in self.layers]
         self.cols = torch.arange(self.max_len, device=self.dev)
@@ -442,12 +454,13 @@ class FastDecoder:
             qk = qkv[:, :nq + nkv]
             half = hd // 2
             qk = qk * cos + torch.cat((-qk[..., half:], qk[..., :half]), dim=-1) * sin     # rotary embedding on q and k at once
-            self.k[i][0].index_copy_(1, pos, qk[:, nq:].transpose(0, 1))
-            self.v[i][0].index_copy_(1, pos, qkv[:, nq + nkv:].transpose(0, 1))
+            kc, vc = self.k[i][self._row], self.v[i][self._row]
+            kc.index_copy_(1, pos, qk[:, nq:].transpose(0, 1))
+            vc.index_copy_(1, pos, qkv[:, nq + nkv:].transpose(0, 1))
             q = qk[:, :nq].reshape(T, nkv, g, hd).permute(1, 0, 2, 3).reshape(nkv, T * g, hd)  # [kv head, (t, q-in-group), hd]
-            sc = torch.matmul(q, self.k[i][0].transpose(1, 2)).float().view(nkv, T, g, self.max_len)
+            sc = torch.matmul(q, kc.transpose(1, 2)).float().view(nkv, T, g, self.max_len)
             pr = torch.softmax(sc * scale + bias[None, :, None, :], dim=-1).to(self.dt).view(nkv, T * g, self.max_len)
-            o = torch.matmul(pr, self.v[i][0]).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
+            o = torch.matmul(pr, vc).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
             h = h + self._lin(o, layer.self_attn.o_proj.weight, layer.self_attn.o_proj.bias)
             x = self._rms(h, layer.post_attention_layernorm)
             gu = self._lin(x, self.wgu[i])
@@ -490,7 +503,8 @@ class FastDecoder:
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
             p_qkv, p_o, p_gu, p_down = packs[i]
             qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
-            o = ops.llama_decode_attention(qkv, cos, sin, pos, self.k[i][0], self.v[i][0], self.n_q, self.n_kv, scale, ws=self._ws)
+            o = ops.llama_decode_attention(qkv, cos, sin, pos, self.k[i][self._row], self.v[i][self._row], self.n_q, self.n_kv, scale,
+                                           ws=self._ws)
             op = layer.self_attn.o_proj
             h = gemv(p_o, op.weight, o, op.bias, residual=h)
             gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
@@ -498,7 +512,7 @@ class FastDecoder:
         head = self.model.lm_head
         return gemv(packs[-1], head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))[None]
 
-    def _pick(self, logits, do_sample, temperature, top_k=0, top_p=1.0):
+    def _pick(self, logits, do_sample, temperature, top_k=0, top_p=1.0, generator=None):
         """``generate``'s sampling chain (transformers' TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial).
         The reference calls ``generate(do_sample=True, temperature=0.2)`` (models/util.py:50-60) and thereby inherits the generation
         config's ``top_k`` (transformers' default: 50): sampling the full softmax instead would be a different sampler."""
@@ -513,7 +527,7 @@ class FastDecoder:
             remove = srt.softmax(dim=-1).cumsum(dim=-1) <= (1.0 - top_p)
             remove[..., -1:] = False                                   # min_tokens_to_keep = 1
             scores = scores.masked_fill(remove.scatter(-1, idx, remove), float("-inf"))
-        return torch.multinomial(torch.softmax(scores, dim=-1), 1)[:, 0]
+        return torch.multinomial(torch.softmax(scores, dim=-1), 1, generator=generator)[:, 0]
 
     def _sampling_defaults(self, do_sample, top_k, top_p):
         """``None`` = what ``generate`` would take from the model's generation_config for a sampling call (top_k 50, top_p 1.0 unless
@@ -574,6 +588,156 @@ class FastDecoder:
             self.profile.update(prompt_tokens=T0, prefill_s=t_prefill - t_start, decode_s=time.perf_counter() - t_prefill,
                                 new_tokens=len(out))
         return torch.cat(out)
+
+    # ------------------------------------------------------------------ several captions in one token loop
+    def _forward_rows(self, h, pos):
+        """``_forward_fused`` for ``n`` sequences: ``h [n, H]`` = the embeddings of their newest tokens, ``pos [n]`` (long, on the device)
+        their positions -> logits ``[n, vocab]``; the caches of rows ``0 .. n - 1`` are updated at ``pos``.  The weights are streamed ONCE
+        for all rows (``rsvld_amd.decode_rows``), and row ``b`` of every operator is bit for bit the single-row operator on row ``b``."""
+        from . import decode_rows as DR
+        m = self.model.model
+        n = h.shape[0]
+        cos, sin = m.rotary_emb(h[None], pos[None])                                # [1, n, hd]
+        cos, sin = cos[0].contiguous(), sin[0].contiguous()
+        h = h.contiguous()
+        scale = self.hd ** -0.5
+        lib = DR.L.load()
+        if self._ws_rows is None:
+            # ONE workspace for the decoder's life, sized for ``batch`` rows: the captured steps of ``_rows`` hold its address, so it is
+            # never replaced (a buffer grown per row count would be freed under the graphs captured with fewer rows)
+            need = int(lib.rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
+            self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
+        if self._packs is not None:
+            def gemv(which, w, *a, **kw):
+                return DR.gemv_w8_rows(*which, *a, **kw)
+        else:
+            def gemv(which, w, *a, **kw):
+                return DR.gemv_rows(w, *a, **kw)
+        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
+        for i, layer in enumerate(self.layers):
+            n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+            p_qkv, p_o, p_gu, p_down = packs[i]
+            qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
+            o = DR.llama_decode_attention_rows(qkv, cos, sin, pos, self.k[i][:n], self.v[i][:n], self.n_q, self.n_kv, scale, ws=self._ws_rows)
+            op = layer.self_attn.o_proj
+            h = gemv(p_o, op.weight, o, op.bias, residual=h)
+            gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
+            h = gemv(p_down, layer.mlp.down_proj.weight, gu, None, glu=True, residual=h)
+        head = self.model.lm_head
+        return gemv(packs[-1], head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))
+
+    def _row_generators(self, n, seeds):
+        if seeds is None:
+            return [None] * n
+        if len(seeds) != n:
+            raise ValueError(f"FastDecoder.generate_batch: {len(seeds)} seeds for {n} prompts")
+        return [torch.Generator(device=self.dev).manual_seed(int(s)) for s in seeds]
+
+    @torch.no_grad()
+    def generate_batch(self, inputs_embeds, max_new_tokens, do_sample=False, temperature=1.0, eos_token_id=None, seeds=None, use_graph=None,
+                       top_k=None, top_p=None):
+        """``generate`` for up to ``batch`` prompts (a list of ``[1, T_b, H]``, lengths may differ) in ONE token loop -> a list of token
+        tensors, each EQUAL to what ``generate`` returns for that prompt alone: the prefill runs prompt after prompt through ``forward``
+        into the prompt's cache row, the decode step of all rows runs through the multi-row operators (bit-identical per row), captured
+        once per number of rows.  Sampling: row ``b`` draws from a generator of its own seeded ``seeds[b]`` -- the draws of the
+        one-at-a-time call under ``torch.random.fork_rng`` + ``torch.manual_seed(seeds[b])``; the caller's generators are not touched
+        (``seeds=None``: every row draws from the current default generator).  A row that has emitted an end token stops: its position
+        is frozen and what the step computes for it is discarded; the loop ends when every row has.  Where the fused step is not
+        available (a CPU decoder, ``_fused_ok``) the prompts go through ``generate`` one after another, with one warning."""
+        n = len(inputs_embeds)
+        if not 1 <= n <= self.batch:
+            raise ValueError(f"FastDecoder.generate_batch: {n} prompts for a decoder built with batch={self.batch}")
+        T0s = [int(e.shape[1]) for e in inputs_embeds]
+        if max(T0s) + max_new_tokens > self.max_len:
+            raise ValueError(f"FastDecoder: prompt {max(T0s)} + {max_new_tokens} new tokens exceed the cache ({self.max_len})")
+        if seeds is not None and len(seeds) != n:
+            raise ValueError(f"FastDecoder.generate_batch: {len(seeds)} seeds for {n} prompts")
+        if not self._fused_ok(inputs_embeds[0].to(self.dt)):
+            import warnings
+            warnings.warn("FastDecoder.generate_batch: the fused decode step is not available for this model / device; the prompts are "
+                          "captioned one after another (same tokens)")
+            outs = []
+            for b, e in enumerate(inputs_embeds):
+                kw = dict(do_sample=do_sample, temperature=temperature, eos_token_id=eos_token_id, use_graph=use_graph, top_k=top_k, top_p=top_p)
+                if seeds is None:
+                    outs.append(self.generate(e, max_new_tokens, **kw))
+                else:
+                    with torch.random.fork_rng(devices=[self.dev] if self.dev.type == "cuda" else []):
+                        torch.manual_seed(int(seeds[b]))
+                        outs.append(self.generate(e, max_new_tokens, **kw))
+            return outs
+        top_k, top_p = self._sampling_defaults(do_sample, top_k, top_p)
+        use_graph = True if use_graph is None else use_graph
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        embed = self.model.model.embed_tokens
+        gens = self._row_generators(n, seeds)
+        if self.profile is not None:
+            import time
+            torch.cuda.current_stream().synchronize()
+            t_start = time.perf_counter()
+        first = []
+        try:
+            for b, e in enumerate(inputs_embeds):                      # prefill: matrix-bound, one prompt at a time, into cache row b
+                self._row = b
+                logits = self.forward(e.to(self.dt), torch.arange(T0s[b], device=self.dev))
+                first.append(self._pick(logits, do_sample, temperature, top_k, top_p, generator=gens[b]))
+        finally:
+            self._row = 0
+        toks = torch.cat(first)                                        # [n]
+        pos = torch.tensor(T0s, device=self.dev)
+        if self.profile is not None:
+            torch.cuda.current_stream().synchronize()
+            t_prefill = time.perf_counter()
+        st = self._rows.get(n) if use_graph else None
+        if use_graph and st is None:
+            st = {"tok": toks.clone(), "pos": pos.clone()}
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                              # warm-up off the capture stream; it rewrites the cache slots
+                self._forward_rows(embed(st["tok"]), st["pos"])        # at ``pos`` with the same values
+            torch.cuda.current_stream().wait_stream(side)
+            st["graph"] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(st["graph"]):                        # one stream, a linear chain of launches
+                st["logits"] = self._forward_rows(embed(st["tok"]), st["pos"])
+            self._rows[n] = st
+        host = toks.tolist()
+        out = [[t] for t in first]
+        done = [bool(eos) and host[b] in eos for b in range(n)]
+        live = torch.tensor([0 if d else 1 for d in done], device=self.dev)
+        steps = 0
+        for _ in range(1, max_new_tokens):
+            if all(done):
+                break
+            if use_graph:
+                st["tok"].copy_(toks)
+                st["pos"].copy_(pos)
+                st["graph"].replay()
+                logits = st["logits"]
+            else:
+                logits = self._forward_rows(embed(toks), pos)
+            if do_sample:                                              # row by row: the shapes, kernels and draws of the single call
+                # (a finished row draws nothing: with ``seeds=None`` all rows share the caller's generator)
+                new = torch.cat([toks[b:b + 1] if done[b] else self._pick(logits[b:b + 1], True, temperature, top_k, top_p, generator=gens[b])
+                                 for b in range(n)])
+            else:
+                new = logits.argmax(-1)
+            steps += 1
+            toks = torch.where(live.bool(), new, toks)                 # a finished row keeps its last token and its position
+            pos = pos + live
+            host = new.tolist()
+            changed = False
+            for b in range(n):
+                if not done[b]:
+                    out[b].append(new[b:b + 1])
+                    if eos and host[b] in eos:
+                        done[b] = changed = True
+            if changed:
+                live = torch.tensor([0 if d else 1 for d in done], device=self.dev)
+        if self.profile is not None:
+            torch.cuda.current_stream().synchronize()
+            self.profile.update(prompt_tokens=T0s, prefill_s=t_prefill - t_start, decode_s=time.perf_counter() - t_prefill,
+                                new_tokens=[len(o) for o in out], steps=steps, rows=n)
+        return [torch.cat(o) for o in out]
 
 
 def normalise_checkpoint_keys(state_dict, model):
@@ -796,3 +960,53 @@ def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, d
         dec = FastDecoder(model, -(-need // 256) * 256, weights=weights)
         model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
+
+
+def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
+                              seeds=None):
+    """``caption_tokens_fast`` for several images under ONE prompt: ``images[b]`` / ``image_sizes[b]`` are the views and the size of image
+    ``b`` -> a list of token tensors, each equal to ``caption_tokens_fast`` on that image alone (under ``seeds[b]``, see
+    ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another weight mode, or
+    for a longer cache -- like ``caption_tokens_fast``, which goes on using a decoder with more rows than one.  The cache length is this
+    group's longest prompt plus the new tokens, rounded up to 256 (kept if the decoder's is longer); the prefill runs over it, so the equality
+    with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it)."""
+    embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
+    need = max(e.shape[1] for e in embeds) + max_new_tokens
+    dec = getattr(model, "_fast_decoder", None)
+    if dec is not None and (dec.stale() or dec.weights != weights or dec.batch < len(embeds)):
+        dec = None
+    if dec is None or dec.max_len < need:
+        model.__dict__.pop("_fast_decoder", None)
+        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, batch=len(embeds))
+        model.__dict__["_fast_decoder"] = dec
+    return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
+
+
+def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv_templates=conv_templates,
+                           image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
+                           do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None):
+    """``get_img_describe`` for a list of images (``image_tensors[b]``: the views of ``images[b]``) under one prompt -> a list of captions,
+    caption ``b`` being what ``get_img_describe(image_tensors[b], images[b], ..., seed=seeds[b])[0]`` returns: with the FastDecoder the
+    token loops of all images run as one (the decoder's weights are streamed once per step for all of them); without it the images
+    are captioned one after another.  ``seeds``: one seed per image, or None (sample from the current generator state)."""
+    n = len(images)
+    if len(image_tensors) != n or (seeds is not None and len(seeds) != n):
+        raise ValueError(f"get_img_describe_batch: {len(image_tensors)} view lists and {None if seeds is None else len(seeds)} seeds for {n} images")
+    decode_weights = "native" if decode_weights is None else decode_weights
+    if decode_weights not in FastDecoder.WEIGHTS:
+        raise ValueError(f"get_img_describe_batch: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
+    mdev = next(model.parameters()).device
+    use_fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
+    if not use_fast or _has_logits_warpers(model) or n > FastDecoder.MAX_BATCH:
+        return [get_img_describe(image_tensors[b], images[b], model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
+                                 num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], fast,
+                                 decode_weights)[0] for b in range(n)]
+    if conv_template != "llava_llama_3":
+        raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
+    system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
+    text = llama3_prompt(tokenizer, prompt, system)
+    input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
+    with torch.no_grad():
+        outs = caption_tokens_fast_batch(model, input_ids, image_tensors, [im.size for im in images], max_new_tokens, do_sample, temperature,
+                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds)
+    return [tokenizer.decode(o.cpu().tolist(), skip_special_tokens=True).lstrip() for o in outs]
