@@ -438,13 +438,15 @@ int rsvld_nchw_f32_to_nhwc_f32(const float* src, float* dst, int B, int C, int H
 /* Weight-streaming matrix-vector product of the caption pass's token loop: y[n] = sum_k w[n][k] x[k] (+ bias[n]); w [N][K]
  * row-major, x [K], bias [N] or NULL, y [N], all 16-bit (dtype), fp32 accumulation; K % 8 == 0, K <= 32768.
  * Replaces torch.nn.functional.linear with ONE activation row in the Llama decode step behind models/util.py:17-66
- * (llava/model/language_model/llava_llama.py:118-137): q|k|v, o, gate|up, down projections and lm_head. */
+ * (llava/model/language_model/llava_llama.py:118-137): q|k|v, o, gate|up, down projections and lm_head.
+ * The products have ONE host path, for 1 .. RSVLD_DECODE_MAX_ROWS activation rows (rsvld_gemv_rows_fused / rsvld_gemv_w8_rows_fused below); the
+ * three single-row entry points are its B = 1 call: this one is rsvld_gemv_fused with nothing folded in. */
 int rsvld_gemv(const void* w, const void* x, const void* bias, void* y, int N, int K, int dtype, void* stream);
 /* rsvld_gemv with the element-wise neighbours of a Llama decoder layer's decode step folded in (the same reference call sites; the unfused
  * sequence is ~26 launches per layer, the token loop is launch-bound): norm_w != NULL: x <- RMSNorm(x) * norm_w (LlamaRMSNorm in front of
  * q|k|v, gate|up and lm_head; norm_eps); glu: x holds 2 K elements [gate | up] and the product runs on silu(gate) * up (SwiGLU in front of
  * down_proj); residual != NULL [N]: y <- residual + (w x + bias) (the layer's two residual additions).  Roundings to the 16-bit type where
- * the unfused sequence has them. */
+ * the unfused sequence has them.  = rsvld_gemv_rows_fused(..., B = 1, ...). */
 int rsvld_gemv_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
                      void* y, int N, int K, int dtype, void* stream);
 /* The weights of those products as OCP e4m3 bytes with ONE power-of-two scale per output row (the opt-in "e4m3" mode of the same token
@@ -458,7 +460,7 @@ int rsvld_pack_rows_e4m3(const void* w, void* q, float* scale, int N, int K, int
 /* rsvld_gemv_fused on such weights (the same reference call sites): y[n] = T(scale[n] * sum_k q[n][k] x'[k] + bias[n]), then the residual;
  * x' = x after norm_w / glu exactly as rsvld_gemv_fused stages it (16-bit), fp32 accumulation, the same roundings to the 16-bit type T.
  * x, bias, norm_w, residual, y are 16-bit (dtype); q [N][K] uint8 and scale [N] fp32 as rsvld_pack_rows_e4m3 writes them.
- * K % 16 == 0, K <= 32768; q, x and norm_w 16-byte aligned. */
+ * K % 16 == 0, K <= 32768; q, x and norm_w 16-byte aligned.  = rsvld_gemv_w8_rows_fused(..., B = 1, ...). */
 int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
                         const void* residual, int glu, void* y, int N, int K, int dtype, void* stream);
 /* One decode step of grouped-query attention over a static cache (LlamaAttention.forward with ONE new token, llava_llama.py:118-137 ->
@@ -466,19 +468,21 @@ int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const 
  * embedding, 16-bit); *pos (DEVICE int64: the step is replayed from a hipGraph) = the token's position; kcache / vcache
  * [n_kv][max_len][head_dim] are UPDATED at *pos; out [n_q x head_dim] = softmax(q K^T scale) V over positions <= *pos.  head_dim = 128,
  * n_q / n_kv <= 8.  ws: rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len) bytes of scratch (no initial state).  *pos outside
- * [0, max_len) is clamped into it by the kernel (the host cannot see a device scalar): nothing is written past the cache. */
+ * [0, max_len) is clamped into it by the kernel (the host cannot see a device scalar): nothing is written past the cache.
+ * Both are the B = 1 call of the _rows entry points below. */
 size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len);
 int rsvld_llama_decode_attention(const void* qkv, const void* cos, const void* sin, const int64_t* pos, void* kcache, void* vcache, void* out,
                                  float* ws, int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype, void* stream);
 
 /* The batched token loop (--caption_batch: the captions of several images' Stage-1 outputs in ONE loop; the reference captions image after
  * image, models/util.py:39-60 called from infer_dir.py:196-201): the three operators above for B <= RSVLD_DECODE_MAX_ROWS independent
- * sequences, the weights streamed once for all of them.  CONTRACT: row b of every result is bit for bit what the single-row entry point
- * gives for row b alone -- the same lane-to-k mapping, step order, wave reduction, fixed K-split partial order and roundings per row, the
- * same row / K-split route for (N, K) whatever B is -- so a caption does not depend on which sequences share its batch, or on how many. */
+ * sequences, the weights streamed once for all of them.  These are the operators' implementations; the single-row entry points above
+ * call them with B = 1 (one row runs the single-row kernels, whichever entry point asks).  CONTRACT: row b of every result is bit for bit
+ * what B = 1 gives for row b alone -- the same lane-to-k mapping, step order, wave reduction, fixed K-split partial order and roundings per
+ * row, the same row / K-split route for (N, K) whatever B is -- so a caption does not depend on which sequences share its batch, or on how many. */
 #define RSVLD_DECODE_MAX_ROWS 8
-/* rsvld_gemv_fused for B rows: x [B][K] ([B][2K] with glu), residual and y [B][N], contiguous; w, bias, norm_w are shared by the rows.
- * Every K rsvld_gemv_fused takes, at every B in 1..8 (rows whose staged form does not fit the CU's 160 KiB of LDS together are walked in
+/* The fused product of rsvld_gemv_fused for B rows: x [B][K] ([B][2K] with glu), residual and y [B][N], contiguous; w, bias, norm_w are shared by the rows.
+ * K % 8 == 0, K <= 32768, at every B in 1..8 (rows whose staged form does not fit the CU's 160 KiB of LDS together are walked in
  * groups, one weight pass per group).  B outside 1..RSVLD_DECODE_MAX_ROWS: RSVLD_EINVAL. */
 int rsvld_gemv_rows_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
                           void* y, int N, int K, int B, int dtype, void* stream);

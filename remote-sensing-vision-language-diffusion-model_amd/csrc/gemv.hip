@@ -1,6 +1,9 @@
-// gemv.hip -- y[n] = sum_k W[n][k] x[k] (+ bias[n]) for ONE activation row: the weight-streaming products of the caption pass's
-// token loop (reference: models/util.py:17-66 -> llava/model/language_model/llava_llama.py:118-137 -> Llama decode; 7 linear
-// layers per decoder layer and the 128 256-row lm_head with M = 1).  HBM-bound: every weight byte is read once and used once,
+// gemv.hip -- y[b][n] = sum_k W[n][k] x[b][k] (+ bias[n]) for B = 1 .. RSVLD_DECODE_MAX_ROWS activation rows: the weight-streaming products
+// of the caption pass's token loop (reference: models/util.py:17-66 -> llava/model/language_model/llava_llama.py:118-137 -> Llama decode;
+// 7 linear layers per decoder layer and the 128 256-row lm_head with M = 1; B > 1: the batched token loop).  One host path -- one validation,
+// one launcher -- behind the four entry points, the single-row ones being its B = 1 call; one row runs gemv_kernel / gemv_w8_kernel, two and
+// more run gemv_rows_kernel, every row bit-identical to the single-row kernels.
+// HBM-bound: every weight byte is read once and used once,
 // so there is no LDS tile and no MFMA -- weights go straight to registers in 16-byte pieces (cdna_hip_programming.md section 5,
 // "GEMV / M <= 16 decode weights": load straight to VGPRs, deep unroll, late wait), x sits in LDS, accumulation is fp32.
 // A wave owns RPW output rows at a time and keeps RPW x 2 sixteen-byte weight loads in flight per lane; the 64 partial sums of a row
@@ -8,8 +11,6 @@
 // Round 5, KS = 4: layers with few output rows (o_proj / down_proj / q|k|v of the 8 B decoder: 4 096 .. 6 144 rows = 256 .. 384 workgroups
 // of 16 rows, ONE per CU with 32 KiB of weight loads in flight where ~64 KiB per CU are needed to keep HBM busy) run with the four waves
 // of a workgroup SPLITTING K for the same GV_RPW rows: four times the workgroups, partial sums through LDS.
-// gemv_rows_kernel (behind the decode attention): the same products for up to RSVLD_DECODE_MAX_ROWS activation rows per weight pass (the
-// batched token loop), every row bit-identical to the single-row kernels.
 #include "rsvld_common.h"
 #include <type_traits>
 
@@ -612,45 +613,112 @@ __global__ __launch_bounds__(64 * GV_WAVES, GVR_MIN_WAVES) void gemv_rows_kernel
     }
 }
 
-}  // namespace
+// ---- host side of the products: one validation (gv_check), one launcher (gvr_launch) for the four entry points
+// The row / K-split route of an (N, K) product, stated once.  The number of activation rows must not enter it: a row's summation order is
+// the route's.  Few output rows (fewer than ~4 row-split workgroups per CU of a 256-CU chip): the four waves of a workgroup split K --
+// 16-bit weights where a quarter of K is whole wave steps, e4m3 for every K whose quarter is whole 16-element pieces (K % 64 == 0) and at
+// least two wave steps long in all (K >= 2 048).
+bool gemv_ksplit(int N, int K) { return K % 2048 == 0 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
+bool gemv_w8_ksplit(int N, int K) { return K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
 
-// the row / K-split route of an (N, K) product: one statement for the single-row launches and the multi-row ones (which must not let the
-// number of activation rows into it: a row's summation order is the route's)
-static bool gemv_ksplit(int N, int K) { return K % 2048 == 0 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
-static bool gemv_w8_ksplit(int N, int K) { return K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
+constexpr int GVR_LDS = 160 * 1024;     // LDS of a CU: what one workgroup may hold (registered per kernel above 64 KiB)
+constexpr int GVR_CUS = 256;            // sizes the persistent grid only (any grid gives the same results)
+// dynamic LDS of a launch with nb staged rows (the kernel's layout)
+constexpr size_t gv_lds_bytes(int K, int nb, bool ksplit) {
+    return (size_t)nb * K * 2 + (ksplit ? nb * 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
+}
 
-static int gemv_launch(const void* w, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu, void* y,
-                       int N, int K, int dtype, void* stream) {
-    if (!w || !x || !y || N <= 0 || K <= 0) return RSVLD_EINVAL;
+// the element type of RSVLD_F16 / RSVLD_BF16 (checked by the caller), resolved once: f gets a null T* to name T by
+template <typename F> auto by_dtype(int dtype, F&& f) { return dtype == RSVLD_F16 ? f((f16*)nullptr) : f((bf16*)nullptr); }
+
+// The operands of a product, for all four entry points.  W8: pieces of 16 weights (K % 16) and a scale per row; else pieces of 8 (K % 8).
+// ONE row with its K-split partial sums must fit the 64 KiB of dynamic LDS a launch gets without an opt-in (more rows go in groups).
+// (glu reads x[b] + K as 16-byte pieces too: aligned because x is and K % 8 == 0 makes K * 2 bytes a multiple of 16 -- no check of its own.)
+template <bool W8>
+int gv_check(const void* w, const float* scale, const void* x, const void* norm_w, int glu, const void* y, int N, int K, int B, int dtype) {
+    if (!w || (W8 && !scale) || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
     if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (K % 8 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // 16-byte pieces; x + scratch within the 64 KiB of dynamic LDS a launch gets without an opt-in
-    if (((uintptr_t)w | (uintptr_t)x | (uintptr_t)norm_w) & 15) return RSVLD_EINVAL;
-    if (glu && (norm_w != nullptr || (((uintptr_t)x + (uintptr_t)K * 2) & 15))) return RSVLD_EINVAL;
+    if (K % (W8 ? 16 : 8) != 0 || gv_lds_bytes(K, 1, true) > 65536) return RSVLD_EUNSUPPORTED;
+    if ((((uintptr_t)w | (uintptr_t)x | (uintptr_t)norm_w) & 15) || (W8 && ((uintptr_t)scale & 3))) return RSVLD_EINVAL;
+    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
+    return RSVLD_OK;
+}
+
+// a group of NB >= 2 rows: gemv_rows_kernel on a persistent grid of what the chip holds at once
+template <typename T, int KS, int NB, bool W8>
+int gvr_go(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
+           void* y, int N, int K, hipStream_t s) {
+    constexpr auto KERN = gemv_rows_kernel<T, KS, NB, W8>;
+    const size_t smem = gv_lds_bytes(K, NB, KS == 4);
+    if (smem > 65536 && rsvld_smem_once<KERN>(GVR_LDS) != hipSuccess) return RSVLD_ELAUNCH;
+    const int nblocks = KS == 4 ? (N + GV_RPW - 1) / GV_RPW : (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW);
+    const int per_cu = (int)(GVR_LDS / smem) < 8 ? (int)(GVR_LDS / smem) : 8;     // workgroups of 4 waves a CU holds
+    const int grid = nblocks < GVR_CUS * per_cu ? nblocks : GVR_CUS * per_cu;
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64 * GV_WAVES), smem, s, w, scale, (const T*)x, (const T*)bias, (T*)y, N, K, (const T*)norm_w, eps,
+                       (const T*)residual, glu, nblocks);
+    return RSVLD_OK;
+}
+// one row: the single-row kernels, a workgroup per block of output rows.  (gemv_rows_kernel<.., NB = 1, ..> gives the same bits and is not
+// instantiated: merged into one template with these two, its NB = 1 form timed 0.4-0.5 us above them on down_proj e4m3 and gate|up native,
+// same weight memory, profiles/gemv_merge_ab.txt -- so one row keeps the kernels it had, and B = 1 of the rows entry points gets them too.)
+template <typename T, int KS, bool W8>
+int gv_one(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
+           void* y, int N, int K, hipStream_t s) {
+    const dim3 grid((unsigned)(KS == 4 ? (N + GV_RPW - 1) / GV_RPW : (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW))), block(64 * GV_WAVES);
+    const size_t smem = gv_lds_bytes(K, 1, KS == 4);
+    if constexpr (W8) hipLaunchKernelGGL((gemv_w8_kernel<T, KS>), grid, block, smem, s, (const uint8_t*)w, scale, (const T*)x, (const T*)bias, (T*)y, N, K,
+                                         (const T*)norm_w, eps, (const T*)residual, glu);
+    else hipLaunchKernelGGL((gemv_kernel<T, KS>), grid, block, smem, s, (const T*)w, (const T*)x, (const T*)bias, (T*)y, N, K, (const T*)norm_w, eps,
+                            (const T*)residual, glu);
+    return RSVLD_OK;
+}
+// One instantiation per row count from two on: 2 types x 2 routes x 7 row counts x 2 weight kinds = 56 kernels, each unrolled over its rows.  Cost,
+// measured on this file: it compiles in ~30 s instead of ~4 s and its object grows from 0.12 to 1.4 MB.  The alternative -- only 2 / 4 / 8
+// rows, a group rounded up and the surplus rows masked at the store -- would spend the surplus rows' arithmetic, which is what binds from
+// four rows on (3 rows at the price of 4, 5 at the price of 8): not taken.  Every count is reachable: B itself, and the groups of gvr_launch.
+template <typename T, int KS, bool W8, typename... A> int gvr_nb(int nb, A... a) {
+    switch (nb) {
+        case 1: return gv_one<T, KS, W8>(a...);
+        case 2: return gvr_go<T, KS, 2, W8>(a...);
+        case 3: return gvr_go<T, KS, 3, W8>(a...);
+        case 4: return gvr_go<T, KS, 4, W8>(a...);
+        case 5: return gvr_go<T, KS, 5, W8>(a...);
+        case 6: return gvr_go<T, KS, 6, W8>(a...);
+        case 7: return gvr_go<T, KS, 7, W8>(a...);
+        case 8: return gvr_go<T, KS, 8, W8>(a...);
+    }
+    return RSVLD_EINVAL;
+}
+
+// The product for B rows (B = 1: the single-row entry points), checked, in groups of equal size whose staged rows fit the LDS (K <= 10 200:
+// one group of eight; down_proj's K = 14 336: 2 x 4; the largest K gv_check takes: 4 x 2) -- a group is one launch, and one pass over the weights
+template <bool W8>
+int gvr_launch(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
+               void* y, int N, int K, int B, int dtype, void* stream) {
+    if (const int rc = gv_check<W8>(w, scale, x, norm_w, glu, y, N, K, B, dtype); rc != RSVLD_OK) return rc;
+    glu = glu ? 1 : 0;
+    const bool ksplit = W8 ? gemv_w8_ksplit(N, K) : gemv_ksplit(N, K);
+    const size_t scratch = gv_lds_bytes(K, 0, true), per_row = gv_lds_bytes(K, 1, true) - scratch;
+    const int fit = (int)((GVR_LDS - scratch) / per_row);                      // >= 2: a single row is <= 64 KiB
+    const int gmax = fit < RSVLD_DECODE_MAX_ROWS ? fit : RSVLD_DECODE_MAX_ROWS;
+    const int ngroups = (B + gmax - 1) / gmax, g = (B + ngroups - 1) / ngroups;
     hipStream_t s = (hipStream_t)stream;
-    // few rows (fewer than ~4 row-split workgroups per CU of a 256-CU chip): the four waves of a workgroup split K instead
-    const bool ksplit = gemv_ksplit(N, K);
-    const dim3 grid(ksplit ? (unsigned)((N + GV_RPW - 1) / GV_RPW) : (unsigned)((N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW)));
-    const size_t smem = (size_t)K * 2 + (ksplit ? 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
-    const f16* wh = (const f16*)w; const f16* xh = (const f16*)x; const f16* bh = (const f16*)bias;
-    const bf16* wb = (const bf16*)w; const bf16* xb = (const bf16*)x; const bf16* bb = (const bf16*)bias;
-    if (dtype == RSVLD_F16) {
-        if (ksplit) hipLaunchKernelGGL((gemv_kernel<f16, 4>), grid, dim3(64 * GV_WAVES), smem, s, wh, xh, bh, (f16*)y, N, K, (const f16*)norm_w, eps, (const f16*)residual, glu);
-        else hipLaunchKernelGGL((gemv_kernel<f16, 1>), grid, dim3(64 * GV_WAVES), smem, s, wh, xh, bh, (f16*)y, N, K, (const f16*)norm_w, eps, (const f16*)residual, glu);
-    } else {
-        if (ksplit) hipLaunchKernelGGL((gemv_kernel<bf16, 4>), grid, dim3(64 * GV_WAVES), smem, s, wb, xb, bb, (bf16*)y, N, K, (const bf16*)norm_w, eps, (const bf16*)residual, glu);
-        else hipLaunchKernelGGL((gemv_kernel<bf16, 1>), grid, dim3(64 * GV_WAVES), smem, s, wb, xb, bb, (bf16*)y, N, K, (const bf16*)norm_w, eps, (const bf16*)residual, glu);
+    for (int b0 = 0; b0 < B; b0 += g) {
+        const int nb = B - b0 < g ? B - b0 : g;
+        const char* xg = (const char*)x + (size_t)b0 * (glu ? 2 : 1) * K * 2;
+        const char* rg = residual ? (const char*)residual + (size_t)b0 * N * 2 : nullptr;
+        char* yg = (char*)y + (size_t)b0 * N * 2;
+        const int rc = by_dtype(dtype, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            return ksplit ? gvr_nb<T, 4, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s)
+                          : gvr_nb<T, 1, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s);
+        });
+        if (rc != RSVLD_OK) return rc;
     }
     return rsvld_check_launch();
 }
 
-extern "C" int rsvld_gemv(const void* w, const void* x, const void* bias, void* y, int N, int K, int dtype, void* stream) {
-    return gemv_launch(w, x, bias, nullptr, 0.f, nullptr, 0, y, N, K, dtype, stream);
-}
-
-extern "C" int rsvld_gemv_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
-                                void* y, int N, int K, int dtype, void* stream) {
-    return gemv_launch(w, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, dtype, stream);
-}
+}  // namespace
 
 extern "C" int rsvld_pack_rows_e4m3(const void* w, void* q, float* scale, int N, int K, int dtype, void* stream) {
     if (!w || !q || !scale || N <= 0 || K <= 0) return RSVLD_EINVAL;
@@ -664,143 +732,39 @@ extern "C" int rsvld_pack_rows_e4m3(const void* w, void* q, float* scale, int N,
     return rsvld_check_launch();
 }
 
-extern "C" int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
-                                   const void* residual, int glu, void* y, int N, int K, int dtype, void* stream) {
-    if (!q || !scale || !x || !y || N <= 0 || K <= 0) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (K % 16 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // 16-byte pieces of 16 weights; x' + scratch as gemv_launch
-    if ((((uintptr_t)q | (uintptr_t)x | (uintptr_t)norm_w) & 15) || ((uintptr_t)scale & 3)) return RSVLD_EINVAL;
-    if (glu && (norm_w != nullptr || (((uintptr_t)x + (uintptr_t)K * 2) & 15))) return RSVLD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    // as gemv_launch: few rows (fewer than ~4 row-split workgroups per CU) split K over the four waves -- here for every K whose quarter is
-    // whole 16-element pieces (K % 64 == 0) and at least two wave steps long in all (K >= 2 048)
-    const bool ksplit = gemv_w8_ksplit(N, K);
-    const dim3 grid(ksplit ? (unsigned)((N + GV_RPW - 1) / GV_RPW) : (unsigned)((N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW)));
-    const size_t smem = (size_t)K * 2 + (ksplit ? 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
-    const uint8_t* qw = (const uint8_t*)q;
-    glu = glu ? 1 : 0;
-    if (dtype == RSVLD_F16) {
-        if (ksplit) hipLaunchKernelGGL((gemv_w8_kernel<f16, 4>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const f16*)x, (const f16*)bias, (f16*)y, N, K, (const f16*)norm_w, norm_eps, (const f16*)residual, glu);
-        else hipLaunchKernelGGL((gemv_w8_kernel<f16, 1>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const f16*)x, (const f16*)bias, (f16*)y, N, K, (const f16*)norm_w, norm_eps, (const f16*)residual, glu);
-    } else {
-        if (ksplit) hipLaunchKernelGGL((gemv_w8_kernel<bf16, 4>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const bf16*)x, (const bf16*)bias, (bf16*)y, N, K, (const bf16*)norm_w, norm_eps, (const bf16*)residual, glu);
-        else hipLaunchKernelGGL((gemv_w8_kernel<bf16, 1>), grid, dim3(64 * GV_WAVES), smem, s, qw, scale, (const bf16*)x, (const bf16*)bias, (bf16*)y, N, K, (const bf16*)norm_w, norm_eps, (const bf16*)residual, glu);
-    }
-    return rsvld_check_launch();
-}
-
-extern "C" size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len) {
-    if (n_q <= 0 || n_kv <= 0 || max_len <= 0) return 0;
-    return (size_t)n_q * ((max_len + DA_CH - 1) / DA_CH) * (DA_HD + 2) * sizeof(float);
-}
-
-extern "C" int rsvld_llama_decode_attention(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
-                                            void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype,
-                                            void* stream) {
-    if (!qkv || !cosv || !sinv || !pos || !kcache || !vcache || !out || !ws) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (n_q <= 0 || n_kv <= 0 || max_len <= 0) return RSVLD_EINVAL;
-    if (head_dim != DA_HD || n_q % n_kv != 0 || n_q / n_kv > DA_GMAX) return RSVLD_EUNSUPPORTED;
-    if (((uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)qkv) & 15) return RSVLD_EINVAL;
-    const int nchunk = (max_len + DA_CH - 1) / DA_CH;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == RSVLD_F16) {
-        hipLaunchKernelGGL((da_kernel<f16>), dim3(n_kv, nchunk), dim3(256), 0, s, (const f16*)qkv, (const f16*)cosv, (const f16*)sinv,
-                           (const long long*)pos, (f16*)kcache, (f16*)vcache, ws, n_q, n_kv, max_len, scale);
-        hipLaunchKernelGGL((da_combine_kernel<f16>), dim3(n_q), dim3(DA_HD), 0, s, ws, (f16*)out, n_q, n_kv, nchunk);
-    } else {
-        hipLaunchKernelGGL((da_kernel<bf16>), dim3(n_kv, nchunk), dim3(256), 0, s, (const bf16*)qkv, (const bf16*)cosv, (const bf16*)sinv,
-                           (const long long*)pos, (bf16*)kcache, (bf16*)vcache, ws, n_q, n_kv, max_len, scale);
-        hipLaunchKernelGGL((da_combine_kernel<bf16>), dim3(n_q), dim3(DA_HD), 0, s, ws, (bf16*)out, n_q, n_kv, nchunk);
-    }
-    return rsvld_check_launch();
-}
-
-// ---- multi-row entry points (the batched token loop: B <= RSVLD_DECODE_MAX_ROWS activation rows per weight pass)
-namespace {
-constexpr int GVR_LDS = 160 * 1024;     // LDS of a CU: what one workgroup may hold (registered per kernel above 64 KiB)
-constexpr int GVR_CUS = 256;            // sizes the persistent grid only (any grid gives the same results)
-
-template <typename T, int KS, int NB, bool W8>
-int gvr_go(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
-           void* y, int N, int K, hipStream_t s) {
-    constexpr auto KERN = gemv_rows_kernel<T, KS, NB, W8>;
-    const size_t smem = (size_t)NB * K * 2 + (KS == 4 ? NB * 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
-    if (smem > 65536 && rsvld_smem_once<KERN>(GVR_LDS) != hipSuccess) return RSVLD_ELAUNCH;
-    const int nblocks = KS == 4 ? (N + GV_RPW - 1) / GV_RPW : (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW);
-    const int per_cu = (int)(GVR_LDS / smem) < 8 ? (int)(GVR_LDS / smem) : 8;     // workgroups of 4 waves a CU holds
-    const int grid = nblocks < GVR_CUS * per_cu ? nblocks : GVR_CUS * per_cu;
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(64 * GV_WAVES), smem, s, w, scale, (const T*)x, (const T*)bias, (T*)y, N, K, (const T*)norm_w, eps,
-                       (const T*)residual, glu, nblocks);
-    return RSVLD_OK;
-}
-// One instantiation per row count: 2 types x 2 routes x 8 row counts x 2 weight kinds = 64 kernels, each unrolled over its rows.  Cost,
-// measured on this file: it compiles in ~30 s instead of ~4 s and its object grows from 0.12 to 1.4 MB.  The alternative -- only 2 / 4 / 8
-// rows, a group rounded up and the surplus rows masked at the store -- would spend the surplus rows' arithmetic, which is what binds from
-// four rows on (3 rows at the price of 4, 5 at the price of 8): not taken.  Every count is reachable: B itself, and the groups of gvr_launch.
-template <typename T, int KS, bool W8, typename... A> int gvr_nb(int nb, A... a) {
-    switch (nb) {
-        case 1: return gvr_go<T, KS, 1, W8>(a...);
-        case 2: return gvr_go<T, KS, 2, W8>(a...);
-        case 3: return gvr_go<T, KS, 3, W8>(a...);
-        case 4: return gvr_go<T, KS, 4, W8>(a...);
-        case 5: return gvr_go<T, KS, 5, W8>(a...);
-        case 6: return gvr_go<T, KS, 6, W8>(a...);
-        case 7: return gvr_go<T, KS, 7, W8>(a...);
-        case 8: return gvr_go<T, KS, 8, W8>(a...);
-    }
-    return RSVLD_EINVAL;
-}
-
-// B rows in groups of equal size whose staged rows fit the LDS (K <= 10 200: one group of eight; down_proj's K = 14 336: 2 x 4; the largest
-// K the single-row entry takes: 4 x 2) -- a group is one launch, and one pass over the weights
-template <bool W8>
-int gvr_launch(const void* w, const float* scale, const void* x, const void* bias, const void* norm_w, float eps, const void* residual, int glu,
-               void* y, int N, int K, int B, int dtype, bool ksplit, void* stream) {
-    const size_t per_row = (size_t)K * 2 + 4 * GV_RPW * sizeof(float);
-    const int fit = (int)((GVR_LDS - 16 * sizeof(float)) / per_row);           // >= 2: a single row is <= 64 KiB
-    const int gmax = fit < RSVLD_DECODE_MAX_ROWS ? fit : RSVLD_DECODE_MAX_ROWS;
-    const int ngroups = (B + gmax - 1) / gmax, g = (B + ngroups - 1) / ngroups;
-    hipStream_t s = (hipStream_t)stream;
-    for (int b0 = 0; b0 < B; b0 += g) {
-        const int nb = B - b0 < g ? B - b0 : g;
-        const char* xg = (const char*)x + (size_t)b0 * (glu ? 2 : 1) * K * 2;
-        const char* rg = residual ? (const char*)residual + (size_t)b0 * N * 2 : nullptr;
-        char* yg = (char*)y + (size_t)b0 * N * 2;
-        int rc;
-        if (dtype == RSVLD_F16) rc = ksplit ? gvr_nb<f16, 4, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s)
-                                            : gvr_nb<f16, 1, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s);
-        else rc = ksplit ? gvr_nb<bf16, 4, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s)
-                         : gvr_nb<bf16, 1, W8>(nb, w, scale, xg, bias, norm_w, eps, rg, glu, yg, N, K, s);
-        if (rc != RSVLD_OK) return rc;
-    }
-    return rsvld_check_launch();
-}
-}  // namespace
-
+// ---- the products' entry points: the single-row ones are the B = 1 call
 extern "C" int rsvld_gemv_rows_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual,
                                      int glu, void* y, int N, int K, int B, int dtype, void* stream) {
-    if (!w || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (K % 8 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // as gemv_launch
-    if (((uintptr_t)w | (uintptr_t)x | (uintptr_t)norm_w) & 15) return RSVLD_EINVAL;
-    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
-    return gvr_launch<false>(w, nullptr, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, B, dtype, gemv_ksplit(N, K), stream);
+    return gvr_launch<false>(w, nullptr, x, bias, norm_w, norm_eps, residual, glu, y, N, K, B, dtype, stream);
 }
 
 extern "C" int rsvld_gemv_w8_rows_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
                                         const void* residual, int glu, void* y, int N, int K, int B, int dtype, void* stream) {
-    if (!q || !scale || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (K % 16 != 0 || (size_t)K * 2 + 4 * GV_RPW * sizeof(float) + 16 * sizeof(float) > 65536) return RSVLD_EUNSUPPORTED;   // as rsvld_gemv_w8_fused
-    if ((((uintptr_t)q | (uintptr_t)x | (uintptr_t)norm_w) & 15) || ((uintptr_t)scale & 3)) return RSVLD_EINVAL;
-    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
-    return gvr_launch<true>(q, scale, x, bias, norm_w, norm_eps, residual, glu ? 1 : 0, y, N, K, B, dtype, gemv_w8_ksplit(N, K), stream);
+    return gvr_launch<true>(q, scale, x, bias, norm_w, norm_eps, residual, glu, y, N, K, B, dtype, stream);
 }
 
+extern "C" int rsvld_gemv(const void* w, const void* x, const void* bias, void* y, int N, int K, int dtype, void* stream) {
+    return rsvld_gemv_rows_fused(w, x, bias, nullptr, 0.f, nullptr, 0, y, N, K, 1, dtype, stream);
+}
+
+extern "C" int rsvld_gemv_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
+                                void* y, int N, int K, int dtype, void* stream) {
+    return rsvld_gemv_rows_fused(w, x, bias, norm_w, norm_eps, residual, glu, y, N, K, 1, dtype, stream);
+}
+
+extern "C" int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                                   const void* residual, int glu, void* y, int N, int K, int dtype, void* stream) {
+    return rsvld_gemv_w8_rows_fused(q, scale, x, bias, norm_w, norm_eps, residual, glu, y, N, K, 1, dtype, stream);
+}
+
+// ---- the decode attention for B sequences (da_kernel takes the sequence from blockIdx.z); one sequence is the B = 1 call
 extern "C" size_t rsvld_llama_decode_attention_rows_ws_bytes(int n_q, int n_kv, int max_len, int B) {
-    if (B < 1 || B > RSVLD_DECODE_MAX_ROWS) return 0;
-    return (size_t)B * rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len);
+    if (n_q <= 0 || n_kv <= 0 || max_len <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return 0;
+    return (size_t)B * n_q * ((max_len + DA_CH - 1) / DA_CH) * (DA_HD + 2) * sizeof(float);
+}
+
+extern "C" size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len) {
+    return rsvld_llama_decode_attention_rows_ws_bytes(n_q, n_kv, max_len, 1);
 }
 
 extern "C" int rsvld_llama_decode_attention_rows(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
@@ -813,14 +777,18 @@ extern "C" int rsvld_llama_decode_attention_rows(const void* qkv, const void* co
     if (((uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)qkv) & 15) return RSVLD_EINVAL;
     const int nchunk = (max_len + DA_CH - 1) / DA_CH;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == RSVLD_F16) {
-        hipLaunchKernelGGL((da_kernel<f16>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const f16*)qkv, (const f16*)cosv, (const f16*)sinv,
-                           (const long long*)pos, (f16*)kcache, (f16*)vcache, ws, n_q, n_kv, max_len, scale);
-        hipLaunchKernelGGL((da_combine_kernel<f16>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (f16*)out, n_q, n_kv, nchunk);
-    } else {
-        hipLaunchKernelGGL((da_kernel<bf16>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const bf16*)qkv, (const bf16*)cosv, (const bf16*)sinv,
-                           (const long long*)pos, (bf16*)kcache, (bf16*)vcache, ws, n_q, n_kv, max_len, scale);
-        hipLaunchKernelGGL((da_combine_kernel<bf16>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (bf16*)out, n_q, n_kv, nchunk);
-    }
+    by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        hipLaunchKernelGGL((da_kernel<T>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const T*)qkv, (const T*)cosv, (const T*)sinv,
+                           (const long long*)pos, (T*)kcache, (T*)vcache, ws, n_q, n_kv, max_len, scale);
+        hipLaunchKernelGGL((da_combine_kernel<T>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (T*)out, n_q, n_kv, nchunk);
+        return 0;
+    });
     return rsvld_check_launch();
+}
+
+extern "C" int rsvld_llama_decode_attention(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
+                                            void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype,
+                                            void* stream) {
+    return rsvld_llama_decode_attention_rows(qkv, cosv, sinv, pos, kcache, vcache, out, ws, n_q, n_kv, head_dim, max_len, 1, scale, dtype, stream);
 }

@@ -343,7 +343,6 @@ class FastDecoder:
         self.v = [torch.zeros(shape, device=self.dev, dtype=self.dt) for _ in self.layers]
         self.cols = torch.arange(self.max_len, device=self.dev)
         self._graph = None
-        self._ws = None
         self.fused = True        # the decode step through the fused kernels where their conditions hold (``_fused_ok``); False = the torch-op sequence
         self.profile = None      # a dict: generate() fills in device-synchronised seconds of its prefill and its token loop
         # One weight-streaming GEMV for q | k | v and one for gate | up: the three (two) weight matrices of a layer become views
@@ -476,41 +475,8 @@ class FastDecoder:
                 and self.n_q % self.n_kv == 0 and self.n_q // self.n_kv <= 8 and embeds.shape[-1] % 8 == 0)
 
     def _forward_fused(self, embeds, pos):
-        """ONE new token through the decoder in 7 launches per layer instead of ~26: RMSNorm folded into the q|k|v and gate|up products, rotary
-        embedding + cache write + grouped-query attention in one operator, the residual additions in the o_proj / down_proj epilogues, SwiGLU in
-        down_proj's prologue.  Same arithmetic and the same roundings as ``forward`` up to the order of two fp32 sums (the RMSNorm's mean, the
-        softmax over key chunks) and the 16-bit rounding of P, which this path skips."""
-        from . import ops
-        m = self.model.model
-        cos, sin = m.rotary_emb(embeds, pos[None])                                 # [1, 1, hd]
-        cos, sin = cos.reshape(-1).contiguous(), sin.reshape(-1).contiguous()
-        h = embeds.reshape(-1).contiguous()
-        scale = self.hd ** -0.5
-        if self._ws is None:
-            lib = ops.L.load()
-            self._ws = torch.empty(int(lib.rsvld_llama_decode_attention_ws_bytes(self.n_q, self.n_kv, self.max_len)) // 4, device=self.dev,
-                                   dtype=torch.float32)          # (per-chunk partial results: written before they are read, no initial state)
-        if self._packs is not None:
-            from . import w8
-
-            def gemv(which, w, *a, **kw):        # the same call on the pack of ``w``
-                return w8.gemv_w8(*which, *a, **kw)
-        else:
-            def gemv(which, w, *a, **kw):
-                return ops.gemv_fused(w, *a, **kw)
-        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
-        for i, layer in enumerate(self.layers):
-            n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
-            p_qkv, p_o, p_gu, p_down = packs[i]
-            qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
-            o = ops.llama_decode_attention(qkv, cos, sin, pos, self.k[i][self._row], self.v[i][self._row], self.n_q, self.n_kv, scale,
-                                           ws=self._ws)
-            op = layer.self_attn.o_proj
-            h = gemv(p_o, op.weight, o, op.bias, residual=h)
-            gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
-            h = gemv(p_down, layer.mlp.down_proj.weight, gu, None, glu=True, residual=h)
-        head = self.model.lm_head
-        return gemv(packs[-1], head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))[None]
+        """ONE new token (``embeds [1, 1, H]``) of the sequence in cache row ``_row`` -> logits ``[1, vocab]``: ``_forward_rows`` on that row."""
+        return self._forward_rows(embeds[0], pos, self._row)
 
     def _pick(self, logits, do_sample, temperature, top_k=0, top_p=1.0, generator=None):
         """``generate``'s sampling chain (transformers' TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial).
@@ -590,10 +556,14 @@ class FastDecoder:
         return torch.cat(out)
 
     # ------------------------------------------------------------------ several captions in one token loop
-    def _forward_rows(self, h, pos):
-        """``_forward_fused`` for ``n`` sequences: ``h [n, H]`` = the embeddings of their newest tokens, ``pos [n]`` (long, on the device)
-        their positions -> logits ``[n, vocab]``; the caches of rows ``0 .. n - 1`` are updated at ``pos``.  The weights are streamed ONCE
-        for all rows (``rsvld_amd.decode_rows``), and row ``b`` of every operator is bit for bit the single-row operator on row ``b``."""
+    def _forward_rows(self, h, pos, row0=0):
+        """The decode step of ``n`` sequences in 7 launches per layer instead of ~26: RMSNorm folded into the q|k|v and gate|up products, rotary
+        embedding + cache write + grouped-query attention in one operator, the residual additions in the o_proj / down_proj epilogues, SwiGLU in
+        down_proj's prologue.  Same arithmetic and the same roundings as ``forward`` up to the order of two fp32 sums (the RMSNorm's mean, the
+        softmax over key chunks) and the 16-bit rounding of P, which this path skips.  ``h [n, H]`` = the embeddings of the sequences' newest
+        tokens, ``pos [n]`` (long, on the device) their positions -> logits ``[n, vocab]``; the caches of rows ``row0 .. row0 + n - 1`` are
+        updated at ``pos``.  The weights are streamed ONCE for all rows (``rsvld_amd.decode_rows``), and row ``b`` of every operator is bit
+        for bit the operator on row ``b`` alone."""
         from . import decode_rows as DR
         m = self.model.model
         n = h.shape[0]
@@ -601,14 +571,14 @@ class FastDecoder:
         cos, sin = cos[0].contiguous(), sin[0].contiguous()
         h = h.contiguous()
         scale = self.hd ** -0.5
-        lib = DR.L.load()
         if self._ws_rows is None:
             # ONE workspace for the decoder's life, sized for ``batch`` rows: the captured steps of ``_rows`` hold its address, so it is
-            # never replaced (a buffer grown per row count would be freed under the graphs captured with fewer rows)
-            need = int(lib.rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
+            # never replaced (a buffer grown per row count would be freed under the graphs captured with fewer rows, ``_graph`` among
+            # them).  Per-chunk partial results: written before they are read, no initial state.
+            need = int(DR.ops.L.load().rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
             self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
         if self._packs is not None:
-            def gemv(which, w, *a, **kw):
+            def gemv(which, w, *a, **kw):        # the same call on the pack of ``w``
                 return DR.gemv_w8_rows(*which, *a, **kw)
         else:
             def gemv(which, w, *a, **kw):
@@ -618,7 +588,8 @@ class FastDecoder:
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
             p_qkv, p_o, p_gu, p_down = packs[i]
             qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
-            o = DR.llama_decode_attention_rows(qkv, cos, sin, pos, self.k[i][:n], self.v[i][:n], self.n_q, self.n_kv, scale, ws=self._ws_rows)
+            o = DR.llama_decode_attention_rows(qkv, cos, sin, pos, self.k[i][row0:row0 + n], self.v[i][row0:row0 + n], self.n_q, self.n_kv, scale,
+                                               ws=self._ws_rows)
             op = layer.self_attn.o_proj
             h = gemv(p_o, op.weight, o, op.bias, residual=h)
             gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))

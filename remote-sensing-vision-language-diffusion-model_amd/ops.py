@@ -1342,66 +1342,112 @@ def _attention_split_kernels(q, k, v, heads, scale):
     return Planes(out)
 
 
+# The decode-step operators: ONE implementation each for ``B`` activation rows / sequences (``rsvld_amd.decode_rows`` is their public
+# ``[B, .]`` face, ``w8`` holds the e4m3 product); the single-row functions below are the ``B = 1`` case on the caller's storage.
+MAX_ROWS = 8      # RSVLD_DECODE_MAX_ROWS
+
+
+def _rows(fn, x):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        _bad(fn, "x", f"must be a [B, K] tensor of activation rows, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    B = x.shape[0]
+    if not 1 <= B <= MAX_ROWS:
+        _bad(fn, "x", f"has {B} rows, expected 1..{MAX_ROWS}")
+    return B
+
+
+def _gemv_rows(fn, launch, w, scale, x, bias, norm, residual, glu, *, w8, single):
+    """``fn`` (the public name errors carry; ``launch``: the profiler's) on ``B`` rows: ``w [N, K]`` 16-bit, or (``w8``) e4m3 bytes with
+    ``scale [N]``.  A single-row function reaches the library through its own entry point, which is the ``B = 1`` call of the rows one."""
+    _arg(fn, "q" if w8 else "w", w, torch.uint8 if w8 else _HALF, shape=(None, None))
+    N, K = w.shape
+    if w8 and (N == 0 or K == 0 or K % 16):
+        _bad(fn, "q", f"has shape {tuple(w.shape)}: rows of whole 16-byte pieces of e4m3 (K % 16 == 0) expected")
+    B = 1 if single else _rows(fn, x)
+    nw, eps = (None, 0.0) if norm is None else norm
+    Kx = 2 * K if glu else K
+    if w8:
+        _arg(fn, "scale", scale, torch.float32, numel=N)
+    # a per-row operand: [B, n]; a single-row function takes its row in any shape of n elements and returns [N]
+    if single:
+        dt = _arg(fn, "x", x, _HALF if w8 else w.dtype, numel=Kx).dtype
+    else:
+        dt = _arg(fn, "x", x, _HALF if w8 else w.dtype, shape=(B, Kx)).dtype
+    _arg(fn, "bias", bias, dt, numel=N, optional=True)
+    _arg(fn, "norm weight", nw, dt, numel=Kx, optional=True)
+    if single:
+        _arg(fn, "residual", residual, dt, numel=N, optional=True)
+    else:
+        _arg(fn, "residual", residual, dt, shape=(B, N), optional=True)
+    if glu and nw is not None:
+        _bad(fn, "norm weight", "cannot be combined with glu")
+    _need_gpu(w, scale, x, bias, nw, residual)
+    y = torch.empty(N if single else (B, N), device=x.device, dtype=dt)
+    entry = _GEMV_ENTRY[w8, single]
+    args = (_ptr(x), _ptr(bias), _ptr(nw), float(eps), _ptr(residual), int(glu), _ptr(y), N, K)
+    args = ((_ptr(w), _ptr(scale)) if w8 else (_ptr(w),)) + args + ((_dt(x), _stream()) if single else (B, _dt(x), _stream()))
+    call = getattr(L.load(), entry)
+    _launch(launch, 2.0 * B * N * K, N * K + N * 4 + B * (K + N) * 2 if w8 else (N * K + B * (K + N)) * 2, lambda: L.check(call(*args), entry))
+    return y
+
+
+_GEMV_ENTRY = {(False, True): "rsvld_gemv_fused", (False, False): "rsvld_gemv_rows_fused",
+               (True, True): "rsvld_gemv_w8_fused", (True, False): "rsvld_gemv_w8_rows_fused"}
+
+
 def gemv(w, x, bias=None):
     """``w [N, K]`` (16-bit, rows contiguous) times ONE activation row ``x [K]`` (+ ``bias [N]``) -> ``[N]``: the weight-streaming
-    products of the caption pass's token loop (rsvld_gemv; HBM-bound, no tile, no MFMA)."""
-    _arg("gemv", "w", w, _HALF, shape=(None, None))
-    N, K = w.shape
-    _arg("gemv", "x", x, w.dtype, numel=K)
-    _arg("gemv", "bias", bias, w.dtype, numel=N, optional=True)
-    _need_gpu(w, x, bias)
-    y = torch.empty(N, device=w.device, dtype=w.dtype)
-    lib = L.load()
-    _launch("gemv", 2.0 * N * K, (N * K + K + N) * 2, lambda: L.check(
-        lib.rsvld_gemv(_ptr(w), _ptr(x), _ptr(bias), _ptr(y), N, K, _dt(w), _stream()), "rsvld_gemv"))
-    return y
+    products of the caption pass's token loop (HBM-bound, no tile, no MFMA): ``gemv_fused`` with nothing folded in."""
+    return _gemv_rows("gemv", "gemv", w, None, x, bias, None, None, False, w8=False, single=True)
 
 
 def gemv_fused(w, x, bias=None, *, norm=None, residual=None, glu=False):
     """``gemv`` with the element-wise neighbours of a Llama decode step folded in (rsvld_gemv_fused): ``norm=(weight, eps)``: the product runs
     on RMSNorm(x) * weight; ``glu``: x holds ``[gate | up]`` (2 K elements) and the product runs on silu(gate) * up; ``residual [N]``: the
-    result is residual + (w x + bias)."""
-    _arg("gemv_fused", "w", w, _HALF, shape=(None, None))
-    N, K = w.shape
-    nw, eps = (None, 0.0) if norm is None else norm
-    _arg("gemv_fused", "x", x, w.dtype, numel=2 * K if glu else K)
-    _arg("gemv_fused", "bias", bias, w.dtype, numel=N, optional=True)
-    _arg("gemv_fused", "norm weight", nw, w.dtype, numel=x.numel(), optional=True)
-    _arg("gemv_fused", "residual", residual, w.dtype, numel=N, optional=True)
-    _need_gpu(w, x, bias, nw, residual)
-    y = torch.empty(N, device=w.device, dtype=w.dtype)
+    result is residual + (w x + bias).  ``decode_rows.gemv_rows`` on one row."""
+    return _gemv_rows("gemv_fused", "gemv", w, None, x, bias, norm, residual, glu, w8=False, single=True)
+
+
+def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, single):
+    """``fn`` on ``B`` sequences with caches ``[B, n_kv, max_len, 128]``; ``single``: caches ``[n_kv, max_len, 128]``, one sequence."""
+    _arg(fn, "kcache", kcache, _HALF, shape=(n_kv, None, None) if single else (None, n_kv, None, None))
+    hd, max_len = kcache.shape[-1], kcache.shape[-2]
+    B = 1 if single else kcache.shape[0]
+    if not 1 <= B <= MAX_ROWS:
+        _bad(fn, "kcache", f"holds {B} sequences, expected 1..{MAX_ROWS}")
+    _arg(fn, "vcache", vcache, kcache.dtype, shape=tuple(kcache.shape))
+    for name, t, n in (("qkv", qkv, (n_q + 2 * n_kv) * hd), ("cos", cos, hd), ("sin", sin, hd)):     # (per sequence, as in _gemv_rows)
+        if single:
+            _arg(fn, name, t, kcache.dtype, numel=n)
+        else:
+            _arg(fn, name, t, kcache.dtype, shape=(B, n))
+    if single:
+        _arg(fn, "pos", pos, torch.int64, numel=1)
+    else:
+        _arg(fn, "pos", pos, torch.int64, shape=(B,))
+    _arg(fn, "ws", ws, torch.float32, shape=(None,), optional=True)
+    _need_gpu(qkv, cos, sin, pos, kcache, vcache, ws)
     lib = L.load()
-    _launch("gemv", 2.0 * N * K, (N * K + K + N) * 2, lambda: L.check(
-        lib.rsvld_gemv_fused(_ptr(w), _ptr(x), _ptr(bias), _ptr(nw), float(eps), _ptr(residual), int(glu), _ptr(y), N, K, _dt(w), _stream()),
-        "rsvld_gemv_fused"))
-    return y
+    ws_n = int(lib.rsvld_llama_decode_attention_rows_ws_bytes(n_q, n_kv, max_len, B)) // 4
+    if ws is None:
+        ws = torch.empty(ws_n, device=qkv.device, dtype=torch.float32)
+    elif ws.numel() < ws_n:
+        _bad(fn, "ws", f"has {ws.numel()} fp32 elements, the step needs {ws_n}")
+    out = torch.empty(n_q * hd if single else (B, n_q * hd), device=qkv.device, dtype=qkv.dtype)
+    entry = "rsvld_llama_decode_attention" if single else "rsvld_llama_decode_attention_rows"
+    args = (_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(ws), n_q, n_kv, hd, max_len)
+    args += (float(scale), _dt(qkv), _stream()) if single else (B, float(scale), _dt(qkv), _stream())
+    call = getattr(lib, entry)
+    _launch(fn, 0.0, 0.0, lambda: L.check(call(*args), entry))
+    return out
 
 
 def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None):
     """One decode step of grouped-query attention over a static cache (rsvld_llama_decode_attention): ``qkv`` = the new token's q | k | v rows,
     ``pos`` a DEVICE int64 scalar; the caches ``[n_kv, max_len, 128]`` are updated at ``pos``; ``ws`` (optional, re-usable): an fp32
-    tensor of rsvld_llama_decode_attention_ws_bytes (scratch: no initial state).  A position outside ``[0, max_len)`` is clamped by the kernel.  -> ``[n_q * 128]``."""
-    fn = "llama_decode_attention"
-    _arg(fn, "kcache", kcache, _HALF, shape=(n_kv, None, None))
-    hd, max_len = kcache.shape[-1], kcache.shape[-2]
-    _arg(fn, "vcache", vcache, kcache.dtype, shape=tuple(kcache.shape))
-    _arg(fn, "qkv", qkv, kcache.dtype, numel=(n_q + 2 * n_kv) * hd)
-    _arg(fn, "cos", cos, kcache.dtype, numel=hd)
-    _arg(fn, "sin", sin, kcache.dtype, numel=hd)
-    _arg(fn, "pos", pos, torch.int64, numel=1)
-    _arg(fn, "ws", ws, torch.float32, shape=(None,), optional=True)
-    _need_gpu(qkv, cos, sin, pos, kcache, vcache, ws)
-    lib = L.load()
-    ws_n = int(lib.rsvld_llama_decode_attention_ws_bytes(n_q, n_kv, max_len)) // 4
-    if ws is None:
-        ws = torch.empty(ws_n, device=qkv.device, dtype=torch.float32)
-    elif ws.numel() < ws_n:
-        _bad(fn, "ws", f"has {ws.numel()} fp32 elements, the step needs {ws_n}")
-    out = torch.empty(n_q * hd, device=qkv.device, dtype=qkv.dtype)
-    _launch("llama_decode_attention", 0.0, 0.0, lambda: L.check(
-        lib.rsvld_llama_decode_attention(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(ws), n_q, n_kv,
-                                         hd, max_len, float(scale), _dt(qkv), _stream()), "rsvld_llama_decode_attention"))
-    return out
+    tensor of rsvld_llama_decode_attention_ws_bytes (scratch: no initial state).  A position outside ``[0, max_len)`` is clamped by the kernel.
+    -> ``[n_q * 128]``.  ``decode_rows.llama_decode_attention_rows`` on one sequence."""
+    return _decode_attention_rows("llama_decode_attention", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, True)
 
 
 # ----------------------------------------------------------------------------- small fp32 layers

@@ -38,25 +38,13 @@ def gemv_w8(q, scale, x, bias=None, *, norm=None, residual=None, glu=False):
     """``ops.gemv_fused`` on packed weights (rsvld_gemv_w8_fused): ``q [N, K]`` uint8 and ``scale [N]`` float32 from ``pack_rows_e4m3``,
     ONE 16-bit activation row ``x`` (``[K]``, or ``[2 K]`` = gate | up with ``glu``) -> ``T(scale * (q x') + bias)``, then the residual,
     in ``x``'s type.  ``norm`` / ``glu`` / ``residual`` as in ``ops.gemv_fused``, with its roundings."""
-    _arg("gemv_w8", "q", q, torch.uint8, shape=(None, None))
-    N, K = q.shape
-    if N == 0 or K == 0 or K % 16:
-        _bad("gemv_w8", "q", f"has shape {tuple(q.shape)}: rows of whole 16-byte pieces of e4m3 (K % 16 == 0) expected")
-    nw, eps = (None, 0.0) if norm is None else norm
-    _arg("gemv_w8", "scale", scale, torch.float32, numel=N)
-    _arg("gemv_w8", "x", x, _HALF, numel=2 * K if glu else K)
-    _arg("gemv_w8", "bias", bias, x.dtype, numel=N, optional=True)
-    _arg("gemv_w8", "norm weight", nw, x.dtype, numel=x.numel(), optional=True)
-    _arg("gemv_w8", "residual", residual, x.dtype, numel=N, optional=True)
-    if glu and nw is not None:
-        _bad("gemv_w8", "norm weight", "cannot be combined with glu")
-    _need_gpu(q, scale, x, bias, nw, residual)
-    y = ops.torch.empty(N, device=x.device, dtype=x.dtype)
-    lib = L.load()
-    _launch("gemv_w8", 2.0 * N * K, N * K + N * 4 + (K + N) * 2, lambda: L.check(
-        lib.rsvld_gemv_w8_fused(_ptr(q), _ptr(scale), _ptr(x), _ptr(bias), _ptr(nw), float(eps), _ptr(residual), int(glu), _ptr(y), N, K,
-                                ops._dt(x), _stream()), "rsvld_gemv_w8_fused"))
-    return y
+    return ops._gemv_rows("gemv_w8", "gemv_w8", q, scale, x, bias, norm, residual, glu, w8=True, single=True)
+
+
+def gemv_w8_rows(q, scale, x, bias=None, *, norm=None, residual=None, glu=False):
+    """``gemv_w8`` for ``B`` activation rows (rsvld_gemv_w8_rows_fused; also ``decode_rows.gemv_w8_rows``): ``x [B, K]`` 16-bit
+    (``[B, 2 K]`` with ``glu``), ``residual [B, N]``; ``bias`` and ``norm`` are shared by the rows.  -> ``[B, N]`` in ``x``'s type."""
+    return ops._gemv_rows("gemv_w8_rows", "gemv_w8_rows", q, scale, x, bias, norm, residual, glu, w8=True, single=False)
 
 
 # ----------------------------------------------------------------------------- host model (what the tests compare the kernels with)

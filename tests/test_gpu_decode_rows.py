@@ -185,6 +185,43 @@ def test_generate_batch_with_growing_and_shrinking_row_counts(cuda, llama):
     assert set(decb._rows) == {2, 3}
 
 
+def test_generate_on_a_batch_decoder_touches_its_own_cache_row_only(cuda, llama):
+    """``generate`` is the decode step on ONE row of a ``batch=3`` decoder (cache row ``_row`` = 0): rows 1 and 2 of every layer's caches
+    keep their bits, through the captured graph and eagerly, and row 0 is what was written."""
+    from rsvld_amd import llava_next as LN
+    model, embs = llama
+    decb = LN.FastDecoder(model, MAX_LEN, batch=3)
+    g = torch.Generator().manual_seed(5)
+    for c in decb.k + decb.v:
+        c.copy_(torch.randn(c.shape, generator=g).to(cuda, c.dtype))
+    before = [c.clone() for c in decb.k + decb.v]
+    assert decb._row == 0
+    for use_graph in (True, False):
+        toks = decb.generate(embs[1], NEW, do_sample=False, use_graph=use_graph)
+        assert len(toks) == NEW
+    for c, c0 in zip(decb.k + decb.v, before):
+        assert torch.equal(c[1:], c0[1:]), "generate wrote outside cache row 0"
+        assert not torch.equal(c[0, :, :PROMPTS[1] + NEW - 1], c0[0, :, :PROMPTS[1] + NEW - 1])
+
+
+def test_generate_and_generate_batch_share_one_workspace(cuda, llama):
+    """A graph-captured ``generate``, a ``generate_batch`` of three, then ``generate`` again on ONE decoder: the single-row graph replays
+    after the three-row step used the same attention workspace, and gives the tokens of a fresh ``batch=1`` decoder."""
+    from rsvld_amd import llava_next as LN
+    model, embs = llama
+    dec1 = LN.FastDecoder(model, MAX_LEN)
+    greedy = [dec1.generate(e, NEW, do_sample=False).tolist() for e in embs]
+    del dec1
+    decb = LN.FastDecoder(model, MAX_LEN, batch=3)
+    assert decb.generate(embs[2], NEW, do_sample=False).tolist() == greedy[2]
+    ws = decb._ws_rows
+    assert decb._graph is not None and ws is not None
+    assert [t.tolist() for t in decb.generate_batch(embs, NEW, do_sample=False)] == greedy
+    torch.cuda.empty_cache()
+    assert decb.generate(embs[1], NEW, do_sample=False).tolist() == greedy[1]
+    assert decb._ws_rows is ws and set(decb._rows) == {3}, "the workspace was replaced under a captured step"
+
+
 def test_a_finished_row_draws_nothing_from_a_shared_generator(cuda, llama):
     """``seeds=None``: every row samples from the caller's default generator.  Row 0 ends with its first token, so the batch is one draw
     for row 0 followed by row 1's draws -- what two single calls in a row draw (one new token for prompt 0, then prompt 1 in full).  A

@@ -162,7 +162,7 @@ def test_fast_decoder_fused_decode_step_equals_the_torch_sequence(cuda):
             outs[fused] = dec.generate(emb, 24, do_sample=False).cpu().tolist()
             assert dec._graph is not None
             logits[fused] = dec._logits.float().cpu()
-        assert (dec._ws is not None) == fused            # the fused operators ran (and only then)
+        assert (dec._ws_rows is not None) == fused            # the fused operators ran (and only then)
     d = float((logits[True] - logits[False]).abs().max())
     rng = float(logits[False].abs().max())
     print(f"FastDecoder, fused decode step vs the torch sequence: last-step logits max|d| = {d:.3e} (range {rng:.2f})")

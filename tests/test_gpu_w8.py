@@ -269,7 +269,7 @@ def test_fast_decoder_e4m3_token_loop(cuda):
     del dec_orig
     with torch.no_grad():
         toks = dec_g.generate(emb, 24, do_sample=False)             # through the captured graph
-    assert dec_g._graph is not None and dec_g._ws is not None and len(toks) == 24
+    assert dec_g._graph is not None and dec_g._ws_rows is not None and len(toks) == 24
     graph_last = dec_g._logits.float().cpu()
     dec_e = LN.FastDecoder(twin, 400, weights="e4m3")
     le = _teacher_forced(dec_e, emb, toks[:-1])
