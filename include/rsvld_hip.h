@@ -497,6 +497,32 @@ int rsvld_llama_decode_attention_rows(const void* qkv, const void* cos, const vo
                                       void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
                                       void* stream);
 
+/* The PREFILL of that token loop (opt-in: FastDecoder(prefill="flash"), --caption_prefill flash): causal grouped-query flash attention of T
+ * new positions over one sequence's static cache (LlamaAttention.forward on the whole prompt behind models/util.py:17-66,
+ * llava/model/language_model/llava_llama.py:118-137).  q [T][n_q x head_dim], token-major, rotary embedding already applied, q_tok_stride
+ * elements between the rows of consecutive tokens (>= n_q x head_dim: q may be a column slice of the fused q | k projection);
+ * kcache / vcache [n_kv][max_len][head_dim], the layout of rsvld_llama_decode_attention, READ ONLY here and already holding positions
+ * 0 .. pos0 + T - 1; pos0 >= 0 (a HOST int: the prefill is not graph-captured) = the position of q's first row; out [T][n_q x head_dim],
+ * contiguous: row t = softmax(q[t] K^T scale) V over keys 0 .. pos0 + t of its kv head.  Scores and softmax in fp32 (the scores are never
+ * rounded to 16 bits), P rounded to the 16-bit type as the PV operand only; no workspace, no split over keys.
+ * CONTRACT: output row t is a function of q[t] and of keys / values 0 .. pos0 + t of its kv head only, bit for bit the same whatever T,
+ * the other rows of the call, max_len and the cache contents above pos0 + T - 1 are (NaN included: no cache row above pos0 + T - 1 is
+ * read).  Keys are walked in ascending 64-key tiles on absolute boundaries; a key above a row's position enters that row only as a
+ * probability of exactly 0, and the values of the keys above the last position of the row's wave (32 consecutive (position, head) rows)
+ * are zeros in the registers.  What remains between a row's position and its wave's last -- at most 31 positions, written by this same
+ * prefill -- is multiplied by that exact 0, so those cache rows must be finite, as the caller's own k / v are.
+ * head_dim = 128 and n_q / n_kv <= 8, 16-bit dtype: else RSVLD_EUNSUPPORTED.  RSVLD_EINVAL: T < 1, pos0 < 0, pos0 + T > max_len,
+ * n_q % n_kv != 0, a pointer that is not 16-byte aligned, q_tok_stride % 8 != 0 or < n_q x head_dim. */
+int rsvld_llama_prefill_attention(const void* q, int64_t q_tok_stride, const void* kcache, const void* vcache, void* out, int T, int pos0,
+                                  int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype, void* stream);
+/* Its launch (host only, nothing is launched): a function of (T, n_q, n_kv) alone.  rows_per_wg (position, head-in-group) rows of one kv
+ * head per workgroup, grid_x row blocks x grid_y kv heads, keys_per_tile keys per LDS tile.  Returns what the call returns for these
+ * arguments before it looks at pointers, positions and dtype. */
+typedef struct rsvld_prefill_attention_plan {
+    int32_t grid_x, grid_y, rows_per_wg, keys_per_tile;
+} rsvld_prefill_attention_plan;
+int rsvld_plan_llama_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_prefill_attention_plan* plan);
+
 /* ---------------------------------------------------------------------------------------
  * Split-operand product path (round 4): the producers / consumers of bf16 PLANES around the RSVLD_SPLIT convolutions.
  * "planes [rows][2C]" = per row lo(C) | hi(C) of an fp32 [rows][C] tensor (see RSVLD_SPLIT above); C % 8 == 0.

@@ -70,6 +70,11 @@ class AttentionPlan(C.Structure):
                 ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32)]
 
 
+class PrefillAttentionPlan(C.Structure):
+    """rsvld_prefill_attention_plan (rsvld_plan_llama_prefill_attention, host only)."""
+    _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("rows_per_wg", C.c_int32), ("keys_per_tile", C.c_int32)]
+
+
 # rsvld_attention_plan.row (RSVLD_ATTN_ROW_*): the rows of the launch table of csrc/attention.hip
 ATTN_ROW = {"d64b_nw4": 1, "d64b_nw8": 2, "d64c": 3, "d512b": 4, "d512b_shared": 5, "d512d": 6}
 
@@ -130,6 +135,8 @@ SIGNATURES = {
     "rsvld_gemv_w8_rows_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "rsvld_llama_decode_attention_rows_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "rsvld_llama_decode_attention_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "rsvld_llama_prefill_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "rsvld_plan_llama_prefill_attention": (_i, [_i, _i, _i, _i, C.POINTER(PrefillAttentionPlan)]),
     "rsvld_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "rsvld_concat_c_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "rsvld_axpby_f32": (_i, [_vp, _vp, _vp, _i64, _f, _f, _vp]),

@@ -352,4 +352,22 @@ inline int plan_attention(int B, int heads, int Nq, int Nk, int D, int plan_div,
     return RSVLD_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// causal grouped-query prefill attention (prefill_attention.hip): rows are (position, head-in-group) pairs of one kv head, T g of them,
+// 128 per workgroup (4 waves x 32); grid = (row blocks, kv heads), no key split and no workspace.  A function of (T, n_q, n_kv) alone:
+// pos0 and max_len change how many key tiles a workgroup walks, never which rows it owns.
+// ---------------------------------------------------------------------------------------
+constexpr int PREFILL_ATTN_ROWS = 128;   // rows per workgroup
+constexpr int PREFILL_ATTN_KEYS = 64;    // keys per tile (tiles start on absolute multiples of it)
+inline int plan_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_prefill_attention_plan* p) {
+    *p = rsvld_prefill_attention_plan{};
+    if (T < 1 || n_q < 1 || n_kv < 1 || n_q % n_kv != 0 || n_kv > 65535) return RSVLD_EINVAL;
+    const int g = n_q / n_kv;
+    if (head_dim != 128 || g > 8) return RSVLD_EUNSUPPORTED;
+    if ((int64_t)T * g > ((int64_t)1 << 30)) return RSVLD_EINVAL;   // the kernel's 32-bit row index
+    p->rows_per_wg = PREFILL_ATTN_ROWS, p->keys_per_tile = PREFILL_ATTN_KEYS;
+    p->grid_x = (int32_t)(((int64_t)T * g + PREFILL_ATTN_ROWS - 1) / PREFILL_ATTN_ROWS), p->grid_y = n_kv;
+    return RSVLD_OK;
+}
+
 }  // namespace rsvld_plan

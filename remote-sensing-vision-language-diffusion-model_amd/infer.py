@@ -72,10 +72,13 @@ class PipelineConfig:
     overlap_vae_with_caption: bool = True   # Stage 2's opening VAE passes on a second HIP stream beside the live caption pass
     device_io: bool = False           # resize / crop / 8-bit conversions around both stages on the GPU (rsvld_amd.imageops) instead of PIL + numpy + CPU torch
     caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8)
+    caption_prefill: str = "torch"    # attention of the caption pass's prefill: "torch" = the stock-torch sequence over the whole cache, "flash" = the causal flash kernel (opt-in, rsvld_amd.prefill_attention)
 
     def __post_init__(self):
         if self.caption_weights not in ("native", "e4m3"):
             raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected 'native' or 'e4m3'")
+        if self.caption_prefill not in ("torch", "flash"):
+            raise ValueError(f"PipelineConfig: caption_prefill={self.caption_prefill!r}, expected 'torch' or 'flash'")
         self.output_dir = Path(self.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
         self.input_path = Path(self.input_img)
@@ -166,7 +169,7 @@ class SuperResolutionPipeline:
         seed = None if self.cfg.seed < 0 else self.cfg.seed
         return LN.get_img_describe(image_tensor=views, image=sr_image, model=self.llava_model, tokenizer=self.llava_tokenizer,
                                    prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed,
-                                   decode_weights=self.cfg.caption_weights)[0]
+                                   decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill)[0]
 
     def run_stage2_captioning_batch(self, sr_images):
         """``run_stage2_captioning`` for the Stage-1 images of several inputs in ONE token loop (``infer_dir --caption_batch``) -> a list
@@ -188,7 +191,7 @@ class SuperResolutionPipeline:
         seeds = None if self.cfg.seed < 0 else [self.cfg.seed] * len(sr_images)
         return LN.get_img_describe_batch(image_tensors=views, images=list(sr_images), model=self.llava_model, tokenizer=self.llava_tokenizer,
                                          prompt=img_prompt, max_new_tokens=256, device=dev, seeds=seeds,
-                                         decode_weights=self.cfg.caption_weights)
+                                         decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill)
 
     def _stage2_input(self, sr_image):
         if self.cfg.device_io:
@@ -279,6 +282,9 @@ def build_parser():
     p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
                    "the checkpoint's 16-bit ones, or e4m3 bytes with one power-of-two scale per output row (half the bytes of a loop bound "
                    "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights)")
+    p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
+                   "stock-torch sequence over the whole cache, or the library's causal grouped-query flash kernel (fp32 scores, no score "
+                   "tensor, the prefill independent of the cache length; opt-in: other logits, fidelity on the real checkpoint is unmeasured)")
     return p
 
 
@@ -287,7 +293,7 @@ def main(argv=None):
     cfg = PipelineConfig(input_img=a.input_img, output_dir=a.output_dir, upscale_factor=a.upscale_factor, seed=a.seed,
                          img_threshold=a.img_threshold, edm_steps=a.edm_steps, sr3_steps=a.sr3_steps, caption=a.caption,
                          no_llava=a.no_llava, llava_path=a.llava_path, llava_adapter=a.llava_adapter, use_tile_vae=a.use_tile_vae,
-                         device_io=a.device_io, caption_weights=a.caption_weights,
+                         device_io=a.device_io, caption_weights=a.caption_weights, caption_prefill=a.caption_prefill,
                          **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if a.fp32 else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if a.tolerance else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if a.split else

@@ -316,18 +316,29 @@ class FastDecoder:
     ``batch``: 1 (default) is the decoder described above.  ``batch=B`` (<= 8, opt-in) allocates ``[B, kv_heads, max_len, head_dim]`` caches
     and adds ``generate_batch``: up to ``B`` captions in ONE token loop, the weights streamed once per step for all of them
     (``rsvld_amd.decode_rows``), each caption token for token what ``generate`` gives for its prompt alone; ``generate`` itself keeps
-    working on such a decoder (in cache row 0)."""
+    working on such a decoder (in cache row 0).
+
+    ``prefill``: "torch" (default) is the prefill described above: the prompt's queries against the whole cache under an additive mask.
+    "flash" (opt-in) runs the prefill's attention through the library's causal grouped-query flash kernel
+    (``rsvld_amd.prefill_attention``): fp32 scores that are never rounded to 16 bits, no score or mask tensor, and a query row reads keys
+    ``0 .. its own position`` only -- so the prefill's logits and cache rows do not depend on ``max_len`` or on what an earlier prompt
+    left in the cache.  Other logits than "torch" gives (closer to an fp32 run, tests/test_gpu_caption_prefill.py); the projections,
+    the rotary embedding, the cache write, the decode step and sampling are unchanged.  It needs 16-bit tensors on the GPU, head_dim
+    128 and at most eight query heads per kv head; anything else raises -- it never falls back to "torch" silently."""
 
     WEIGHTS = ("native", "e4m3")
+    PREFILLS = ("torch", "flash")
 
     MAX_BATCH = 8            # RSVLD_DECODE_MAX_ROWS
 
-    def __init__(self, model, max_len, weights="native", batch=1):
+    def __init__(self, model, max_len, weights="native", batch=1, prefill="torch"):
         if weights not in self.WEIGHTS:
             raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
+        if prefill not in self.PREFILLS:
+            raise ValueError(f"FastDecoder: prefill={prefill!r}, expected one of {self.PREFILLS}")
         if not isinstance(batch, int) or not 1 <= batch <= self.MAX_BATCH:
             raise ValueError(f"FastDecoder: batch={batch!r}, expected 1..{self.MAX_BATCH}")
-        self.weights, self.batch = weights, batch
+        self.weights, self.batch, self.prefill = weights, batch, prefill
         self._row = 0            # the cache row ``forward`` reads and writes (``generate_batch`` prefills row after row)
         self._rows = {}          # generate_batch: number of sequences -> the captured step (static buffers + graph)
         self._ws_rows = None
@@ -338,6 +349,11 @@ class FastDecoder:
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         p = next(model.parameters())
         self.dev, self.dt = p.device, p.dtype
+        if prefill == "flash" and not (self.dev.type == "cuda" and self.dt in (torch.float16, torch.bfloat16) and self.hd == 128
+                                       and self.n_q % self.n_kv == 0 and self.n_q // self.n_kv <= 8):
+            raise ValueError(f"FastDecoder(prefill='flash'): a {self.dt} model on {self.dev} with head_dim {self.hd} and {self.n_q} heads on "
+                             f"{self.n_kv} kv heads is not covered by the flash prefill kernel (16-bit weights on the GPU, head_dim 128, at "
+                             f"most 8 query heads per kv head are required; there is no fallback to 'torch')")
         shape = (batch, self.n_kv, self.max_len, self.hd)
         self.k = [torch.zeros(shape, device=self.dev, dtype=self.dt) for _ in self.layers]
         self.v = [torch.zeros(shape, device=self.dev, dtype=self.dt) for _ in self.layers]
@@ -426,12 +442,14 @@ class FastDecoder:
             return ops.gemv(w, x[0].contiguous(), b)[None]
         return torch.nn.functional.linear(x, w, b)
 
-    def forward(self, embeds, pos):
+    def forward(self, embeds, pos, pos0=None):
         """``embeds [1, T, H]`` at absolute positions ``pos [T]`` (long, on the device) -> logits of the LAST position
         ``[1, vocab]``; writes the keys / values of these positions into the cache.  One code path for the prefill (T > 1)
         and the decode step (T = 1): scores in the activation type, softmax in fp32 (``transformers``' eager attention),
         grouped-query heads as a batched matmul over the kv heads -- no expanded copy of the cache, no mask tensor beyond an
-        additive ``[T, max_len]`` row."""
+        additive ``[T, max_len]`` row.  ``prefill="flash"``, T > 1: the attention is ``prefill_attention.llama_prefill_attention`` (no
+        mask tensor at all); ``pos`` must then be ``pos0, pos0 + 1, ..`` and the caller says ``pos0`` as a HOST int (``generate`` /
+        ``generate_batch``: 0) -- it is not read back from ``pos``, which would be a host synchronisation."""
         m = self.model.model
         T = embeds.shape[1]
         nq, nkv, hd = self.n_q, self.n_kv, self.hd
@@ -443,8 +461,14 @@ class FastDecoder:
                                "(see _fused_ok) and the e4m3 weights have no other path; use weights='native'")
         cos, sin = m.rotary_emb(embeds, pos[None])                                 # [1, T, hd]
         cos, sin = cos[0][:, None], sin[0][:, None]                                # [T, 1, hd]
-        bias = torch.zeros((T, self.max_len), device=self.dev, dtype=torch.float32)
-        bias.masked_fill_(self.cols[None, :] > pos[:, None], float("-inf"))       # causal over the filled prefix
+        flash = self.prefill == "flash" and T > 1
+        if flash:
+            if pos0 is None:
+                raise ValueError("FastDecoder(prefill='flash').forward: pos0 (the host int position of the first row) is required at T > 1")
+            from . import prefill_attention as PA
+        else:
+            bias = torch.zeros((T, self.max_len), device=self.dev, dtype=torch.float32)
+            bias.masked_fill_(self.cols[None, :] > pos[:, None], float("-inf"))   # causal over the filled prefix
         scale = hd ** -0.5
         h = embeds[0]                                                               # [T, H]
         for i, layer in enumerate(self.layers):
@@ -456,10 +480,13 @@ class FastDecoder:
             kc, vc = self.k[i][self._row], self.v[i][self._row]
             kc.index_copy_(1, pos, qk[:, nq:].transpose(0, 1))
             vc.index_copy_(1, pos, qkv[:, nq + nkv:].transpose(0, 1))
-            q = qk[:, :nq].reshape(T, nkv, g, hd).permute(1, 0, 2, 3).reshape(nkv, T * g, hd)  # [kv head, (t, q-in-group), hd]
-            sc = torch.matmul(q, kc.transpose(1, 2)).float().view(nkv, T, g, self.max_len)
-            pr = torch.softmax(sc * scale + bias[None, :, None, :], dim=-1).to(self.dt).view(nkv, T * g, self.max_len)
-            o = torch.matmul(pr, vc).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
+            if flash:      # q stays the column slice of qk it is: the kernel takes its token stride
+                o = PA.llama_prefill_attention(qk[:, :nq], kc, vc, nq, nkv, scale, pos0=int(pos0))
+            else:
+                q = qk[:, :nq].reshape(T, nkv, g, hd).permute(1, 0, 2, 3).reshape(nkv, T * g, hd)  # [kv head, (t, q-in-group), hd]
+                sc = torch.matmul(q, kc.transpose(1, 2)).float().view(nkv, T, g, self.max_len)
+                pr = torch.softmax(sc * scale + bias[None, :, None, :], dim=-1).to(self.dt).view(nkv, T * g, self.max_len)
+                o = torch.matmul(pr, vc).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
             h = h + self._lin(o, layer.self_attn.o_proj.weight, layer.self_attn.o_proj.bias)
             x = self._rms(h, layer.post_attention_layernorm)
             gu = self._lin(x, self.wgu[i])
@@ -521,7 +548,7 @@ class FastDecoder:
             import time
             torch.cuda.current_stream().synchronize()   # (this stream only: a caller may run other work on a second stream beside the token loop)
             t_start = time.perf_counter()
-        logits = self.forward(inputs_embeds.to(self.dt), torch.arange(T0, device=self.dev))
+        logits = self.forward(inputs_embeds.to(self.dt), torch.arange(T0, device=self.dev), pos0=0)
         tok = self._pick(logits, do_sample, temperature, top_k, top_p)
         out = [tok]
         if self.profile is not None:
@@ -650,7 +677,7 @@ class FastDecoder:
         try:
             for b, e in enumerate(inputs_embeds):                      # prefill: matrix-bound, one prompt at a time, into cache row b
                 self._row = b
-                logits = self.forward(e.to(self.dt), torch.arange(T0s[b], device=self.dev))
+                logits = self.forward(e.to(self.dt), torch.arange(T0s[b], device=self.dev), pos0=0)
                 first.append(self._pick(logits, do_sample, temperature, top_k, top_p, generator=gens[b]))
         finally:
             self._row = 0
@@ -851,7 +878,7 @@ def _eos_ids(model, tokenizer):
 
 def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templates=conv_templates,
                      image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
-                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None):
+                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None, decode_prefill=None):
     """models/util.py:17-66 -> ``[caption]``.  ``seed`` (an addition) makes the caption a function of (image, prompt,
     weights, seed): sampling then runs inside ``torch.random.fork_rng`` with the CPU and the model's device generator seeded
     THERE, so the caller's generators -- which Stage 2 draws its noise from right afterwards, and in the reference live on
@@ -860,10 +887,15 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     ``fast`` (default: on a GPU, with one beam): the token loop runs through ``FastDecoder`` (static cache, decode step
     replayed from a hipGraph) instead of ``transformers``' ``generate``; same tokens (tests/test_llava_next.py).
     ``decode_weights`` (None = "native"): "e4m3" streams the token loop's weights as e4m3 bytes (``FastDecoder(weights=...)``, opt-in:
-    other logits than the 16-bit weights give); it needs the fast path, anything else raises."""
+    other logits than the 16-bit weights give); it needs the fast path, anything else raises.
+    ``decode_prefill`` (None = "torch"): "flash" runs the prefill's attention through the causal flash kernel
+    (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too."""
     decode_weights = "native" if decode_weights is None else decode_weights
     if decode_weights not in FastDecoder.WEIGHTS:
         raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
+    decode_prefill = "torch" if decode_prefill is None else decode_prefill
+    if decode_prefill not in FastDecoder.PREFILLS:
+        raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
     if conv_template != "llava_llama_3":
         raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
     system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
@@ -881,12 +913,15 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     if decode_weights != "native" and not fast:
         raise ValueError(f"get_img_describe: decode_weights={decode_weights!r} needs the FastDecoder token loop (a GPU model, one beam, no "
                          f"logits processors beyond temperature / top_k / top_p)")
+    if decode_prefill != "torch" and not fast:
+        raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r} needs the FastDecoder token loop (a GPU model, one beam, no "
+                         f"logits processors beyond temperature / top_k / top_p)")
 
     def run():
         if fast:   # (no_grad, not inference_mode: tensors made in inference mode cannot be updated in place by a later call
             with torch.no_grad():   # outside it, and a hipGraph capture that fails on that leaves the generator in capture state)
                 return caption_tokens_fast(model, input_ids, image_tensor, [image.size], max_new_tokens, do_sample, temperature,
-                                           _eos_ids(model, tokenizer), weights=decode_weights)
+                                           _eos_ids(model, tokenizer), weights=decode_weights, prefill=decode_prefill)
         with torch.inference_mode():
             return model.generate(input_ids, images=image_tensor, image_sizes=[image.size], do_sample=do_sample,
                                   temperature=temperature, num_beams=num_beams, max_new_tokens=max_new_tokens,
@@ -916,46 +951,48 @@ def _has_logits_warpers(model):
             or bool(getattr(g, "suppress_tokens", None)))
 
 
-def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native"):
-    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size and weight mode:
-    asking for the other mode rebuilds the decoder, its packs and its captured graph)."""
+def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
+                        prefill="torch"):
+    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode and
+    prefill mode: asking for the other mode rebuilds the decoder, its packs and its captured graph)."""
     embeds = model.multimodal_embeds(input_ids, images, image_sizes)
     need = embeds.shape[1] + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
     if dec is not None and dec.stale():     # the model was moved / cast / reloaded since the decoder fused its weights: rebuild
         dec = None
-    if dec is not None and dec.weights != weights:
+    if dec is not None and (dec.weights != weights or dec.prefill != prefill):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)      # (the old decoder's cache and packs go before the new ones are allocated)
-        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights)
+        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, prefill=prefill)
         model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
 
 
 def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
-                              seeds=None):
+                              seeds=None, prefill="torch"):
     """``caption_tokens_fast`` for several images under ONE prompt: ``images[b]`` / ``image_sizes[b]`` are the views and the size of image
     ``b`` -> a list of token tensors, each equal to ``caption_tokens_fast`` on that image alone (under ``seeds[b]``, see
     ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another weight mode, or
     for a longer cache -- like ``caption_tokens_fast``, which goes on using a decoder with more rows than one.  The cache length is this
     group's longest prompt plus the new tokens, rounded up to 256 (kept if the decoder's is longer); the prefill runs over it, so the equality
-    with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it)."""
+    with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it) -- or, with
+    ``prefill="flash"``, at any cache length: that prefill does not depend on it either."""
     embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
     need = max(e.shape[1] for e in embeds) + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
-    if dec is not None and (dec.stale() or dec.weights != weights or dec.batch < len(embeds)):
+    if dec is not None and (dec.stale() or dec.weights != weights or dec.prefill != prefill or dec.batch < len(embeds)):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)
-        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, batch=len(embeds))
+        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, batch=len(embeds), prefill=prefill)
         model.__dict__["_fast_decoder"] = dec
     return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
 
 
 def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv_templates=conv_templates,
                            image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
-                           do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None):
+                           do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None, decode_prefill=None):
     """``get_img_describe`` for a list of images (``image_tensors[b]``: the views of ``images[b]``) under one prompt -> a list of captions,
     caption ``b`` being what ``get_img_describe(image_tensors[b], images[b], ..., seed=seeds[b])[0]`` returns: with the FastDecoder the
     token loops of all images run as one (the decoder's weights are streamed once per step for all of them); without it the images
@@ -966,12 +1003,15 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     decode_weights = "native" if decode_weights is None else decode_weights
     if decode_weights not in FastDecoder.WEIGHTS:
         raise ValueError(f"get_img_describe_batch: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
+    decode_prefill = "torch" if decode_prefill is None else decode_prefill
+    if decode_prefill not in FastDecoder.PREFILLS:
+        raise ValueError(f"get_img_describe_batch: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
     mdev = next(model.parameters()).device
     use_fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
     if not use_fast or _has_logits_warpers(model) or n > FastDecoder.MAX_BATCH:
         return [get_img_describe(image_tensors[b], images[b], model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
                                  num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], fast,
-                                 decode_weights)[0] for b in range(n)]
+                                 decode_weights, decode_prefill)[0] for b in range(n)]
     if conv_template != "llava_llama_3":
         raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
     system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
@@ -979,5 +1019,5 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
     with torch.no_grad():
         outs = caption_tokens_fast_batch(model, input_ids, image_tensors, [im.size for im in images], max_new_tokens, do_sample, temperature,
-                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds)
+                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds, prefill=decode_prefill)
     return [tokenizer.decode(o.cpu().tolist(), skip_special_tokens=True).lstrip() for o in outs]

@@ -1450,6 +1450,38 @@ def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale,
     return _decode_attention_rows("llama_decode_attention", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, True)
 
 
+def _prefill_attention(fn, q, kcache, vcache, n_q, n_kv, scale, pos0):
+    """``prefill_attention.llama_prefill_attention`` (its public face): operand contracts, the output, the launch."""
+    _arg(fn, "kcache", kcache, _HALF, shape=(n_kv, None, None))
+    max_len, hd = kcache.shape[1], kcache.shape[2]
+    _arg(fn, "vcache", vcache, kcache.dtype, shape=tuple(kcache.shape))
+    if not isinstance(q, torch.Tensor) or q.dim() not in (2, 3):
+        _bad(fn, "q", f"must be a [T, n_q * {hd}] or [T, n_q, {hd}] tensor, got {tuple(q.shape) if isinstance(q, torch.Tensor) else type(q).__name__}")
+    T = q.shape[0]
+    _arg(fn, "q", q, kcache.dtype, shape=(T, n_q * hd) if q.dim() == 2 else (T, n_q, hd), layout="rows")
+    if q.dim() == 3 and n_q > 1 and q.stride(1) != hd:
+        _bad(fn, "q", f"must hold a token's heads side by side, got strides {tuple(q.stride())}")
+    q_ts = q.stride(0) if T > 1 else n_q * hd
+    if not isinstance(pos0, int) or isinstance(pos0, bool):
+        _bad(fn, "pos0", f"must be a host int (the prefill is not graph-captured), got {type(pos0).__name__}")
+    if T < 1 or pos0 < 0 or pos0 + T > max_len:
+        _bad(fn, "q", f"holds {T} positions from {pos0} on, the cache holds {max_len}")
+    if q_ts < n_q * hd:
+        _bad(fn, "q", f"has overlapping token rows (strides {tuple(q.stride())})")
+    if n_kv < 1 or n_q % n_kv:
+        _bad(fn, "q", f"has {n_q} heads on {n_kv} kv heads")
+    _need_gpu(q, kcache, vcache)
+    out = torch.empty((T, n_q * hd), device=q.device, dtype=q.dtype)
+    lib = L.load()
+    # causal: 2 (QK^T, PV) x 2 T (pos0 + (T + 1) / 2) n_q hd FLOP; q and out once, the filled prefix of both caches once per row block
+    flops = 4.0 * n_q * hd * T * (pos0 + (T + 1) / 2.0)
+    nbytes = (2 * T * n_q * hd + 2 * n_kv * (pos0 + T) * hd) * 2
+    _launch(fn, flops, nbytes, lambda: L.check(
+        lib.rsvld_llama_prefill_attention(_ptr(q), q_ts, _ptr(kcache), _ptr(vcache), _ptr(out), T, pos0, n_q, n_kv, hd, max_len, float(scale),
+                                          _dt(q), _stream()), "rsvld_llama_prefill_attention"))
+    return out
+
+
 # ----------------------------------------------------------------------------- small fp32 layers
 def linear_small(x, w, b, act_in=0, act_out=0):
     """fp32 ``[rows, in] -> [rows, out]`` with torch nn.Linear weight layout."""
