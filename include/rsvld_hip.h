@@ -523,6 +523,29 @@ typedef struct rsvld_prefill_attention_plan {
 } rsvld_prefill_attention_plan;
 int rsvld_plan_llama_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_prefill_attention_plan* plan);
 
+/* The PROJECTIONS of that prefill on the e4m3 packs of the token loop (opt-in: FastDecoder(prefill_weights="e4m3"), --caption_weights
+ * e4m3-only): out[m][n] = T(scale[n] * sum_k x[m][k] e4m3(q[n][k]) + bias[n]), the formula of rsvld_gemv_w8_fused without its fused
+ * neighbours, for M activation rows.  Replaces torch.nn.functional.linear on the 16-bit weights in the _lin calls of
+ * llava_next.FastDecoder.forward at T > 1 (q|k|v, o_proj, gate|up, down_proj of LlamaDecoderLayer.forward on the whole prompt behind
+ * models/util.py:17-66, llava/model/language_model/llava_llama.py:118-137), after which nothing reads the 16-bit decoder weights.
+ * x [M][K] 16-bit (dtype), rows contiguous; q [N][K] uint8 and scale [N] fp32 as rsvld_pack_rows_e4m3 writes them; bias [N] (dtype) or
+ * NULL; out [M][N] (dtype).  K % 16 == 0 (else RSVLD_EUNSUPPORTED), any M, N >= 1; x and q 16-byte aligned.  Device pointers and a
+ * stream: nothing is allocated, no environment variable is read, no state is kept.
+ * The sum runs on 16-bit MFMAs with fp32 accumulation; the weight bytes reach the matrix pipe converted to dtype UNSCALED (every e4m3
+ * value is exact in fp16 and bf16; q 2^e is not always exact in fp16), scale and bias are applied in fp32 and the result is rounded to
+ * dtype once, to nearest even.  A byte 0x7F / 0xFF (e4m3 NaN) in row n of q makes out[:, n] NaN, as in the matrix-vector product.
+ * CONTRACT: out[m][:] is a function of x[m][:], q, scale and bias only, bit for bit the same whatever M, m and the other rows of x are
+ * (NaN included): one tile shape and one ascending K order for every shape, no split over K, edge tiles zero-filled and masked. */
+int rsvld_gemm_w8(const void* x, const uint8_t* q, const float* scale, const void* bias, void* out, int M, int N, int K, int dtype,
+                  void* stream);
+/* Its launch (host only, nothing is launched): tile_m x tile_n outputs per workgroup of `waves` waves, K walked in steps of tile_k,
+ * grid_x row tiles x grid_y column tiles.  M enters grid_x alone.  Returns what the call returns for these arguments before it looks
+ * at pointers. */
+typedef struct rsvld_gemm_w8_plan {
+    int32_t grid_x, grid_y, tile_m, tile_n, tile_k, waves;
+} rsvld_gemm_w8_plan;
+int rsvld_plan_gemm_w8(int M, int N, int K, int dtype, rsvld_gemm_w8_plan* plan);
+
 /* ---------------------------------------------------------------------------------------
  * Split-operand product path (round 4): the producers / consumers of bf16 PLANES around the RSVLD_SPLIT convolutions.
  * "planes [rows][2C]" = per row lo(C) | hi(C) of an fp32 [rows][C] tensor (see RSVLD_SPLIT above); C % 8 == 0.

@@ -75,6 +75,12 @@ class PrefillAttentionPlan(C.Structure):
     _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("rows_per_wg", C.c_int32), ("keys_per_tile", C.c_int32)]
 
 
+class GemmW8Plan(C.Structure):
+    """rsvld_gemm_w8_plan (rsvld_plan_gemm_w8, host only)."""
+    _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32), ("tile_k", C.c_int32),
+                ("waves", C.c_int32)]
+
+
 # rsvld_attention_plan.row (RSVLD_ATTN_ROW_*): the rows of the launch table of csrc/attention.hip
 ATTN_ROW = {"d64b_nw4": 1, "d64b_nw8": 2, "d64c": 3, "d512b": 4, "d512b_shared": 5, "d512d": 6}
 
@@ -137,6 +143,8 @@ SIGNATURES = {
     "rsvld_llama_decode_attention_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_llama_prefill_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_plan_llama_prefill_attention": (_i, [_i, _i, _i, _i, C.POINTER(PrefillAttentionPlan)]),
+    "rsvld_gemm_w8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "rsvld_plan_gemm_w8": (_i, [_i, _i, _i, _i, C.POINTER(GemmW8Plan)]),
     "rsvld_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "rsvld_concat_c_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "rsvld_axpby_f32": (_i, [_vp, _vp, _vp, _i64, _f, _f, _vp]),

@@ -370,4 +370,21 @@ inline int plan_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_
     return RSVLD_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// 16-bit rows x e4m3 packs (gemm_w8.hip): ONE tile shape, ONE K order (ascending steps of GW_BK, no split over K), whatever the shape
+// is -- so there is nothing here that M could move: it enters grid_x alone, and a row's bits do not depend on the rows around it.
+// Grid = (row tiles, column tiles): the row tiles of one column tile are dispatched together and share its weight bytes in L2.
+// ---------------------------------------------------------------------------------------
+constexpr int GW_BM = 128, GW_BN = 128, GW_BK = 64, GW_WAVES = 4;
+inline int plan_gemm_w8(int M, int N, int K, int dtype, rsvld_gemm_w8_plan* p) {
+    *p = rsvld_gemm_w8_plan{};
+    if (M < 1 || N < 1 || K < 1) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % 16 != 0) return RSVLD_EUNSUPPORTED;                               // 16-byte pieces of e4m3
+    if (((int64_t)N + GW_BN - 1) / GW_BN > 65535) return RSVLD_EUNSUPPORTED;  // grid_y
+    p->tile_m = GW_BM, p->tile_n = GW_BN, p->tile_k = GW_BK, p->waves = GW_WAVES;
+    p->grid_x = (int32_t)(((int64_t)M + GW_BM - 1) / GW_BM), p->grid_y = (N + GW_BN - 1) / GW_BN;
+    return RSVLD_OK;
+}
+
 }  // namespace rsvld_plan

@@ -18,6 +18,7 @@ from PIL import Image
 from . import imageops
 from .configs import sr3 as SR3
 from .data import dataset as SR_Dataset
+from .llava_next import CAPTION_WEIGHTS
 from .models.util import PIL2Tensor, Tensor2PIL, create_SR_model
 from .sr3_model import create_model
 from .utils import logger as Logger
@@ -71,12 +72,12 @@ class PipelineConfig:
     allow_random_init: bool = False   # tests / benchmarks only: run without checkpoints on seeded random weights
     overlap_vae_with_caption: bool = True   # Stage 2's opening VAE passes on a second HIP stream beside the live caption pass
     device_io: bool = False           # resize / crop / 8-bit conversions around both stages on the GPU (rsvld_amd.imageops) instead of PIL + numpy + CPU torch
-    caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8)
+    caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8), "e4m3-only" = the prefill on them too and the 16-bit decoder weights released (llava_next.CAPTION_WEIGHTS)
     caption_prefill: str = "torch"    # attention of the caption pass's prefill: "torch" = the stock-torch sequence over the whole cache, "flash" = the causal flash kernel (opt-in, rsvld_amd.prefill_attention)
 
     def __post_init__(self):
-        if self.caption_weights not in ("native", "e4m3"):
-            raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected 'native' or 'e4m3'")
+        if self.caption_weights not in CAPTION_WEIGHTS:
+            raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected one of {CAPTION_WEIGHTS}")
         if self.caption_prefill not in ("torch", "flash"):
             raise ValueError(f"PipelineConfig: caption_prefill={self.caption_prefill!r}, expected 'torch' or 'flash'")
         self.output_dir = Path(self.output_dir)
@@ -279,9 +280,10 @@ def build_parser():
                                                          "inputs: rsvld_amd.ops.UNET_POLICY; fp16 x weight pairs, two MFMAs)")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (the shipped fp16 UNets): "
                                                              "+3 %% time, Stage-2 distance from the CPU path 3e-3 instead of 3e-2")
-    p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
+    p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: "
                    "the checkpoint's 16-bit ones, or e4m3 bytes with one power-of-two scale per output row (half the bytes of a loop bound "
-                   "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights)")
+                   "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights); e4m3-only "
+                   "runs the prefill on those bytes too and releases the 16-bit decoder weights (one model throughout, 8 GB instead of 24)")
     p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
                    "stock-torch sequence over the whole cache, or the library's causal grouped-query flash kernel (fp32 scores, no score "
                    "tensor, the prefill independent of the cache length; opt-in: other logits, fidelity on the real checkpoint is unmeasured)")

@@ -20,6 +20,7 @@ import torch
 
 from . import parallel
 from .infer import PipelineConfig, SuperResolutionPipeline
+from .llava_next import CAPTION_WEIGHTS
 
 EXTS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 
@@ -140,8 +141,9 @@ def build_parser():
                    "fp16 x weight pairs for the layer inputs of rsvld_amd.ops.UNET_POLICY): inside 1e-3 of the reference's CPU path; see INTEGRATION.md")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (+3 %% time, 10x closer to the CPU path)")
     p.add_argument("--device_io", action="store_true", help="the image steps around both stages on the GPU (rsvld_amd.imageops)")
-    p.add_argument("--caption_weights", choices=("native", "e4m3"), default="native", help="weights of the caption pass's token loop: "
-                   "the checkpoint's 16-bit ones, or e4m3 bytes with a scale per row (opt-in; see INTEGRATION.md)")
+    p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: "
+                   "the checkpoint's 16-bit ones, e4m3 bytes with a scale per row, or e4m3-only: the prefill on them too and the 16-bit "
+                   "decoder weights released (opt-in; see INTEGRATION.md)")
     p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
                    "stock-torch sequence, or the library's causal flash kernel (opt-in; with it the captions of --caption_batch N no "
                    "longer depend on the cache length a group was prefilled at; see DESIGN.md section 8)")

@@ -38,6 +38,18 @@ LLAMA3_SYSTEM = ("You are a helpful language and vision assistant. You are able 
                  "provides, and assist the user with a variety of tasks using natural language.")   # conversation.py:388
 DEFAULT_MODEL = "lmms-lab/llama3-llava-next-8b"     # models/util.py:112-114
 DEFAULT_ADAPTER = "./CKPT_PTH/Llava-next"           # models/util.py:115
+# The caption pass's weight switch -- PipelineConfig.caption_weights, --caption_weights of infer.py / infer_dir.py, decode_weights of
+# get_img_describe(_batch) -- validated against THIS tuple everywhere.  "e4m3-only": the prefill on the packs too and the 16-bit decoder
+# weights released, FastDecoder(weights="e4m3", prefill_weights="e4m3", release_native=True).
+CAPTION_WEIGHTS = ("native", "e4m3", "e4m3-only")
+
+
+def decoder_mode(caption_weights):
+    """A ``CAPTION_WEIGHTS`` value -> the three ``FastDecoder`` keywords it stands for."""
+    if caption_weights not in CAPTION_WEIGHTS:
+        raise ValueError(f"caption weights {caption_weights!r}, expected one of {CAPTION_WEIGHTS}")
+    only = caption_weights == "e4m3-only"
+    return dict(weights="e4m3" if only else caption_weights, prefill_weights="e4m3" if only else "native", release_native=only)
 
 
 # ------------------------------------------------------------------------------------------------ image side (host)
@@ -310,8 +322,9 @@ class FastDecoder:
     gate|up, ``down_proj`` and ``lm_head`` once as OCP e4m3 bytes with one power-of-two scale per output row (``rsvld_amd.w8``) and the
     fused decode step streams THOSE -- half the bytes of a loop bound by nothing else; activations, the KV cache, accumulation, the
     fused neighbours and sampling are unchanged.  The prefill keeps the 16-bit weights, so the packs come ON TOP of them: 8 GB beside
-    the 16 GB that stay resident for the 8 B decoder.  The mode needs the fused decode step (``_fused_ok``) and ``K % 16 == 0`` in
-    every packed product; where either fails the decoder raises -- it never falls back to the native weights silently.
+    the 16 GB that stay resident for the 8 B decoder (unless ``prefill_weights="e4m3"`` / ``release_native``, below).  The mode needs
+    the fused decode step (``_fused_ok``) and ``K % 16 == 0`` in every packed product; where either fails the decoder raises -- it
+    never falls back to the native weights silently.
 
     ``batch``: 1 (default) is the decoder described above.  ``batch=B`` (<= 8, opt-in) allocates ``[B, kv_heads, max_len, head_dim]`` caches
     and adds ``generate_batch``: up to ``B`` captions in ONE token loop, the weights streamed once per step for all of them
@@ -324,21 +337,47 @@ class FastDecoder:
     ``0 .. its own position`` only -- so the prefill's logits and cache rows do not depend on ``max_len`` or on what an earlier prompt
     left in the cache.  Other logits than "torch" gives (closer to an fp32 run, tests/test_gpu_caption_prefill.py); the projections,
     the rotary embedding, the cache write, the decode step and sampling are unchanged.  It needs 16-bit tensors on the GPU, head_dim
-    128 and at most eight query heads per kv head; anything else raises -- it never falls back to "torch" silently."""
+    128 and at most eight query heads per kv head; anything else raises -- it never falls back to "torch" silently.
+
+    ``prefill_weights``: "native" (default) is the prefill described above, on the 16-bit weights.  "e4m3" (opt-in, requires
+    ``weights="e4m3"``) sends the prefill's q|k|v, ``o_proj``, gate|up and ``down_proj`` through ``w8.linear_w8`` on the token loop's
+    packs and the last row's ``lm_head`` through ``w8.gemv_w8``: the caption is then ONE model from the first prompt token on -- the
+    torch model on ``w8.dequant(pack(w))`` up to summation order -- a prefill row's projections do not depend on the rows around it, and
+    nothing reads the 16-bit decoder weights any more.
+    ``release_native=True`` (requires ``prefill_weights="e4m3"``) therefore lets them go: packing proceeds layer by layer, a layer's
+    seven projection weights are replaced by empty tensors once its four packs exist, ``lm_head.weight`` at the end (kept where it
+    shares ``embed_tokens``' storage).  The packs are parked on the model (``model._e4m3_packs``); a decoder built later adopts them.
+    On such a model every ``FastDecoder`` that needs the 16-bit weights, and ``merge_lora``, raise: reload the model."""
 
     WEIGHTS = ("native", "e4m3")
     PREFILLS = ("torch", "flash")
+    PREFILL_WEIGHTS = ("native", "e4m3")
 
     MAX_BATCH = 8            # RSVLD_DECODE_MAX_ROWS
+    PARKED = "_e4m3_packs"   # the model attribute (plain, like ``_fast_decoder``) that holds the packs of a model whose 16-bit weights are released
 
-    def __init__(self, model, max_len, weights="native", batch=1, prefill="torch"):
+    def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False):
         if weights not in self.WEIGHTS:
             raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
         if prefill not in self.PREFILLS:
             raise ValueError(f"FastDecoder: prefill={prefill!r}, expected one of {self.PREFILLS}")
+        if prefill_weights not in self.PREFILL_WEIGHTS:
+            raise ValueError(f"FastDecoder: prefill_weights={prefill_weights!r}, expected one of {self.PREFILL_WEIGHTS}")
+        if prefill_weights == "e4m3" and weights != "e4m3":
+            raise ValueError(f"FastDecoder: prefill_weights='e4m3' runs the prefill on the token loop's packs and requires weights='e4m3' "
+                             f"(got weights={weights!r}; there is no fallback)")
+        if release_native and prefill_weights != "e4m3":
+            raise ValueError("FastDecoder: release_native=True requires prefill_weights='e4m3' (the 16-bit weights can only go once "
+                             "nothing reads them)")
         if not isinstance(batch, int) or not 1 <= batch <= self.MAX_BATCH:
             raise ValueError(f"FastDecoder: batch={batch!r}, expected 1..{self.MAX_BATCH}")
-        self.weights, self.batch, self.prefill = weights, batch, prefill
+        parked = model.__dict__.get(self.PARKED)
+        if parked is not None and (weights != "e4m3" or prefill_weights != "e4m3"):
+            raise RuntimeError(f"FastDecoder(weights={weights!r}, prefill_weights={prefill_weights!r}): this model's 16-bit decoder weights "
+                               f"were released by an earlier FastDecoder(release_native=True) and only its e4m3 packs remain; reload the "
+                               f"model to run on the 16-bit weights")
+        self.weights, self.batch, self.prefill, self.prefill_weights = weights, batch, prefill, prefill_weights
+        self.release_native = bool(release_native) or parked is not None     # (a model that is released stays so: its packs are adopted)
         self._row = 0            # the cache row ``forward`` reads and writes (``generate_batch`` prefills row after row)
         self._rows = {}          # generate_batch: number of sequences -> the captured step (static buffers + graph)
         self._ws_rows = None
@@ -365,6 +404,9 @@ class FastDecoder:
         # of one concatenated tensor (no copy is kept, ``state_dict`` is unchanged), so a decode step launches 4 GEMVs per layer
         # instead of 7.
         self.wqkv, self.bqkv, self.wgu = [], [], []
+        if self.release_native:
+            self._packs = self._adopt_packs(parked) if parked is not None else self._pack_and_release()
+            return
         for layer in self.layers:
             at, mlp = layer.self_attn, layer.mlp
             self.wqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "weight"))
@@ -373,6 +415,104 @@ class FastDecoder:
                 raise NotImplementedError("FastDecoder: biased MLP projections")
             self.wgu.append(self._fuse([mlp.gate_proj, mlp.up_proj], "weight"))
         self._packs = self._pack_e4m3() if weights == "e4m3" else None
+
+    # ------------------------------------------------------------------ release_native: the packs are the only copy of the decoder's weights
+    def _released_params(self):
+        """The parameters ``release_native`` empties: the seven projection weights of every layer, then ``lm_head.weight`` unless it
+        shares ``embed_tokens``' storage (a tied head stays: the embedding reads it)."""
+        ps = []
+        for layer in self.layers:
+            at, mlp = layer.self_attn, layer.mlp
+            ps += [m.weight for m in (at.q_proj, at.k_proj, at.v_proj, at.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj)]
+        head, emb = self.model.lm_head.weight, self.model.model.embed_tokens.weight
+        tied = head.numel() > 0 and head.untyped_storage().data_ptr() == emb.untyped_storage().data_ptr()
+        return ps if tied else ps + [head]
+
+    def _pack_and_release(self):
+        """Layer by layer: fuse, pack the layer's four products, then replace its seven 16-bit weights by empty tensors -- allocated memory
+        never stands more than one layer's sources above the packs made so far.  ``lm_head`` last.  The packs are parked on the model,
+        where a decoder built later (a longer cache, more rows) finds them: their sources no longer exist."""
+        srcs = list(self._released_params())
+        if srcs[-1] is not self.model.lm_head.weight:
+            srcs.append(self.model.lm_head.weight)          # a tied head is packed too, only not released
+        for t in srcs:                                       # every source is checked before the first one is released
+            self._packable(t)
+        if any(layer.mlp.gate_proj.bias is not None for layer in self.layers):
+            raise NotImplementedError("FastDecoder: biased MLP projections")
+        packs = []
+        with torch.no_grad():
+            for layer in self.layers:
+                at, mlp = layer.self_attn, layer.mlp
+                self.bqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "bias") if at.q_proj.bias is not None else None)
+                wqkv = self._fuse([at.q_proj, at.k_proj, at.v_proj], "weight")
+                p_qkv = self._pack_tight(wqkv)
+                del wqkv
+                self._release(at.q_proj, at.k_proj, at.v_proj)
+                p_o = self._pack_tight(at.o_proj.weight.contiguous())
+                self._release(at.o_proj)
+                wgu = self._fuse([mlp.gate_proj, mlp.up_proj], "weight")
+                p_gu = self._pack_tight(wgu)
+                del wgu
+                self._release(mlp.gate_proj, mlp.up_proj)
+                p_down = self._pack_tight(mlp.down_proj.weight.contiguous())
+                self._release(mlp.down_proj)
+                packs.append((p_qkv, p_o, p_gu, p_down))
+                self.wqkv.append(None)
+                self.wgu.append(None)
+            head = self.model.lm_head
+            packs.append(self._pack_tight(head.weight.contiguous()))
+            if head.weight.untyped_storage().data_ptr() != self.model.model.embed_tokens.weight.untyped_storage().data_ptr():
+                self._release(head)
+        self.model.__dict__[self.PARKED] = packs             # not a submodule, not a buffer: a plain attribute
+        return packs
+
+    @staticmethod
+    def _pack_tight(w):
+        """``w8.pack_rows_e4m3(w)`` with the bytes in an allocator block of exactly their size.  torch's caching allocator hands a
+        request the smallest free block that holds it and does not split the block when 1 MiB or less would remain -- and a release
+        leaves exactly such holes (a 1.5 MiB pack falls into the 2 MiB a source just left and keeps, and counts as, all of it): up to
+        1 MiB per pack of memory that was to be freed.  So the size is probed first: a probe that came with more than its own bytes is
+        held back (its hole is then out of the way) and the next one tried; the probe that fits alone is freed, and the pack's
+        allocation, the same size on the same stream, takes the block it leaves (an exact fit is the smallest block that holds it).
+        After a few holes the allocator cuts from a large block or a fresh segment, which is exact; the held holes are freed again."""
+        from . import w8
+        dev, nbytes = w.device, w.numel()                  # one e4m3 byte per weight
+        exact = -(-nbytes // 512) * 512                      # the allocator's own rounding
+        held, probe = [], None
+        for _ in range(8):
+            before = torch.cuda.memory_allocated(dev)
+            probe = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            if torch.cuda.memory_allocated(dev) - before <= exact:
+                break
+            held.append(probe)
+        del probe
+        packed = w8.pack_rows_e4m3(w)
+        del held
+        return packed
+
+    @staticmethod
+    def _release(*mods):
+        for m in mods:
+            m.weight.data = torch.empty(0, dtype=m.weight.dtype, device=m.weight.device)
+
+    def _adopt_packs(self, parked):
+        """A decoder on a model an earlier one released: the parked packs ARE the weights."""
+        emb = self.model.model.embed_tokens.weight
+        if any(p.numel() for p in self._released_params()) or len(parked) != len(self.layers) + 1 or parked[-1][0].device != emb.device:
+            raise RuntimeError("FastDecoder: this model's 16-bit decoder weights were released and its e4m3 packs no longer match it (a "
+                               "parameter was assigned since, or the model was moved); reload the model")
+        for layer in self.layers:
+            at = layer.self_attn
+            self.bqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "bias") if at.q_proj.bias is not None else None)
+            self.wqkv.append(None)
+            self.wgu.append(None)
+        return parked
+
+    @staticmethod
+    def _packable(t):
+        if t.dim() != 2 or t.shape[1] % 16 or t.dtype not in (torch.float16, torch.bfloat16) or not t.is_cuda:
+            raise ValueError(f"FastDecoder(weights='e4m3'): a {t.dtype} weight of shape {tuple(t.shape)} on {t.device} cannot be "
+                             f"packed (16-bit weights on the GPU with K % 16 == 0 are required; there is no fallback to 'native')")
 
     def _pack_sources(self):
         """The 16-bit tensors the e4m3 mode packs, in pack order: per layer q|k|v, o_proj, gate|up, down_proj; then lm_head."""
@@ -394,9 +534,7 @@ class FastDecoder:
         from . import w8
         src = self._pack_sources()
         for t in src:
-            if t.dim() != 2 or t.shape[1] % 16 or t.dtype not in (torch.float16, torch.bfloat16) or not t.is_cuda:
-                raise ValueError(f"FastDecoder(weights='e4m3'): a {t.dtype} weight of shape {tuple(t.shape)} on {t.device} cannot be "
-                                 f"packed (16-bit weights on the GPU with K % 16 == 0 are required; there is no fallback to 'native')")
+            self._packable(t)
         with torch.no_grad():
             packs = [w8.pack_rows_e4m3(t.contiguous()) for t in src]
         # what ``stale`` compares: a pack is a COPY, so an in-place update of its source (a LoRA merge) must be seen too
@@ -406,7 +544,12 @@ class FastDecoder:
     def stale(self):
         """The fused q | k | v and gate | up tensors are VIEWED by the model's own modules; ``model.to()`` / ``.half()`` / a LoRA merge /
         ``load_state_dict(assign=True)`` give the modules new storage and leave this decoder (weights, KV cache, captured graph) on
-        the old one.  Cheap check: first and last layer still alias the fused tensors, on the same device and dtype."""
+        the old one.  Cheap check: first and last layer still alias the fused tensors, on the same device and dtype.
+        ``release_native``: there is nothing left to alias -- stale when a released parameter holds elements again (the model was
+        reloaded under the decoder) or the packs sit on another device than ``embed_tokens``."""
+        if self.release_native:
+            return (any(p.numel() for p in self._released_params())
+                    or self._packs[-1][0].device != self.model.model.embed_tokens.weight.device)
         for i in (0, len(self.layers) - 1):
             q = self.layers[i].self_attn.q_proj.weight
             g = self.layers[i].mlp.gate_proj.weight
@@ -471,9 +614,19 @@ class FastDecoder:
             bias.masked_fill_(self.cols[None, :] > pos[:, None], float("-inf"))   # causal over the filled prefix
         scale = hd ** -0.5
         h = embeds[0]                                                               # [T, H]
+        if self.prefill_weights == "e4m3":     # (T > 1 here) every product on the token loop's packs: the 16-bit weights are not read
+            from . import w8
+
+            def lin(x, w, b=None, *, pack):
+                return w8.linear_w8(*pack, x.contiguous(), b)
+        else:
+            def lin(x, w, b=None, *, pack):
+                return self._lin(x, w, b)
+        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
         for i, layer in enumerate(self.layers):
+            p_qkv, p_o, p_gu, p_down = packs[i]
             x = self._rms(h, layer.input_layernorm)
-            qkv = self._lin(x, self.wqkv[i], self.bqkv[i]).view(T, nq + 2 * nkv, hd)
+            qkv = lin(x, self.wqkv[i], self.bqkv[i], pack=p_qkv).view(T, nq + 2 * nkv, hd)
             qk = qkv[:, :nq + nkv]
             half = hd // 2
             qk = qk * cos + torch.cat((-qk[..., half:], qk[..., :half]), dim=-1) * sin     # rotary embedding on q and k at once
@@ -487,12 +640,15 @@ class FastDecoder:
                 sc = torch.matmul(q, kc.transpose(1, 2)).float().view(nkv, T, g, self.max_len)
                 pr = torch.softmax(sc * scale + bias[None, :, None, :], dim=-1).to(self.dt).view(nkv, T * g, self.max_len)
                 o = torch.matmul(pr, vc).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
-            h = h + self._lin(o, layer.self_attn.o_proj.weight, layer.self_attn.o_proj.bias)
+            h = h + lin(o, layer.self_attn.o_proj.weight, layer.self_attn.o_proj.bias, pack=p_o)
             x = self._rms(h, layer.post_attention_layernorm)
-            gu = self._lin(x, self.wgu[i])
+            gu = lin(x, self.wgu[i], pack=p_gu)
             inter = gu.shape[-1] // 2
-            h = h + self._lin(torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:], layer.mlp.down_proj.weight)
-        return self._lin(self._rms(h[-1:], m.norm), self.model.lm_head.weight, self.model.lm_head.bias)
+            h = h + lin(torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:], layer.mlp.down_proj.weight, pack=p_down)
+        last = self._rms(h[-1:], m.norm)
+        if self.prefill_weights == "e4m3":     # ONE row: the matrix-vector product of the decode step, on the same pack
+            return w8.gemv_w8(*packs[-1], last[0].contiguous(), self.model.lm_head.bias)[None]
+        return self._lin(last, self.model.lm_head.weight, self.model.lm_head.bias)
 
     def _fused_ok(self, embeds):
         """The decode step as the library's fused kernels (rsvld_gemv_fused, rsvld_llama_decode_attention): 16-bit tensors on the GPU, head_dim
@@ -757,6 +913,9 @@ def merge_lora(model, adapter_dir):
     """Fold a PEFT LoRA adapter (adapter_config.json + adapter_model.safetensors / .bin) into ``model``'s Linear weights:
     ``W += (B @ A) * lora_alpha / r``.  Equivalent to ``PeftModel.from_pretrained(...).merge_and_unload()`` for plain LoRA on
     Linear layers; anything else in the adapter raises."""
+    if model.__dict__.get(FastDecoder.PARKED) is not None:
+        raise RuntimeError("merge_lora: this model's 16-bit decoder weights were released (FastDecoder(release_native=True) / caption "
+                           "weights 'e4m3-only') and there is nothing to merge into; reload the model, merge, then build the decoder")
     cfg = json.load(open(os.path.join(adapter_dir, "adapter_config.json")))
     if cfg.get("peft_type", "LORA") != "LORA" or cfg.get("use_dora") or cfg.get("modules_to_save"):
         raise NotImplementedError("merge_lora handles plain LoRA adapters on Linear layers")
@@ -887,12 +1046,14 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     ``fast`` (default: on a GPU, with one beam): the token loop runs through ``FastDecoder`` (static cache, decode step
     replayed from a hipGraph) instead of ``transformers``' ``generate``; same tokens (tests/test_llava_next.py).
     ``decode_weights`` (None = "native"): "e4m3" streams the token loop's weights as e4m3 bytes (``FastDecoder(weights=...)``, opt-in:
-    other logits than the 16-bit weights give); it needs the fast path, anything else raises.
+    other logits than the 16-bit weights give); "e4m3-only" runs the prefill on those bytes too and RELEASES the model's 16-bit decoder
+    weights (``CAPTION_WEIGHTS``, ``decoder_mode``: afterwards the model serves this mode only, until it is reloaded); both need the
+    fast path, anything else raises.
     ``decode_prefill`` (None = "torch"): "flash" runs the prefill's attention through the causal flash kernel
     (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too."""
     decode_weights = "native" if decode_weights is None else decode_weights
-    if decode_weights not in FastDecoder.WEIGHTS:
-        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
+    if decode_weights not in CAPTION_WEIGHTS:
+        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {CAPTION_WEIGHTS}")
     decode_prefill = "torch" if decode_prefill is None else decode_prefill
     if decode_prefill not in FastDecoder.PREFILLS:
         raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
@@ -951,6 +1112,17 @@ def _has_logits_warpers(model):
             or bool(getattr(g, "suppress_tokens", None)))
 
 
+def _decoder_fields(dec):
+    """The three fields of a decoder that ``decoder_mode`` names: what ``caption_tokens_fast(_batch)`` compare to decide a rebuild."""
+    return dict(weights=dec.weights, prefill_weights=getattr(dec, "prefill_weights", "native"), release_native=getattr(dec, "release_native", False))
+
+
+def _decoder_keywords(mode):
+    """``decoder_mode``'s keywords as the constructor gets them: the two later ones only where they are not the defaults, so that a
+    stand-in decoder class with the three-keyword signature keeps working for "native" and "e4m3"."""
+    return mode if mode["release_native"] else dict(weights=mode["weights"])
+
+
 def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
                         prefill="torch"):
     """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode and
@@ -960,11 +1132,12 @@ def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, d
     dec = getattr(model, "_fast_decoder", None)
     if dec is not None and dec.stale():     # the model was moved / cast / reloaded since the decoder fused its weights: rebuild
         dec = None
-    if dec is not None and (dec.weights != weights or dec.prefill != prefill):
+    mode = decoder_mode(weights)
+    if dec is not None and (_decoder_fields(dec) != mode or dec.prefill != prefill):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)      # (the old decoder's cache and packs go before the new ones are allocated)
-        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, prefill=prefill)
+        dec = FastDecoder(model, -(-need // 256) * 256, prefill=prefill, **_decoder_keywords(mode))
         model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
 
@@ -981,11 +1154,12 @@ def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tok
     embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
     need = max(e.shape[1] for e in embeds) + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
-    if dec is not None and (dec.stale() or dec.weights != weights or dec.prefill != prefill or dec.batch < len(embeds)):
+    mode = decoder_mode(weights)
+    if dec is not None and (dec.stale() or _decoder_fields(dec) != mode or dec.prefill != prefill or dec.batch < len(embeds)):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)
-        dec = FastDecoder(model, -(-need // 256) * 256, weights=weights, batch=len(embeds), prefill=prefill)
+        dec = FastDecoder(model, -(-need // 256) * 256, batch=len(embeds), prefill=prefill, **_decoder_keywords(mode))
         model.__dict__["_fast_decoder"] = dec
     return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
 
@@ -1001,8 +1175,8 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     if len(image_tensors) != n or (seeds is not None and len(seeds) != n):
         raise ValueError(f"get_img_describe_batch: {len(image_tensors)} view lists and {None if seeds is None else len(seeds)} seeds for {n} images")
     decode_weights = "native" if decode_weights is None else decode_weights
-    if decode_weights not in FastDecoder.WEIGHTS:
-        raise ValueError(f"get_img_describe_batch: decode_weights={decode_weights!r}, expected one of {FastDecoder.WEIGHTS}")
+    if decode_weights not in CAPTION_WEIGHTS:
+        raise ValueError(f"get_img_describe_batch: decode_weights={decode_weights!r}, expected one of {CAPTION_WEIGHTS}")
     decode_prefill = "torch" if decode_prefill is None else decode_prefill
     if decode_prefill not in FastDecoder.PREFILLS:
         raise ValueError(f"get_img_describe_batch: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
