@@ -497,6 +497,30 @@ int rsvld_llama_decode_attention_rows(const void* qkv, const void* cos, const vo
                                       void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
                                       void* stream);
 
+/* The same two products on MFMAs (opt-in: FastDecoder(decode="mfma"), --caption_decode mfma).  Replaces torch.nn.functional.linear in the
+ * Llama decode step behind models/util.py:17-66 (llava/model/language_model/llava_llama.py:118-137): q|k|v, o, gate|up, down projections
+ * and lm_head, for the B <= RSVLD_DECODE_MAX_ROWS captions of the batched token loop (models/util.py:39-60 called from
+ * infer_dir.py:196-201) -- the call sites of rsvld_gemv_rows_fused / rsvld_gemv_w8_rows_fused, whose arguments, operand limits and error
+ * codes these take unchanged.  The VALU kernels spend one fmaf chain per activation row and weight element; here a 16x16x32 MFMA takes 16
+ * weight rows x 32 k against all rows at once, so B rows cost the arithmetic of one.  x' (norm_w / glu) is staged and the result leaves
+ * (scale, bias, residual) by the very code of the VALU kernels: the same bits; the fp32 sum between them is taken in another order.
+ * CONTRACT: row b of the result is a function of x[b], the weights, scale, bias and residual[b] alone, bit for bit the same for every B
+ * in 1..8 and whatever the other rows hold (NaN and Inf included): the activation rows are the COLUMNS of the MFMA's B operand, unused
+ * columns are zero registers, and the route (rsvld_plan_gemv_mma) does not know B.  B = 1 runs these kernels too. */
+int rsvld_gemv_mma_rows_fused(const void* w, const void* x, const void* bias, const void* norm_w, float norm_eps, const void* residual, int glu,
+                              void* y, int N, int K, int B, int dtype, void* stream);
+int rsvld_gemv_w8_mma_rows_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
+                                 const void* residual, int glu, void* y, int N, int K, int B, int dtype, void* stream);
+/* Their route (host only, nothing is launched), a function of (N, K, weight kind: w8 != 0 = e4m3 bytes) -- there is no B to pass.
+ * ksplit: the `ways` waves of a workgroup split K for one block of rows_per_block output rows in ranges of steps_per_way steps (partial
+ * sums added in wave order); else a wave owns a block over all of K.  step_k: elements of K per step; slab_bytes: a wave's LDS slab;
+ * blocks: what the workgroups walk -- blocks of rows_per_block rows (ksplit) or of 4 x rows_per_block rows, one per wave; group_rows: the activation rows one launch stages (more
+ * rows go in equal groups, one weight pass each).  RSVLD_EUNSUPPORTED: K % 8 (16-bit) / K % 16 (e4m3) != 0 or K > 32 704. */
+typedef struct rsvld_gemv_mma_plan {
+    int32_t ksplit, ways, step_k, steps_per_way, slab_bytes, rows_per_block, blocks, group_rows;
+} rsvld_gemv_mma_plan;
+int rsvld_plan_gemv_mma(int N, int K, int w8, int dtype, rsvld_gemv_mma_plan* plan);
+
 /* The PREFILL of that token loop (opt-in: FastDecoder(prefill="flash"), --caption_prefill flash): causal grouped-query flash attention of T
  * new positions over one sequence's static cache (LlamaAttention.forward on the whole prompt behind models/util.py:17-66,
  * llava/model/language_model/llava_llama.py:118-137).  q [T][n_q x head_dim], token-major, rotary embedding already applied, q_tok_stride

@@ -81,6 +81,12 @@ class GemmW8Plan(C.Structure):
                 ("waves", C.c_int32)]
 
 
+class GemvMmaPlan(C.Structure):
+    """rsvld_gemv_mma_plan (rsvld_plan_gemv_mma, host only): the route of the MFMA decode products; no field depends on a row count."""
+    _fields_ = [("ksplit", C.c_int32), ("ways", C.c_int32), ("step_k", C.c_int32), ("steps_per_way", C.c_int32), ("slab_bytes", C.c_int32),
+                ("rows_per_block", C.c_int32), ("blocks", C.c_int32), ("group_rows", C.c_int32)]
+
+
 # rsvld_attention_plan.row (RSVLD_ATTN_ROW_*): the rows of the launch table of csrc/attention.hip
 ATTN_ROW = {"d64b_nw4": 1, "d64b_nw8": 2, "d64c": 3, "d512b": 4, "d512b_shared": 5, "d512d": 6}
 
@@ -139,6 +145,9 @@ SIGNATURES = {
     "rsvld_llama_decode_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_gemv_rows_fused": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "rsvld_gemv_w8_rows_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "rsvld_gemv_mma_rows_fused": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "rsvld_gemv_w8_mma_rows_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "rsvld_plan_gemv_mma": (_i, [_i, _i, _i, _i, C.POINTER(GemvMmaPlan)]),
     "rsvld_llama_decode_attention_rows_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "rsvld_llama_decode_attention_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_llama_prefill_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),

@@ -16,8 +16,7 @@
 
 namespace {
 
-constexpr int GV_WAVES = 4;    // waves per workgroup
-constexpr int GV_RPW = 4;      // rows a wave accumulates at a time
+#include "gemv_fused.h"   // GV_WAVES, GV_RPW, gv_stage_x, gv_store, gv_lds_bytes, by_dtype, gv_check: shared with gemv_mma.hip
 
 template <typename T> __device__ __forceinline__ float dot8(const u32x4& w, const u32x4& x, float acc) {
     float wf[8], xf[8];
@@ -26,67 +25,6 @@ template <typename T> __device__ __forceinline__ float dot8(const u32x4& w, cons
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc = __builtin_fmaf(wf[e], xf[e], acc);
     return acc;
-}
-
-// Fused forms (round 5, rsvld_gemv_fused: the decode step of a Llama layer in five launches instead of ~26 small ones).  All three act on
-// the activation row while it is staged into LDS, or on the result before its one store -- outside the weight-streaming loop:
-//   norm_w != nullptr   x <- T( x * rsqrt(mean(x^2) + eps) * norm_w )         (the RMSNorm in front of q|k|v, gate|up and lm_head)
-//   glu                 x has 2 K elements [gate | up]: x <- T( T(silu(gate)) * up )   (the SwiGLU in front of down_proj)
-//   residual != nullptr y <- T( residual + T(W x + b) )                        (h + o_proj(...), h + down_proj(...))
-// with the roundings of the unfused torch sequence (F.rms_norm, silu(g) * u, h + linear) kept where they were.  gv_stage_x / gv_store are
-// shared by the 16-bit kernel and the e4m3 one (gemv_w8_kernel): one statement of these roundings.
-// gv_stage_x: the activation row into LDS as K elements of T (4 floats of reduction scratch ``red_off`` bytes behind it), closed by a barrier.
-// (Thread indices come from the kernel and the pointers carry no __restrict__: in this form the 16-bit kernels' weight-streaming loops and
-// epilogues compile to the instructions they had with the staging written out in the kernel -- only address arithmetic of the staging itself
-// is ordered differently -- and they time the same; with __restrict__ parameters the row route measured 1 % slower.)
-template <typename T>
-__device__ __forceinline__ void gv_stage_x(char* smem, int red_off, const T* x, const T* norm_w, float eps, int K, int glu,
-                                           const int tid, const int lane, const int w) {
-    if (glu) {
-        for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) {
-            float g[8], u[8];
-            unpack8<T>(*(const u32x4*)(x + i), g);
-            unpack8<T>(*(const u32x4*)(x + K + i), u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma clang fp contract(off)
-                const T sg = (T)silu_f(g[e]);     // (silu rounded, THEN the product: two torch kernels)
-                g[e] = (float)sg * u[e];
-            }
-            *(u32x4*)(smem + i * 2) = pack8<T>(g);
-        }
-    } else if (norm_w != nullptr) {
-        float* red = (float*)(smem + (size_t)K * 2 + red_off);
-        float ss = 0.f;
-        for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) {
-            float f[8];
-            unpack8<T>(*(const u32x4*)(x + i), f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(f[e], f[e], ss);
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) red[w] = ss;
-        __syncthreads();
-        const float inv = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + eps);
-        for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) {
-            float f[8], g[8];
-            unpack8<T>(*(const u32x4*)(x + i), f);
-            unpack8<T>(*(const u32x4*)(norm_w + i), g);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = f[e] * inv * g[e];
-            *(u32x4*)(smem + i * 2) = pack8<T>(f);
-        }
-    } else {
-        for (int i = tid * 8; i < K; i += 64 * GV_WAVES * 8) *(u32x4*)(smem + i * 2) = *(const u32x4*)(x + i);
-    }
-    __syncthreads();
-}
-// gv_store: y[row] = T(v + bias[row]), then the residual
-template <typename T>
-__device__ __forceinline__ void gv_store(T* y, const T* bias, const T* residual, int row, float v) {
-    T r = (T)(v + (bias != nullptr ? (float)bias[row] : 0.f));
-    if (residual != nullptr) r = (T)((float)residual[row] + (float)r);
-    y[row] = r;
 }
 
 template <typename T, int KS>
@@ -620,29 +558,6 @@ __global__ __launch_bounds__(64 * GV_WAVES, GVR_MIN_WAVES) void gemv_rows_kernel
 // least two wave steps long in all (K >= 2 048).
 bool gemv_ksplit(int N, int K) { return K % 2048 == 0 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
 bool gemv_w8_ksplit(int N, int K) { return K % 64 == 0 && K >= 2048 && (N + GV_WAVES * GV_RPW - 1) / (GV_WAVES * GV_RPW) < 1024; }
-
-constexpr int GVR_LDS = 160 * 1024;     // LDS of a CU: what one workgroup may hold (registered per kernel above 64 KiB)
-constexpr int GVR_CUS = 256;            // sizes the persistent grid only (any grid gives the same results)
-// dynamic LDS of a launch with nb staged rows (the kernel's layout)
-constexpr size_t gv_lds_bytes(int K, int nb, bool ksplit) {
-    return (size_t)nb * K * 2 + (ksplit ? nb * 4 * GV_RPW * sizeof(float) : 0) + 16 * sizeof(float);
-}
-
-// the element type of RSVLD_F16 / RSVLD_BF16 (checked by the caller), resolved once: f gets a null T* to name T by
-template <typename F> auto by_dtype(int dtype, F&& f) { return dtype == RSVLD_F16 ? f((f16*)nullptr) : f((bf16*)nullptr); }
-
-// The operands of a product, for all four entry points.  W8: pieces of 16 weights (K % 16) and a scale per row; else pieces of 8 (K % 8).
-// ONE row with its K-split partial sums must fit the 64 KiB of dynamic LDS a launch gets without an opt-in (more rows go in groups).
-// (glu reads x[b] + K as 16-byte pieces too: aligned because x is and K % 8 == 0 makes K * 2 bytes a multiple of 16 -- no check of its own.)
-template <bool W8>
-int gv_check(const void* w, const float* scale, const void* x, const void* norm_w, int glu, const void* y, int N, int K, int B, int dtype) {
-    if (!w || (W8 && !scale) || !x || !y || N <= 0 || K <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (K % (W8 ? 16 : 8) != 0 || gv_lds_bytes(K, 1, true) > 65536) return RSVLD_EUNSUPPORTED;
-    if ((((uintptr_t)w | (uintptr_t)x | (uintptr_t)norm_w) & 15) || (W8 && ((uintptr_t)scale & 3))) return RSVLD_EINVAL;
-    if (glu && norm_w != nullptr) return RSVLD_EINVAL;
-    return RSVLD_OK;
-}
 
 // a group of NB >= 2 rows: gemv_rows_kernel on a persistent grid of what the chip holds at once
 template <typename T, int KS, int NB, bool W8>

@@ -387,4 +387,37 @@ inline int plan_gemm_w8(int M, int N, int K, int dtype, rsvld_gemm_w8_plan* p) {
     return RSVLD_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// the decode products on MFMAs (gemv_mma.hip): a wave streams GM_ROWS weight rows in steps of GM_STEP_BYTES per row through its own LDS
+// slab into the A operand of 16x16x32 MFMAs.  The route -- K split or not, its ways, the step and the slab -- is a function of
+// (N, K, weight kind) ONLY.  The number of activation rows is no argument: it decides how many rows are staged and in how many
+// launches they go (group_rows, a function of K), never the order a row's sum is taken in.
+// Row route: a wave owns a block of GM_ROWS output rows over all of K, a workgroup GM_WAVES blocks.  K-split route (few row blocks: the
+// row route would leave most of a 256-CU chip idle; and at least two steps per wave to split): the GM_WAVES waves of a workgroup take
+// consecutive ranges of whole steps of ONE block and their partial sums meet in LDS in wave order.
+// ---------------------------------------------------------------------------------------
+constexpr int GM_ROWS = 16, GM_WAVES = 4, GM_STEP_BYTES = 512;
+constexpr int GM_SLAB = GM_ROWS * GM_STEP_BYTES;                       // bytes of one wave's slab
+constexpr int GM_LDS = 160 * 1024, GM_PART = GM_WAVES * GM_ROWS * 16 * 4, GM_SCRATCH = 64;
+// bytes between two staged rows: K elements, rounded up to the 256 bytes of the LDS bank row, plus 32 -- the rows a quarter-wave reads
+// as the B operand then fall into different banks
+constexpr int64_t gm_xstride(int K) { return ((int64_t)K * 2 + 255) / 256 * 256 + 32; }
+inline int plan_gemv_mma(int N, int K, int w8, int dtype, rsvld_gemv_mma_plan* p) {
+    *p = rsvld_gemv_mma_plan{};
+    if (N < 1 || K < 1) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (K % (w8 ? 16 : 8) != 0 || (int64_t)K * 2 + 128 > 65536) return RSVLD_EUNSUPPORTED;   // (K's limit in gv_check, gemv_fused.h)
+    p->step_k = w8 ? GM_STEP_BYTES : GM_STEP_BYTES / 2;
+    p->slab_bytes = GM_SLAB;
+    p->rows_per_block = GM_ROWS;
+    const int steps = (K + p->step_k - 1) / p->step_k;
+    p->ksplit = (steps >= 2 * GM_WAVES && ((int64_t)N + GM_WAVES * GM_ROWS - 1) / (GM_WAVES * GM_ROWS) < 256) ? 1 : 0;
+    p->ways = p->ksplit ? GM_WAVES : 1;
+    p->steps_per_way = (steps + p->ways - 1) / p->ways;
+    p->blocks = (int32_t)(p->ksplit ? ((int64_t)N + GM_ROWS - 1) / GM_ROWS : ((int64_t)N + GM_WAVES * GM_ROWS - 1) / (GM_WAVES * GM_ROWS));
+    const int64_t fit = (GM_LDS - GM_WAVES * GM_SLAB - GM_PART - GM_SCRATCH) / gm_xstride(K);   // >= 1: a row is < 64 KiB + 288
+    p->group_rows = (int32_t)(fit < RSVLD_DECODE_MAX_ROWS ? fit : RSVLD_DECODE_MAX_ROWS);
+    return RSVLD_OK;
+}
+
 }  // namespace rsvld_plan

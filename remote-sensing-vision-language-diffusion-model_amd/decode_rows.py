@@ -13,10 +13,21 @@ from .ops import MAX_ROWS   # noqa: F401
 from .w8 import gemv_w8_rows   # noqa: F401
 
 
-def gemv_rows(w, x, bias=None, *, norm=None, residual=None, glu=False):
+def gemv_rows(w, x, bias=None, *, norm=None, residual=None, glu=False, kernel="valu"):
     """``ops.gemv_fused`` for ``B`` activation rows (rsvld_gemv_rows_fused): ``w [N, K]`` 16-bit, ``x [B, K]`` (``[B, 2 K]`` = gate | up
-    with ``glu``), ``residual [B, N]``; ``bias [N]`` and ``norm=(weight [K], eps)`` are shared by the rows.  -> ``[B, N]``."""
-    return ops._gemv_rows("gemv_rows", "gemv_rows", w, None, x, bias, norm, residual, glu, w8=False, single=False)
+    with ``glu``), ``residual [B, N]``; ``bias [N]`` and ``norm=(weight [K], eps)`` are shared by the rows.  -> ``[B, N]``.
+    ``kernel="mfma"`` (opt-in): the product on MFMAs (rsvld_gemv_mma_rows_fused, csrc/gemv_mma.hip), at every ``B`` including 1: the same
+    staged rows and epilogue roundings, the fp32 sum in another order -- row ``b`` bit-identical among ITS row counts, not to "valu"."""
+    return ops._gemv_rows("gemv_rows", "gemv_rows" if kernel == "valu" else "gemv_mma_rows", w, None, x, bias, norm, residual, glu, w8=False,
+                          single=False, kernel=kernel)
+
+
+def plan_gemv_mma(N, K, w8=False, dtype=None):
+    """The route of the ``kernel="mfma"`` products on ``[N, K]`` weights (rsvld_plan_gemv_mma, host only): ``_lib.GemvMmaPlan``.  There
+    is no row count to pass: the route cannot depend on it."""
+    pl = L.GemvMmaPlan()
+    L.check(L.load().rsvld_plan_gemv_mma(int(N), int(K), int(bool(w8)), L.F16 if dtype is None else ops._DT[dtype], pl), "rsvld_plan_gemv_mma")
+    return pl
 
 
 def llama_decode_attention_rows(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None):

@@ -18,7 +18,7 @@ from PIL import Image
 from . import imageops
 from .configs import sr3 as SR3
 from .data import dataset as SR_Dataset
-from .llava_next import CAPTION_WEIGHTS
+from .llava_next import CAPTION_DECODES, CAPTION_WEIGHTS
 from .models.util import PIL2Tensor, Tensor2PIL, create_SR_model
 from .sr3_model import create_model
 from .utils import logger as Logger
@@ -74,12 +74,15 @@ class PipelineConfig:
     device_io: bool = False           # resize / crop / 8-bit conversions around both stages on the GPU (rsvld_amd.imageops) instead of PIL + numpy + CPU torch
     caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8), "e4m3-only" = the prefill on them too and the 16-bit decoder weights released (llava_next.CAPTION_WEIGHTS)
     caption_prefill: str = "torch"    # attention of the caption pass's prefill: "torch" = the stock-torch sequence over the whole cache, "flash" = the causal flash kernel (opt-in, rsvld_amd.prefill_attention)
+    caption_decode: str = "valu"      # kernels of the token loop's products: "valu" = the vector-ALU ones, "mfma" = on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in, csrc/gemv_mma.hip; llava_next.CAPTION_DECODES)
 
     def __post_init__(self):
         if self.caption_weights not in CAPTION_WEIGHTS:
             raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected one of {CAPTION_WEIGHTS}")
         if self.caption_prefill not in ("torch", "flash"):
             raise ValueError(f"PipelineConfig: caption_prefill={self.caption_prefill!r}, expected 'torch' or 'flash'")
+        if self.caption_decode not in CAPTION_DECODES:
+            raise ValueError(f"PipelineConfig: caption_decode={self.caption_decode!r}, expected one of {CAPTION_DECODES}")
         self.output_dir = Path(self.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
         self.input_path = Path(self.input_img)
@@ -170,7 +173,8 @@ class SuperResolutionPipeline:
         seed = None if self.cfg.seed < 0 else self.cfg.seed
         return LN.get_img_describe(image_tensor=views, image=sr_image, model=self.llava_model, tokenizer=self.llava_tokenizer,
                                    prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed,
-                                   decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill)[0]
+                                   decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill,
+                                   decode_kernel=self.cfg.caption_decode)[0]
 
     def run_stage2_captioning_batch(self, sr_images):
         """``run_stage2_captioning`` for the Stage-1 images of several inputs in ONE token loop (``infer_dir --caption_batch``) -> a list
@@ -192,7 +196,8 @@ class SuperResolutionPipeline:
         seeds = None if self.cfg.seed < 0 else [self.cfg.seed] * len(sr_images)
         return LN.get_img_describe_batch(image_tensors=views, images=list(sr_images), model=self.llava_model, tokenizer=self.llava_tokenizer,
                                          prompt=img_prompt, max_new_tokens=256, device=dev, seeds=seeds,
-                                         decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill)
+                                         decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill,
+                                         decode_kernel=self.cfg.caption_decode)
 
     def _stage2_input(self, sr_image):
         if self.cfg.device_io:
@@ -287,6 +292,9 @@ def build_parser():
     p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
                    "stock-torch sequence over the whole cache, or the library's causal grouped-query flash kernel (fp32 scores, no score "
                    "tensor, the prefill independent of the cache length; opt-in: other logits, fidelity on the real checkpoint is unmeasured)")
+    p.add_argument("--caption_decode", choices=CAPTION_DECODES, default="valu", help="kernels of the token loop's weight-streaming products: "
+                   "on the vector ALU, or on MFMAs (another summation order: other logits, within the fp32 summation error; opt-in: "
+                   "fidelity on the real checkpoint is unmeasured)")
     return p
 
 
@@ -296,6 +304,7 @@ def main(argv=None):
                          img_threshold=a.img_threshold, edm_steps=a.edm_steps, sr3_steps=a.sr3_steps, caption=a.caption,
                          no_llava=a.no_llava, llava_path=a.llava_path, llava_adapter=a.llava_adapter, use_tile_vae=a.use_tile_vae,
                          device_io=a.device_io, caption_weights=a.caption_weights, caption_prefill=a.caption_prefill,
+                         caption_decode=a.caption_decode,
                          **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if a.fp32 else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if a.tolerance else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if a.split else

@@ -42,6 +42,11 @@ DEFAULT_ADAPTER = "./CKPT_PTH/Llava-next"           # models/util.py:115
 # get_img_describe(_batch) -- validated against THIS tuple everywhere.  "e4m3-only": the prefill on the packs too and the 16-bit decoder
 # weights released, FastDecoder(weights="e4m3", prefill_weights="e4m3", release_native=True).
 CAPTION_WEIGHTS = ("native", "e4m3", "e4m3-only")
+# The token loop's kernel switch -- PipelineConfig.caption_decode, --caption_decode of infer.py / infer_dir.py, decode_kernel of
+# get_img_describe(_batch), decode of caption_tokens_fast(_batch), FastDecoder.DECODES -- validated against THIS tuple everywhere.
+# "valu": the weight-streaming products on the vector ALU (csrc/gemv.hip); "mfma" (opt-in): on MFMAs (csrc/gemv_mma.hip), whose
+# arithmetic does not grow with the captions of a batch.  The two sum in different orders: other logits, the same contract each.
+CAPTION_DECODES = ("valu", "mfma")
 
 
 def decoder_mode(caption_weights):
@@ -347,16 +352,28 @@ class FastDecoder:
     ``release_native=True`` (requires ``prefill_weights="e4m3"``) therefore lets them go: packing proceeds layer by layer, a layer's
     seven projection weights are replaced by empty tensors once its four packs exist, ``lm_head.weight`` at the end (kept where it
     shares ``embed_tokens``' storage).  The packs are parked on the model (``model._e4m3_packs``); a decoder built later adopts them.
-    On such a model every ``FastDecoder`` that needs the 16-bit weights, and ``merge_lora``, raise: reload the model."""
+    On such a model every ``FastDecoder`` that needs the 16-bit weights, and ``merge_lora``, raise: reload the model.
+
+    ``decode``: "valu" (default) runs the products of the fused decode step on the vector ALU (csrc/gemv.hip), whose per-row fp32
+    arithmetic binds from four rows on.  "mfma" (opt-in) sends the four products per layer and ``lm_head`` through the MFMA kernels
+    (csrc/gemv_mma.hip, ``decode_rows.gemv_rows(..., kernel="mfma")``) at EVERY row count, ``generate``'s single row included -- so
+    that, inside the mode, ``generate_batch`` still equals ``generate`` per prompt token for token (a row's bits do not depend on the
+    row count).  An MFMA sums in another order than the fmaf chain: other logits than "valu" gives, within the summation error of
+    either.  Attention, the prefill and sampling are untouched; it combines with every other switch.  The mode needs the fused decode
+    step (``_fused_ok``); where that fails the decoder raises -- it never falls back to "valu" or to torch silently."""
 
     WEIGHTS = ("native", "e4m3")
     PREFILLS = ("torch", "flash")
     PREFILL_WEIGHTS = ("native", "e4m3")
+    DECODES = CAPTION_DECODES
 
     MAX_BATCH = 8            # RSVLD_DECODE_MAX_ROWS
     PARKED = "_e4m3_packs"   # the model attribute (plain, like ``_fast_decoder``) that holds the packs of a model whose 16-bit weights are released
 
-    def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False):
+    def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False,
+                 decode="valu"):
+        if decode not in self.DECODES:
+            raise ValueError(f"FastDecoder: decode={decode!r}, expected one of {self.DECODES}")
         if weights not in self.WEIGHTS:
             raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
         if prefill not in self.PREFILLS:
@@ -377,6 +394,7 @@ class FastDecoder:
                                f"were released by an earlier FastDecoder(release_native=True) and only its e4m3 packs remain; reload the "
                                f"model to run on the 16-bit weights")
         self.weights, self.batch, self.prefill, self.prefill_weights = weights, batch, prefill, prefill_weights
+        self.decode = decode
         self.release_native = bool(release_native) or parked is not None     # (a model that is released stays so: its packs are adopted)
         self._row = 0            # the cache row ``forward`` reads and writes (``generate_batch`` prefills row after row)
         self._rows = {}          # generate_batch: number of sequences -> the captured step (static buffers + graph)
@@ -599,6 +617,9 @@ class FastDecoder:
         g = nq // nkv
         if T == 1 and self._fused_ok(embeds):
             return self._forward_fused(embeds, pos)
+        if T == 1 and self.decode != "valu":
+            raise RuntimeError(f"FastDecoder(decode={self.decode!r}): the fused decode step is not available for this model / input "
+                               "(see _fused_ok) and the mode has no other path; use decode='valu'")
         if T == 1 and self._packs is not None:
             raise RuntimeError("FastDecoder(weights='e4m3'): the fused decode step is not available for this model / input "
                                "(see _fused_ok) and the e4m3 weights have no other path; use weights='native'")
@@ -760,12 +781,13 @@ class FastDecoder:
             # them).  Per-chunk partial results: written before they are read, no initial state.
             need = int(DR.ops.L.load().rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
             self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
+        kern = {} if self.decode == "valu" else {"kernel": self.decode}     # ("valu": the call as it always was)
         if self._packs is not None:
             def gemv(which, w, *a, **kw):        # the same call on the pack of ``w``
-                return DR.gemv_w8_rows(*which, *a, **kw)
+                return DR.gemv_w8_rows(*which, *a, **kw, **kern)
         else:
             def gemv(which, w, *a, **kw):
-                return DR.gemv_rows(w, *a, **kw)
+                return DR.gemv_rows(w, *a, **kw, **kern)
         packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
         for i, layer in enumerate(self.layers):
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
@@ -807,6 +829,9 @@ class FastDecoder:
         if seeds is not None and len(seeds) != n:
             raise ValueError(f"FastDecoder.generate_batch: {len(seeds)} seeds for {n} prompts")
         if not self._fused_ok(inputs_embeds[0].to(self.dt)):
+            if self.decode != "valu":
+                raise RuntimeError(f"FastDecoder(decode={self.decode!r}).generate_batch: the fused decode step is not available for this "
+                                   "model / device (see _fused_ok) and the mode has no other path; use decode='valu'")
             import warnings
             warnings.warn("FastDecoder.generate_batch: the fused decode step is not available for this model / device; the prompts are "
                           "captioned one after another (same tokens)")
@@ -1037,7 +1062,8 @@ def _eos_ids(model, tokenizer):
 
 def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templates=conv_templates,
                      image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
-                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None, decode_prefill=None):
+                     do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None, decode_prefill=None,
+                     decode_kernel=None):
     """models/util.py:17-66 -> ``[caption]``.  ``seed`` (an addition) makes the caption a function of (image, prompt,
     weights, seed): sampling then runs inside ``torch.random.fork_rng`` with the CPU and the model's device generator seeded
     THERE, so the caller's generators -- which Stage 2 draws its noise from right afterwards, and in the reference live on
@@ -1050,7 +1076,12 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     weights (``CAPTION_WEIGHTS``, ``decoder_mode``: afterwards the model serves this mode only, until it is reloaded); both need the
     fast path, anything else raises.
     ``decode_prefill`` (None = "torch"): "flash" runs the prefill's attention through the causal flash kernel
-    (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too."""
+    (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too.
+    ``decode_kernel`` (None = "valu"): "mfma" runs the token loop's products on MFMAs (``FastDecoder(decode=...)``, ``CAPTION_DECODES``,
+    opt-in: other logits, within the summation error); it needs the fast path too."""
+    decode_kernel = "valu" if decode_kernel is None else decode_kernel
+    if decode_kernel not in CAPTION_DECODES:
+        raise ValueError(f"get_img_describe: decode_kernel={decode_kernel!r}, expected one of {CAPTION_DECODES}")
     decode_weights = "native" if decode_weights is None else decode_weights
     if decode_weights not in CAPTION_WEIGHTS:
         raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {CAPTION_WEIGHTS}")
@@ -1077,12 +1108,16 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     if decode_prefill != "torch" and not fast:
         raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r} needs the FastDecoder token loop (a GPU model, one beam, no "
                          f"logits processors beyond temperature / top_k / top_p)")
+    if decode_kernel != "valu" and not fast:
+        raise ValueError(f"get_img_describe: decode_kernel={decode_kernel!r} needs the FastDecoder token loop (a GPU model, one beam, no "
+                         f"logits processors beyond temperature / top_k / top_p)")
 
     def run():
         if fast:   # (no_grad, not inference_mode: tensors made in inference mode cannot be updated in place by a later call
             with torch.no_grad():   # outside it, and a hipGraph capture that fails on that leaves the generator in capture state)
                 return caption_tokens_fast(model, input_ids, image_tensor, [image.size], max_new_tokens, do_sample, temperature,
-                                           _eos_ids(model, tokenizer), weights=decode_weights, prefill=decode_prefill)
+                                           _eos_ids(model, tokenizer), weights=decode_weights, prefill=decode_prefill,
+                                           **_decode_keyword(decode_kernel))
         with torch.inference_mode():
             return model.generate(input_ids, images=image_tensor, image_sizes=[image.size], do_sample=do_sample,
                                   temperature=temperature, num_beams=num_beams, max_new_tokens=max_new_tokens,
@@ -1117,6 +1152,11 @@ def _decoder_fields(dec):
     return dict(weights=dec.weights, prefill_weights=getattr(dec, "prefill_weights", "native"), release_native=getattr(dec, "release_native", False))
 
 
+def _decode_keyword(decode):
+    """``decode`` as a keyword only where it is not the default: a stand-in with the earlier signature keeps working for "valu"."""
+    return {} if decode == "valu" else {"decode": decode}
+
+
 def _decoder_keywords(mode):
     """``decoder_mode``'s keywords as the constructor gets them: the two later ones only where they are not the defaults, so that a
     stand-in decoder class with the three-keyword signature keeps working for "native" and "e4m3"."""
@@ -1124,49 +1164,56 @@ def _decoder_keywords(mode):
 
 
 def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
-                        prefill="torch"):
-    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode and
-    prefill mode: asking for the other mode rebuilds the decoder, its packs and its captured graph)."""
+                        prefill="torch", decode="valu"):
+    """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode,
+    prefill mode and decode kernel: asking for another mode rebuilds the decoder, its packs and its captured graph)."""
+    if decode not in CAPTION_DECODES:
+        raise ValueError(f"caption_tokens_fast: decode={decode!r}, expected one of {CAPTION_DECODES}")
     embeds = model.multimodal_embeds(input_ids, images, image_sizes)
     need = embeds.shape[1] + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
     if dec is not None and dec.stale():     # the model was moved / cast / reloaded since the decoder fused its weights: rebuild
         dec = None
     mode = decoder_mode(weights)
-    if dec is not None and (_decoder_fields(dec) != mode or dec.prefill != prefill):
+    if dec is not None and (_decoder_fields(dec) != mode or dec.prefill != prefill or getattr(dec, "decode", "valu") != decode):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)      # (the old decoder's cache and packs go before the new ones are allocated)
-        dec = FastDecoder(model, -(-need // 256) * 256, prefill=prefill, **_decoder_keywords(mode))
+        dec = FastDecoder(model, -(-need // 256) * 256, prefill=prefill, **_decoder_keywords(mode), **_decode_keyword(decode))
         model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
 
 
 def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
-                              seeds=None, prefill="torch"):
+                              seeds=None, prefill="torch", decode="valu"):
     """``caption_tokens_fast`` for several images under ONE prompt: ``images[b]`` / ``image_sizes[b]`` are the views and the size of image
     ``b`` -> a list of token tensors, each equal to ``caption_tokens_fast`` on that image alone (under ``seeds[b]``, see
     ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another weight mode, or
     for a longer cache -- like ``caption_tokens_fast``, which goes on using a decoder with more rows than one.  The cache length is this
     group's longest prompt plus the new tokens, rounded up to 256 (kept if the decoder's is longer); the prefill runs over it, so the equality
     with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it) -- or, with
-    ``prefill="flash"``, at any cache length: that prefill does not depend on it either."""
+    ``prefill="flash"``, at any cache length: that prefill does not depend on it either.  ``decode``: as in ``caption_tokens_fast``."""
+    if decode not in CAPTION_DECODES:
+        raise ValueError(f"caption_tokens_fast_batch: decode={decode!r}, expected one of {CAPTION_DECODES}")
     embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
     need = max(e.shape[1] for e in embeds) + max_new_tokens
     dec = getattr(model, "_fast_decoder", None)
     mode = decoder_mode(weights)
-    if dec is not None and (dec.stale() or _decoder_fields(dec) != mode or dec.prefill != prefill or dec.batch < len(embeds)):
+    if dec is not None and (dec.stale() or _decoder_fields(dec) != mode or dec.prefill != prefill or dec.batch < len(embeds)
+                            or getattr(dec, "decode", "valu") != decode):
         dec = None
     if dec is None or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)
-        dec = FastDecoder(model, -(-need // 256) * 256, batch=len(embeds), prefill=prefill, **_decoder_keywords(mode))
+        dec = FastDecoder(model, -(-need // 256) * 256, batch=len(embeds), prefill=prefill, **_decoder_keywords(mode),
+                          **_decode_keyword(decode))
         model.__dict__["_fast_decoder"] = dec
     return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
 
 
 def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv_templates=conv_templates,
                            image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
-                           do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None, decode_prefill=None):
+                           do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None, decode_prefill=None,
+                           decode_kernel=None):
     """``get_img_describe`` for a list of images (``image_tensors[b]``: the views of ``images[b]``) under one prompt -> a list of captions,
     caption ``b`` being what ``get_img_describe(image_tensors[b], images[b], ..., seed=seeds[b])[0]`` returns: with the FastDecoder the
     token loops of all images run as one (the decoder's weights are streamed once per step for all of them); without it the images
@@ -1180,12 +1227,15 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     decode_prefill = "torch" if decode_prefill is None else decode_prefill
     if decode_prefill not in FastDecoder.PREFILLS:
         raise ValueError(f"get_img_describe_batch: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
+    decode_kernel = "valu" if decode_kernel is None else decode_kernel
+    if decode_kernel not in CAPTION_DECODES:
+        raise ValueError(f"get_img_describe_batch: decode_kernel={decode_kernel!r}, expected one of {CAPTION_DECODES}")
     mdev = next(model.parameters()).device
     use_fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
     if not use_fast or _has_logits_warpers(model) or n > FastDecoder.MAX_BATCH:
         return [get_img_describe(image_tensors[b], images[b], model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
                                  num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], fast,
-                                 decode_weights, decode_prefill)[0] for b in range(n)]
+                                 decode_weights, decode_prefill, decode_kernel)[0] for b in range(n)]
     if conv_template != "llava_llama_3":
         raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
     system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
@@ -1193,5 +1243,6 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
     with torch.no_grad():
         outs = caption_tokens_fast_batch(model, input_ids, image_tensors, [im.size for im in images], max_new_tokens, do_sample, temperature,
-                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds, prefill=decode_prefill)
+                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds, prefill=decode_prefill,
+                                         **_decode_keyword(decode_kernel))
     return [tokenizer.decode(o.cpu().tolist(), skip_special_tokens=True).lstrip() for o in outs]

@@ -1356,9 +1356,16 @@ def _rows(fn, x):
     return B
 
 
-def _gemv_rows(fn, launch, w, scale, x, bias, norm, residual, glu, *, w8, single):
+GEMV_KERNELS = ("valu", "mfma")    # the two families of decode products: csrc/gemv.hip / csrc/gemv_mma.hip
+
+
+def _gemv_rows(fn, launch, w, scale, x, bias, norm, residual, glu, *, w8, single, kernel="valu"):
     """``fn`` (the public name errors carry; ``launch``: the profiler's) on ``B`` rows: ``w [N, K]`` 16-bit, or (``w8``) e4m3 bytes with
-    ``scale [N]``.  A single-row function reaches the library through its own entry point, which is the ``B = 1`` call of the rows one."""
+    ``scale [N]``.  A single-row function reaches the library through its own entry point, which is the ``B = 1`` call of the rows one.
+    ``kernel="mfma"`` (rows functions only): the same operands, checks and errors, launched through the MFMA entry points -- at every
+    ``B``, one row included."""
+    if kernel not in GEMV_KERNELS or (single and kernel != "valu"):
+        raise ValueError(f"{fn}: kernel={kernel!r}, expected one of {GEMV_KERNELS if not single else GEMV_KERNELS[:1]}")
     _arg(fn, "q" if w8 else "w", w, torch.uint8 if w8 else _HALF, shape=(None, None))
     N, K = w.shape
     if w8 and (N == 0 or K == 0 or K % 16):
@@ -1383,7 +1390,7 @@ def _gemv_rows(fn, launch, w, scale, x, bias, norm, residual, glu, *, w8, single
         _bad(fn, "norm weight", "cannot be combined with glu")
     _need_gpu(w, scale, x, bias, nw, residual)
     y = torch.empty(N if single else (B, N), device=x.device, dtype=dt)
-    entry = _GEMV_ENTRY[w8, single]
+    entry = _GEMV_ENTRY[w8, single] if kernel == "valu" else _GEMV_MMA_ENTRY[w8]
     args = (_ptr(x), _ptr(bias), _ptr(nw), float(eps), _ptr(residual), int(glu), _ptr(y), N, K)
     args = ((_ptr(w), _ptr(scale)) if w8 else (_ptr(w),)) + args + ((_dt(x), _stream()) if single else (B, _dt(x), _stream()))
     call = getattr(L.load(), entry)
@@ -1393,6 +1400,7 @@ def _gemv_rows(fn, launch, w, scale, x, bias, norm, residual, glu, *, w8, single
 
 _GEMV_ENTRY = {(False, True): "rsvld_gemv_fused", (False, False): "rsvld_gemv_rows_fused",
                (True, True): "rsvld_gemv_w8_fused", (True, False): "rsvld_gemv_w8_rows_fused"}
+_GEMV_MMA_ENTRY = {False: "rsvld_gemv_mma_rows_fused", True: "rsvld_gemv_w8_mma_rows_fused"}
 
 
 def gemv(w, x, bias=None):

@@ -42,10 +42,12 @@ def gemv_w8(q, scale, x, bias=None, *, norm=None, residual=None, glu=False):
     return ops._gemv_rows("gemv_w8", "gemv_w8", q, scale, x, bias, norm, residual, glu, w8=True, single=True)
 
 
-def gemv_w8_rows(q, scale, x, bias=None, *, norm=None, residual=None, glu=False):
+def gemv_w8_rows(q, scale, x, bias=None, *, norm=None, residual=None, glu=False, kernel="valu"):
     """``gemv_w8`` for ``B`` activation rows (rsvld_gemv_w8_rows_fused; also ``decode_rows.gemv_w8_rows``): ``x [B, K]`` 16-bit
-    (``[B, 2 K]`` with ``glu``), ``residual [B, N]``; ``bias`` and ``norm`` are shared by the rows.  -> ``[B, N]`` in ``x``'s type."""
-    return ops._gemv_rows("gemv_w8_rows", "gemv_w8_rows", q, scale, x, bias, norm, residual, glu, w8=True, single=False)
+    (``[B, 2 K]`` with ``glu``), ``residual [B, N]``; ``bias`` and ``norm`` are shared by the rows.  -> ``[B, N]`` in ``x``'s type.
+    ``kernel="mfma"`` (opt-in): rsvld_gemv_w8_mma_rows_fused, as ``decode_rows.gemv_rows`` describes it."""
+    return ops._gemv_rows("gemv_w8_rows", "gemv_w8_rows" if kernel == "valu" else "gemv_w8_mma_rows", q, scale, x, bias, norm, residual, glu,
+                          w8=True, single=False, kernel=kernel)
 
 
 def linear_w8(q, scale, x, bias=None):
