@@ -50,14 +50,11 @@ def test_gemv_w8_rows_guarded(cuda, N, K, B, dt):
     guarded.run_guarded(fn, dict(q=q, scale=scale, **rest), expect="gemv_w8_rows")
 
 
-@pytest.mark.parametrize("B,dt", [(3, F16), (3, BF16), (8, F16), (8, BF16)], ids=["b3_f16", "b3_bf16", "b8_f16", "b8_bf16"])
-def test_llama_decode_attention_rows_guarded(cuda, B, dt):
-    """Positions 0, the last slot (the write of the LAST sequence lands flush against the end of both caches) and chunk boundaries
-    between; every slot beyond a sequence's position holds 0xFF bytes; the scratch is allocated under the proxy (poison)."""
+def _attention_rows_guarded(cuda, nq, nkv, max_len, positions, dt, seed):
+    """Every slot beyond a sequence's position holds 0xFF bytes; the scratch is allocated under the proxy (poison)."""
     from rsvld_amd import decode_rows as DR
-    nq, nkv, hd, max_len = 8, 2, 128, 777
-    positions = [0, 255, 256, 300, 127, 128, 5, 776][:B - 1] + [776]
-    g = torch.Generator().manual_seed(B)
+    B, hd = len(positions), 128
+    g = torch.Generator().manual_seed(seed)
     qkv = torch.randn(B, (nq + 2 * nkv) * hd, generator=g).to(cuda, dt)
     kc, vc = torch.randn(B, nkv, max_len, hd, generator=g).to(cuda, dt), torch.randn(B, nkv, max_len, hd, generator=g).to(cuda, dt)
     ang = torch.rand(B, hd // 2, generator=g) * 6
@@ -70,3 +67,20 @@ def test_llama_decode_attention_rows_guarded(cuda, B, dt):
     fn = lambda qkv, cos, sin, p, kc, vc: DR.llama_decode_attention_rows(qkv, cos, sin, p, kc, vc, nq, nkv, hd ** -0.5)
     guarded.run_guarded(fn, dict(qkv=qkv, cos=cos, sin=sin, p=torch.tensor(positions, device=cuda), kc=guarded.Op(kc, inplace=mask),
                                  vc=guarded.Op(vc, inplace=mask)), expect="llama_decode_attention_rows")
+
+
+@pytest.mark.parametrize("B,dt", [(3, F16), (3, BF16), (8, F16), (8, BF16)], ids=["b3_f16", "b3_bf16", "b8_f16", "b8_bf16"])
+def test_llama_decode_attention_rows_guarded(cuda, B, dt):
+    """Positions 0, the last slot (the write of the LAST sequence lands flush against the end of both caches) and chunk boundaries
+    between."""
+    _attention_rows_guarded(cuda, 8, 2, 777, [0, 255, 256, 300, 127, 128, 5, 776][:B - 1] + [776], dt, seed=B)
+
+
+@pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("nq,nkv,max_len,positions", [(8, 1, 384, (0, 128, 383)), (2, 1, 8325, (100, 8192, 8324))],
+                         ids=["q8_kv1_len384", "q2_kv1_len8325"])
+def test_llama_decode_attention_rows_guarded_group_of_8_and_66_chunks(cuda, nq, nkv, max_len, positions, dt):
+    """B = 3.  Eight query heads on ONE kv head: the per-head loops of da_kernel take their second pass and a chunk's partials are 8 rows
+    of the workspace.  max_len = 8325 is 66 key chunks: da_combine_kernel's second round, with the round empty (100), one key in it
+    (8192) and the last slot flush against the end of both caches (8324)."""
+    _attention_rows_guarded(cuda, nq, nkv, max_len, list(positions), dt, seed=max_len)

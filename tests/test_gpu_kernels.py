@@ -646,11 +646,11 @@ def test_gemv_fused_decode_step_neighbours(cuda, dtype, shape):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("pos", [0, 5, 255, 256, 700])
+@pytest.mark.parametrize("pos", [0, 5, 127, 128, 255, 256, 700])
 def test_llama_decode_attention_vs_torch_sequence(cuda, dtype, pos):
     """rsvld_llama_decode_attention (rotary embedding of the new q / k, cache write at a DEVICE position, grouped-query attention over the
     filled prefix) against the torch-op sequence of FastDecoder.forward for ONE new token: 8 query heads on 2 kv heads, head_dim 128,
-    positions on both sides of the 256-key chunk boundary."""
+    positions on both sides of the boundaries of the 128-key chunks (DA_CH) a workgroup takes."""
     from rsvld_amd import ops
     nq, nkv, hd, max_len = 8, 2, 128, 777
     g = torch.Generator().manual_seed(pos + 1)

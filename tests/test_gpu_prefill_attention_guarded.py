@@ -13,11 +13,13 @@ pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
 HD = 128
-CASES = [(33, 0, 8, 2, 64), (60, 100, 8, 2, 192)]      # (T, pos0, n_q, n_kv, max_len) of tests/test_gpu_prefill_attention.py
+# (T, pos0, n_q, n_kv, max_len) of tests/test_gpu_prefill_attention.py, and g = 3 of tests/test_gpu_caption_attention.py: 128 rows per
+# workgroup and 32 per wave are no multiple of 3, one token's heads straddle two waves
+CASES = [(33, 0, 8, 2, 64), (60, 100, 8, 2, 192), (45, 0, 3, 1, 64)]
 
 
 @pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
-@pytest.mark.parametrize("case", CASES, ids=["t33_p0", "t60_p100"])
+@pytest.mark.parametrize("case", CASES, ids=["t33_p0", "t60_p100", "t45_p0_g3"])
 def test_llama_prefill_attention_guarded(cuda, case, dtype):
     from rsvld_amd import prefill_attention as PA
     T, pos0, n_q, n_kv, max_len = case
