@@ -18,7 +18,7 @@ from PIL import Image
 from . import imageops
 from .configs import sr3 as SR3
 from .data import dataset as SR_Dataset
-from .llava_next import CAPTION_DECODES, CAPTION_WEIGHTS
+from .llava_next import add_caption_arguments, caption_mode
 from .models.util import PIL2Tensor, Tensor2PIL, create_SR_model
 from .sr3_model import create_model
 from .utils import logger as Logger
@@ -77,12 +77,8 @@ class PipelineConfig:
     caption_decode: str = "valu"      # kernels of the token loop's products: "valu" = the vector-ALU ones, "mfma" = on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in, csrc/gemv_mma.hip; llava_next.CAPTION_DECODES)
 
     def __post_init__(self):
-        if self.caption_weights not in CAPTION_WEIGHTS:
-            raise ValueError(f"PipelineConfig: caption_weights={self.caption_weights!r}, expected one of {CAPTION_WEIGHTS}")
-        if self.caption_prefill not in ("torch", "flash"):
-            raise ValueError(f"PipelineConfig: caption_prefill={self.caption_prefill!r}, expected 'torch' or 'flash'")
-        if self.caption_decode not in CAPTION_DECODES:
-            raise ValueError(f"PipelineConfig: caption_decode={self.caption_decode!r}, expected one of {CAPTION_DECODES}")
+        caption_mode(self.caption_weights, self.caption_prefill, self.caption_decode, who="PipelineConfig",
+                     names=("caption_weights", "caption_prefill", "caption_decode"))
         self.output_dir = Path(self.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
         self.input_path = Path(self.input_img)
@@ -285,16 +281,7 @@ def build_parser():
                                                          "inputs: rsvld_amd.ops.UNET_POLICY; fp16 x weight pairs, two MFMAs)")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (the shipped fp16 UNets): "
                                                              "+3 %% time, Stage-2 distance from the CPU path 3e-3 instead of 3e-2")
-    p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: "
-                   "the checkpoint's 16-bit ones, or e4m3 bytes with one power-of-two scale per output row (half the bytes of a loop bound "
-                   "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights); e4m3-only "
-                   "runs the prefill on those bytes too and releases the 16-bit decoder weights (one model throughout, 8 GB instead of 24)")
-    p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
-                   "stock-torch sequence over the whole cache, or the library's causal grouped-query flash kernel (fp32 scores, no score "
-                   "tensor, the prefill independent of the cache length; opt-in: other logits, fidelity on the real checkpoint is unmeasured)")
-    p.add_argument("--caption_decode", choices=CAPTION_DECODES, default="valu", help="kernels of the token loop's weight-streaming products: "
-                   "on the vector ALU, or on MFMAs (another summation order: other logits, within the fp32 summation error; opt-in: "
-                   "fidelity on the real checkpoint is unmeasured)")
+    add_caption_arguments(p)
     return p
 
 

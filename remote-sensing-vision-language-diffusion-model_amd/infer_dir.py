@@ -20,7 +20,7 @@ import torch
 
 from . import parallel
 from .infer import PipelineConfig, SuperResolutionPipeline
-from .llava_next import CAPTION_DECODES, CAPTION_WEIGHTS
+from .llava_next import add_caption_arguments
 
 EXTS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 
@@ -142,18 +142,7 @@ def build_parser():
                    "fp16 x weight pairs for the layer inputs of rsvld_amd.ops.UNET_POLICY): inside 1e-3 of the reference's CPU path; see INTEGRATION.md")
     p.add_argument("--vae_split", action="store_true", help="only the VAE passes in the split-operand mode (+3 %% time, 10x closer to the CPU path)")
     p.add_argument("--device_io", action="store_true", help="the image steps around both stages on the GPU (rsvld_amd.imageops)")
-    p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: "
-                   "the checkpoint's 16-bit ones, e4m3 bytes with a scale per row, or e4m3-only: the prefill on them too and the 16-bit "
-                   "decoder weights released (opt-in; see INTEGRATION.md)")
-    p.add_argument("--caption_prefill", choices=("torch", "flash"), default="torch", help="attention of the caption pass's prefill: the "
-                   "stock-torch sequence, or the library's causal flash kernel (opt-in; with it the captions of --caption_batch N no "
-                   "longer depend on the cache length a group was prefilled at; see DESIGN.md section 8)")
-    p.add_argument("--caption_decode", choices=CAPTION_DECODES, default="valu", help="kernels of the token loop's weight-streaming products: "
-                   "on the vector ALU, or on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in: other logits; the captions "
-                   "of --caption_batch N stay those of N = 1 inside the mode; see DESIGN.md section 8)")
-    p.add_argument("--caption_batch", type=int, default=1, choices=range(1, 9), metavar="N", help="caption the Stage-1 images of N (1..8) "
-                   "inputs in one token loop (the captioner's weights are streamed once per token for all of them); the same captions "
-                   "and PNGs as N = 1 for a fixed --seed")
+    add_caption_arguments(p, batch=True)
     return p
 
 

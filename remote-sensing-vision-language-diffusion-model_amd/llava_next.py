@@ -23,10 +23,13 @@ Pinned offline by tests/test_llava_next.py against token ids, input embeddings a
 tiny seeded LLaMA + CLIP configuration (tests/golden/gen_llava_golden.py).
 """
 import ast
+import collections
+import dataclasses
 import json
 import math
 import os
 import re
+import time
 
 import torch
 from torch import nn
@@ -38,23 +41,87 @@ LLAMA3_SYSTEM = ("You are a helpful language and vision assistant. You are able 
                  "provides, and assist the user with a variety of tasks using natural language.")   # conversation.py:388
 DEFAULT_MODEL = "lmms-lab/llama3-llava-next-8b"     # models/util.py:112-114
 DEFAULT_ADAPTER = "./CKPT_PTH/Llava-next"           # models/util.py:115
-# The caption pass's weight switch -- PipelineConfig.caption_weights, --caption_weights of infer.py / infer_dir.py, decode_weights of
-# get_img_describe(_batch) -- validated against THIS tuple everywhere.  "e4m3-only": the prefill on the packs too and the 16-bit decoder
-# weights released, FastDecoder(weights="e4m3", prefill_weights="e4m3", release_native=True).
+# The caption pass's three user-level switches: PipelineConfig.caption_weights / caption_prefill / caption_decode, --caption_weights /
+# --caption_prefill / --caption_decode of infer.py and infer_dir.py, decode_weights / decode_prefill / decode_kernel of
+# get_img_describe(_batch), weights / prefill / decode of caption_tokens_fast(_batch).  ``caption_mode`` validates them -- it alone -- and
+# maps them to the ``CaptionMode`` a ``FastDecoder`` is built and compared with.
+# "e4m3-only": the prefill on the packs too and the 16-bit decoder weights released, CaptionMode(weights="e4m3", prefill_weights="e4m3",
+# release_native=True).  Decodes: "valu" runs the weight-streaming products on the vector ALU (csrc/gemv.hip); "mfma" (opt-in) on MFMAs
+# (csrc/gemv_mma.hip), whose arithmetic does not grow with the captions of a batch.  The two sum in different orders: other logits, the
+# same contract each.
 CAPTION_WEIGHTS = ("native", "e4m3", "e4m3-only")
-# The token loop's kernel switch -- PipelineConfig.caption_decode, --caption_decode of infer.py / infer_dir.py, decode_kernel of
-# get_img_describe(_batch), decode of caption_tokens_fast(_batch), FastDecoder.DECODES -- validated against THIS tuple everywhere.
-# "valu": the weight-streaming products on the vector ALU (csrc/gemv.hip); "mfma" (opt-in): on MFMAs (csrc/gemv_mma.hip), whose
-# arithmetic does not grow with the captions of a batch.  The two sum in different orders: other logits, the same contract each.
+CAPTION_PREFILLS = ("torch", "flash")
 CAPTION_DECODES = ("valu", "mfma")
 
 
+@dataclasses.dataclass(frozen=True)
+class CaptionMode:
+    """What a ``FastDecoder`` runs on, beyond its model and the size of its cache: the five switches its docstring describes.  The record
+    owns every check of a value or a combination that needs no model; two decoders serve the same calls exactly when their records are
+    equal (``_decoder_for``)."""
+    weights: str = "native"
+    prefill: str = "torch"
+    prefill_weights: str = "native"
+    release_native: bool = False
+    decode: str = "valu"
+
+    WEIGHTS = PREFILL_WEIGHTS = ("native", "e4m3")      # (un-annotated: class constants, not fields)
+
+    def __post_init__(self):
+        for name, allowed in (("decode", CAPTION_DECODES), ("weights", self.WEIGHTS), ("prefill", CAPTION_PREFILLS),
+                              ("prefill_weights", self.PREFILL_WEIGHTS)):
+            if getattr(self, name) not in allowed:
+                raise ValueError(f"FastDecoder: {name}={getattr(self, name)!r}, expected one of {allowed}")
+        if self.prefill_weights == "e4m3" and self.weights != "e4m3":
+            raise ValueError(f"FastDecoder: prefill_weights='e4m3' runs the prefill on the token loop's packs and requires weights='e4m3' "
+                             f"(got weights={self.weights!r}; there is no fallback)")
+        if self.release_native and self.prefill_weights != "e4m3":
+            raise ValueError("FastDecoder: release_native=True requires prefill_weights='e4m3' (the 16-bit weights can only go once "
+                             "nothing reads them)")
+
+
+def caption_mode(weights=None, prefill=None, decode=None, who="caption_mode", names=("weights", "prefill", "decode")):
+    """The user-level triple (a ``CAPTION_WEIGHTS``, a ``CAPTION_PREFILLS`` and a ``CAPTION_DECODES`` value; None = the default, the first
+    of its tuple) -> its ``CaptionMode``.  ``who`` / ``names``: the caller and what IT calls the three, for the error."""
+    tuples = (CAPTION_WEIGHTS, CAPTION_PREFILLS, CAPTION_DECODES)
+    weights, prefill, decode = (allowed[0] if v is None else v for v, allowed in zip((weights, prefill, decode), tuples))
+    for name, v, allowed in zip(names, (weights, prefill, decode), tuples):
+        if v not in allowed:
+            raise ValueError(f"{who}: {name}={v!r}, expected one of {allowed}")
+    only = weights == "e4m3-only"
+    return CaptionMode(weights="e4m3" if only else weights, prefill=prefill, prefill_weights="e4m3" if only else "native", release_native=only,
+                       decode=decode)
+
+
 def decoder_mode(caption_weights):
-    """A ``CAPTION_WEIGHTS`` value -> the three ``FastDecoder`` keywords it stands for."""
-    if caption_weights not in CAPTION_WEIGHTS:
-        raise ValueError(f"caption weights {caption_weights!r}, expected one of {CAPTION_WEIGHTS}")
-    only = caption_weights == "e4m3-only"
-    return dict(weights="e4m3" if only else caption_weights, prefill_weights="e4m3" if only else "native", release_native=only)
+    """A ``CAPTION_WEIGHTS`` value -> the three weight fields of its ``CaptionMode``, as ``FastDecoder`` keywords."""
+    mode = caption_mode(caption_weights, who="decoder_mode", names=("caption_weights", "prefill", "decode"))
+    return dict(weights=mode.weights, prefill_weights=mode.prefill_weights, release_native=mode.release_native)
+
+
+def add_caption_arguments(p, batch=False):
+    """``--caption_weights``, ``--caption_prefill``, ``--caption_decode`` and (``batch``: the directory runner) ``--caption_batch`` on an
+    argparse parser; the runner's help texts say what the option means for a group of captions."""
+    p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: " + (
+        "the checkpoint's 16-bit ones, e4m3 bytes with a scale per row, or e4m3-only: the prefill on them too and the 16-bit "
+        "decoder weights released (opt-in; see INTEGRATION.md)" if batch else
+        "the checkpoint's 16-bit ones, or e4m3 bytes with one power-of-two scale per output row (half the bytes of a loop bound "
+        "by nothing else; opt-in: fidelity on the real checkpoint is unmeasured; +8 GB beside the 16-bit weights); e4m3-only "
+        "runs the prefill on those bytes too and releases the 16-bit decoder weights (one model throughout, 8 GB instead of 24)"))
+    p.add_argument("--caption_prefill", choices=CAPTION_PREFILLS, default="torch", help="attention of the caption pass's prefill: the " + (
+        "stock-torch sequence, or the library's causal flash kernel (opt-in; with it the captions of --caption_batch N no "
+        "longer depend on the cache length a group was prefilled at; see DESIGN.md section 8)" if batch else
+        "stock-torch sequence over the whole cache, or the library's causal grouped-query flash kernel (fp32 scores, no score "
+        "tensor, the prefill independent of the cache length; opt-in: other logits, fidelity on the real checkpoint is unmeasured)"))
+    p.add_argument("--caption_decode", choices=CAPTION_DECODES, default="valu", help="kernels of the token loop's weight-streaming products: " + (
+        "on the vector ALU, or on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in: other logits; the captions "
+        "of --caption_batch N stay those of N = 1 inside the mode; see DESIGN.md section 8)" if batch else
+        "on the vector ALU, or on MFMAs (another summation order: other logits, within the fp32 summation error; opt-in: "
+        "fidelity on the real checkpoint is unmeasured)"))
+    if batch:
+        p.add_argument("--caption_batch", type=int, default=1, choices=range(1, 9), metavar="N", help="caption the Stage-1 images of N (1..8) "
+                       "inputs in one token loop (the captioner's weights are streamed once per token for all of them); the same captions "
+                       "and PNGs as N = 1 for a fixed --seed")
 
 
 # ------------------------------------------------------------------------------------------------ image side (host)
@@ -360,32 +427,27 @@ class FastDecoder:
     that, inside the mode, ``generate_batch`` still equals ``generate`` per prompt token for token (a row's bits do not depend on the
     row count).  An MFMA sums in another order than the fmaf chain: other logits than "valu" gives, within the summation error of
     either.  Attention, the prefill and sampling are untouched; it combines with every other switch.  The mode needs the fused decode
-    step (``_fused_ok``); where that fails the decoder raises -- it never falls back to "valu" or to torch silently."""
+    step (``_fused_ok``); where that fails the decoder raises -- it never falls back to "valu" or to torch silently.
 
-    WEIGHTS = ("native", "e4m3")
-    PREFILLS = ("torch", "flash")
-    PREFILL_WEIGHTS = ("native", "e4m3")
-    DECODES = CAPTION_DECODES
+    The five switches are ONE frozen record, ``self.mode`` (a ``CaptionMode``, which checks every value and combination that needs no
+    model); ``weights`` .. ``decode`` read it.  The weights are ONE table: per layer the products ``qkv``, ``o``, ``gu``, ``down``, then
+    ``head``, each a ``(w, b, pack)`` -- the 16-bit weight, the bias, the e4m3 pack, None where the mode has none -- which
+    ``_prefill_product`` and ``_step_product`` take."""
+
+    WEIGHTS, PREFILLS, PREFILL_WEIGHTS, DECODES = CaptionMode.WEIGHTS, CAPTION_PREFILLS, CaptionMode.PREFILL_WEIGHTS, CAPTION_DECODES
 
     MAX_BATCH = 8            # RSVLD_DECODE_MAX_ROWS
     PARKED = "_e4m3_packs"   # the model attribute (plain, like ``_fast_decoder``) that holds the packs of a model whose 16-bit weights are released
 
+    Product = collections.namedtuple("Product", "w b pack")            # one matrix product: 16-bit weight | None, bias | None, (q, scale) | None
+    LayerProducts = collections.namedtuple("LayerProducts", "qkv o gu down")
+
+    weights, prefill, prefill_weights, release_native, decode = (
+        property(lambda self, f=f: getattr(self.mode, f)) for f in ("weights", "prefill", "prefill_weights", "release_native", "decode"))
+
     def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False,
                  decode="valu"):
-        if decode not in self.DECODES:
-            raise ValueError(f"FastDecoder: decode={decode!r}, expected one of {self.DECODES}")
-        if weights not in self.WEIGHTS:
-            raise ValueError(f"FastDecoder: weights={weights!r}, expected one of {self.WEIGHTS}")
-        if prefill not in self.PREFILLS:
-            raise ValueError(f"FastDecoder: prefill={prefill!r}, expected one of {self.PREFILLS}")
-        if prefill_weights not in self.PREFILL_WEIGHTS:
-            raise ValueError(f"FastDecoder: prefill_weights={prefill_weights!r}, expected one of {self.PREFILL_WEIGHTS}")
-        if prefill_weights == "e4m3" and weights != "e4m3":
-            raise ValueError(f"FastDecoder: prefill_weights='e4m3' runs the prefill on the token loop's packs and requires weights='e4m3' "
-                             f"(got weights={weights!r}; there is no fallback)")
-        if release_native and prefill_weights != "e4m3":
-            raise ValueError("FastDecoder: release_native=True requires prefill_weights='e4m3' (the 16-bit weights can only go once "
-                             "nothing reads them)")
+        mode = CaptionMode(weights, prefill, prefill_weights, bool(release_native), decode)
         if not isinstance(batch, int) or not 1 <= batch <= self.MAX_BATCH:
             raise ValueError(f"FastDecoder: batch={batch!r}, expected 1..{self.MAX_BATCH}")
         parked = model.__dict__.get(self.PARKED)
@@ -393,9 +455,10 @@ class FastDecoder:
             raise RuntimeError(f"FastDecoder(weights={weights!r}, prefill_weights={prefill_weights!r}): this model's 16-bit decoder weights "
                                f"were released by an earlier FastDecoder(release_native=True) and only its e4m3 packs remain; reload the "
                                f"model to run on the 16-bit weights")
-        self.weights, self.batch, self.prefill, self.prefill_weights = weights, batch, prefill, prefill_weights
-        self.decode = decode
-        self.release_native = bool(release_native) or parked is not None     # (a model that is released stays so: its packs are adopted)
+        # (a model that is released stays so: its packs are adopted).  Assign a ``dataclasses.replace(dec.mode, ...)`` to switch a live
+        # decoder between modes its table serves (tools/bench_caption_e4m3_only.py: ``prefill_weights`` is read by ``forward`` alone).
+        self.mode = dataclasses.replace(mode, release_native=True) if parked is not None else mode
+        self.batch = batch
         self._row = 0            # the cache row ``forward`` reads and writes (``generate_batch`` prefills row after row)
         self._rows = {}          # generate_batch: number of sequences -> the captured step (static buffers + graph)
         self._ws_rows = None
@@ -418,21 +481,67 @@ class FastDecoder:
         self._graph = None
         self.fused = True        # the decode step through the fused kernels where their conditions hold (``_fused_ok``); False = the torch-op sequence
         self.profile = None      # a dict: generate() fills in device-synchronised seconds of its prefill and its token loop
-        # One weight-streaming GEMV for q | k | v and one for gate | up: the three (two) weight matrices of a layer become views
-        # of one concatenated tensor (no copy is kept, ``state_dict`` is unchanged), so a decode step launches 4 GEMVs per layer
-        # instead of 7.
-        self.wqkv, self.bqkv, self.wgu = [], [], []
-        if self.release_native:
-            self._packs = self._adopt_packs(parked) if parked is not None else self._pack_and_release()
-            return
-        for layer in self.layers:
-            at, mlp = layer.self_attn, layer.mlp
-            self.wqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "weight"))
-            self.bqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "bias") if at.q_proj.bias is not None else None)
-            if mlp.gate_proj.bias is not None:
-                raise NotImplementedError("FastDecoder: biased MLP projections")
-            self.wgu.append(self._fuse([mlp.gate_proj, mlp.up_proj], "weight"))
-        self._packs = self._pack_e4m3() if weights == "e4m3" else None
+        self._build_table(parked)
+
+    def _build_table(self, parked):
+        """``self.table`` (a ``LayerProducts`` per layer), ``self.head`` and ``self._packs`` (the packs alone: a 4-tuple per layer, then
+        the head's -- what is parked on a released model) in one pass over the layers.  Three questions shape a product: are parked
+        packs ADOPTED (a decoder on a model an earlier one released: the parked packs ARE the weights), is it PACKED
+        (``weights="e4m3"``), are its sources RELEASED.
+
+        One weight-streaming GEMV for q | k | v and one for gate | up: the three (two) weight matrices of a layer become views of one
+        concatenated tensor (no copy is kept, ``state_dict`` is unchanged), so a decode step launches 4 GEMVs per layer instead of 7.
+        ``release_native``: product by product -- fuse, pack, then replace the sources by empty tensors -- so allocated memory never stands
+        more than one layer's sources above the packs made so far; ``lm_head`` last (kept where it shares ``embed_tokens``' storage: a
+        tied head is packed too, only not released).  The packs are parked on the model, where a decoder built later (a longer cache,
+        more rows) finds them: their sources no longer exist."""
+        head, emb = self.model.lm_head, self.model.model.embed_tokens.weight
+        if parked is not None:
+            if any(p.numel() for p in self._released_params()) or len(parked) != len(self.layers) + 1 or parked[-1][0].device != emb.device:
+                raise RuntimeError("FastDecoder: this model's 16-bit decoder weights were released and its e4m3 packs no longer match it (a "
+                                   "parameter was assigned since, or the model was moved); reload the model")
+        elif self.weights == "e4m3":
+            for t in dict.fromkeys(self._released_params() + [head.weight]):     # every source is checked before the first one is packed or released
+                self._packable(t)
+        if any(layer.mlp.gate_proj.bias is not None for layer in self.layers):
+            raise NotImplementedError("FastDecoder: biased MLP projections")
+        tied = head.weight.untyped_storage().data_ptr() == emb.untyped_storage().data_ptr()
+        self.table = []
+        with torch.no_grad():
+            for i, layer in enumerate(self.layers):
+                at, mlp = layer.self_attn, layer.mlp
+                qkv = (at.q_proj, at.k_proj, at.v_proj)
+                b_qkv = self._fuse(qkv, "bias") if at.q_proj.bias is not None else None
+                sources = ((qkv, b_qkv), ((at.o_proj,), at.o_proj.bias), ((mlp.gate_proj, mlp.up_proj), None), ((mlp.down_proj,), None))
+                adopted = parked[i] if parked is not None else [None] * len(sources)
+                self.table.append(self.LayerProducts(*(self._product(mods, b, pack) for (mods, b), pack in zip(sources, adopted))))
+            self.head = self._product((head,), head.bias, parked[-1] if parked is not None else None, release=not tied)
+        if parked is not None:
+            self._packs = parked
+        elif self.weights == "e4m3":
+            self._packs = [tuple(p.pack for p in row) for row in self.table] + [self.head.pack]
+            if self.release_native:
+                self.model.__dict__[self.PARKED] = self._packs       # not a submodule, not a buffer: a plain attribute
+            else:   # what ``stale`` compares: a pack is a COPY, so an in-place update of its source (a LoRA merge) must be seen too
+                self._pack_state = [self._identity(t) for t in self._pack_sources()]
+        else:
+            self._packs = None
+
+    def _product(self, mods, bias, adopted, release=True):
+        """The ``Product`` of one module, or of several fused into one (their weights become views of the concatenation)."""
+        if adopted is not None:
+            return self.Product(None, bias, adopted)
+        w = self._fuse(mods, "weight") if len(mods) > 1 else mods[0].weight
+        if self.weights != "e4m3":
+            return self.Product(w, bias, None)
+        if not self.release_native:
+            from . import w8
+            return self.Product(w, bias, w8.pack_rows_e4m3(w.contiguous()))
+        pack = self._pack_tight(w.contiguous())
+        del w                                                # (the fused tensor goes with the views the modules held)
+        if release:
+            self._release(*mods)
+        return self.Product(None, bias, pack)
 
     # ------------------------------------------------------------------ release_native: the packs are the only copy of the decoder's weights
     def _released_params(self):
@@ -445,44 +554,6 @@ class FastDecoder:
         head, emb = self.model.lm_head.weight, self.model.model.embed_tokens.weight
         tied = head.numel() > 0 and head.untyped_storage().data_ptr() == emb.untyped_storage().data_ptr()
         return ps if tied else ps + [head]
-
-    def _pack_and_release(self):
-        """Layer by layer: fuse, pack the layer's four products, then replace its seven 16-bit weights by empty tensors -- allocated memory
-        never stands more than one layer's sources above the packs made so far.  ``lm_head`` last.  The packs are parked on the model,
-        where a decoder built later (a longer cache, more rows) finds them: their sources no longer exist."""
-        srcs = list(self._released_params())
-        if srcs[-1] is not self.model.lm_head.weight:
-            srcs.append(self.model.lm_head.weight)          # a tied head is packed too, only not released
-        for t in srcs:                                       # every source is checked before the first one is released
-            self._packable(t)
-        if any(layer.mlp.gate_proj.bias is not None for layer in self.layers):
-            raise NotImplementedError("FastDecoder: biased MLP projections")
-        packs = []
-        with torch.no_grad():
-            for layer in self.layers:
-                at, mlp = layer.self_attn, layer.mlp
-                self.bqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "bias") if at.q_proj.bias is not None else None)
-                wqkv = self._fuse([at.q_proj, at.k_proj, at.v_proj], "weight")
-                p_qkv = self._pack_tight(wqkv)
-                del wqkv
-                self._release(at.q_proj, at.k_proj, at.v_proj)
-                p_o = self._pack_tight(at.o_proj.weight.contiguous())
-                self._release(at.o_proj)
-                wgu = self._fuse([mlp.gate_proj, mlp.up_proj], "weight")
-                p_gu = self._pack_tight(wgu)
-                del wgu
-                self._release(mlp.gate_proj, mlp.up_proj)
-                p_down = self._pack_tight(mlp.down_proj.weight.contiguous())
-                self._release(mlp.down_proj)
-                packs.append((p_qkv, p_o, p_gu, p_down))
-                self.wqkv.append(None)
-                self.wgu.append(None)
-            head = self.model.lm_head
-            packs.append(self._pack_tight(head.weight.contiguous()))
-            if head.weight.untyped_storage().data_ptr() != self.model.model.embed_tokens.weight.untyped_storage().data_ptr():
-                self._release(head)
-        self.model.__dict__[self.PARKED] = packs             # not a submodule, not a buffer: a plain attribute
-        return packs
 
     @staticmethod
     def _pack_tight(w):
@@ -513,19 +584,6 @@ class FastDecoder:
         for m in mods:
             m.weight.data = torch.empty(0, dtype=m.weight.dtype, device=m.weight.device)
 
-    def _adopt_packs(self, parked):
-        """A decoder on a model an earlier one released: the parked packs ARE the weights."""
-        emb = self.model.model.embed_tokens.weight
-        if any(p.numel() for p in self._released_params()) or len(parked) != len(self.layers) + 1 or parked[-1][0].device != emb.device:
-            raise RuntimeError("FastDecoder: this model's 16-bit decoder weights were released and its e4m3 packs no longer match it (a "
-                               "parameter was assigned since, or the model was moved); reload the model")
-        for layer in self.layers:
-            at = layer.self_attn
-            self.bqkv.append(self._fuse([at.q_proj, at.k_proj, at.v_proj], "bias") if at.q_proj.bias is not None else None)
-            self.wqkv.append(None)
-            self.wgu.append(None)
-        return parked
-
     @staticmethod
     def _packable(t):
         if t.dim() != 2 or t.shape[1] % 16 or t.dtype not in (torch.float16, torch.bfloat16) or not t.is_cuda:
@@ -535,8 +593,8 @@ class FastDecoder:
     def _pack_sources(self):
         """The 16-bit tensors the e4m3 mode packs, in pack order: per layer q|k|v, o_proj, gate|up, down_proj; then lm_head."""
         src = []
-        for i, layer in enumerate(self.layers):
-            src += [self.wqkv[i], layer.self_attn.o_proj.weight, self.wgu[i], layer.mlp.down_proj.weight]
+        for row, layer in zip(self.table, self.layers):
+            src += [row.qkv.w, layer.self_attn.o_proj.weight, row.gu.w, layer.mlp.down_proj.weight]
         return src + [self.model.lm_head.weight]
 
     @staticmethod
@@ -546,18 +604,6 @@ class FastDecoder:
             return t.data_ptr(), t._version
         except RuntimeError:
             return t.data_ptr(), 0
-
-    def _pack_e4m3(self):
-        """-> per layer ``(qkv, o, gu, down)`` and last the ``lm_head``, each a ``(q, scale)`` of ``w8.pack_rows_e4m3``."""
-        from . import w8
-        src = self._pack_sources()
-        for t in src:
-            self._packable(t)
-        with torch.no_grad():
-            packs = [w8.pack_rows_e4m3(t.contiguous()) for t in src]
-        # what ``stale`` compares: a pack is a COPY, so an in-place update of its source (a LoRA merge) must be seen too
-        self._pack_state = [self._identity(t) for t in src]
-        return [tuple(packs[4 * i:4 * i + 4]) for i in range(len(self.layers))] + [packs[-1]]
 
     def stale(self):
         """The fused q | k | v and gate | up tensors are VIEWED by the model's own modules; ``model.to()`` / ``.half()`` / a LoRA merge /
@@ -569,10 +615,9 @@ class FastDecoder:
             return (any(p.numel() for p in self._released_params())
                     or self._packs[-1][0].device != self.model.model.embed_tokens.weight.device)
         for i in (0, len(self.layers) - 1):
-            q = self.layers[i].self_attn.q_proj.weight
-            g = self.layers[i].mlp.gate_proj.weight
-            if (q.data_ptr() != self.wqkv[i].data_ptr() or g.data_ptr() != self.wgu[i].data_ptr() or q.device != self.wqkv[i].device
-                    or q.dtype != self.wqkv[i].dtype):
+            q, wqkv = self.layers[i].self_attn.q_proj.weight, self.table[i].qkv.w
+            g, wgu = self.layers[i].mlp.gate_proj.weight, self.table[i].gu.w
+            if q.data_ptr() != wqkv.data_ptr() or g.data_ptr() != wgu.data_ptr() or q.device != wqkv.device or q.dtype != wqkv.dtype:
                 return True
         if self._packs is not None:      # the e4m3 packs are copies: same storage, not written since, and on the weights' device
             src = self._pack_sources()
@@ -602,6 +647,25 @@ class FastDecoder:
             from . import ops
             return ops.gemv(w, x[0].contiguous(), b)[None]
         return torch.nn.functional.linear(x, w, b)
+
+    def _prefill_product(self, p, x):
+        """``x [T, K]`` times product ``p`` in ``forward``.  ``prefill_weights="e4m3"``: on the token loop's pack -- the 16-bit weights
+        are not read -- through the tile GEMM, and ONE row (the last position under ``lm_head``) through the matrix-vector product of the
+        decode step; else ``_lin`` on the 16-bit weight."""
+        if self.prefill_weights != "e4m3":
+            return self._lin(x, p.w, p.b)
+        from . import w8
+        if x.shape[0] == 1:
+            return w8.gemv_w8(*p.pack, x[0].contiguous(), p.b)[None]
+        return w8.linear_w8(*p.pack, x.contiguous(), p.b)
+
+    def _step_product(self, p, x, **fused):
+        """``x [n, K]`` times product ``p`` in the fused decode step of ``n`` rows, on the pack where the decoder has packs, with the
+        neighbours ``fused`` in (``norm=``, ``residual=``, ``glu=``), on the kernels of ``decode``."""
+        from . import decode_rows as DR
+        if p.pack is not None:
+            return DR.gemv_w8_rows(*p.pack, x, p.b, kernel=self.decode, **fused)
+        return DR.gemv_rows(p.w, x, p.b, kernel=self.decode, **fused)
 
     def forward(self, embeds, pos, pos0=None):
         """``embeds [1, T, H]`` at absolute positions ``pos [T]`` (long, on the device) -> logits of the LAST position
@@ -635,19 +699,10 @@ class FastDecoder:
             bias.masked_fill_(self.cols[None, :] > pos[:, None], float("-inf"))   # causal over the filled prefix
         scale = hd ** -0.5
         h = embeds[0]                                                               # [T, H]
-        if self.prefill_weights == "e4m3":     # (T > 1 here) every product on the token loop's packs: the 16-bit weights are not read
-            from . import w8
-
-            def lin(x, w, b=None, *, pack):
-                return w8.linear_w8(*pack, x.contiguous(), b)
-        else:
-            def lin(x, w, b=None, *, pack):
-                return self._lin(x, w, b)
-        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
-        for i, layer in enumerate(self.layers):
-            p_qkv, p_o, p_gu, p_down = packs[i]
+        lin = self._prefill_product
+        for i, (layer, w) in enumerate(zip(self.layers, self.table)):
             x = self._rms(h, layer.input_layernorm)
-            qkv = lin(x, self.wqkv[i], self.bqkv[i], pack=p_qkv).view(T, nq + 2 * nkv, hd)
+            qkv = lin(w.qkv, x).view(T, nq + 2 * nkv, hd)
             qk = qkv[:, :nq + nkv]
             half = hd // 2
             qk = qk * cos + torch.cat((-qk[..., half:], qk[..., :half]), dim=-1) * sin     # rotary embedding on q and k at once
@@ -661,15 +716,12 @@ class FastDecoder:
                 sc = torch.matmul(q, kc.transpose(1, 2)).float().view(nkv, T, g, self.max_len)
                 pr = torch.softmax(sc * scale + bias[None, :, None, :], dim=-1).to(self.dt).view(nkv, T * g, self.max_len)
                 o = torch.matmul(pr, vc).view(nkv, T, g, hd).permute(1, 0, 2, 3).reshape(T, nq * hd)
-            h = h + lin(o, layer.self_attn.o_proj.weight, layer.self_attn.o_proj.bias, pack=p_o)
+            h = h + lin(w.o, o)
             x = self._rms(h, layer.post_attention_layernorm)
-            gu = lin(x, self.wgu[i], pack=p_gu)
+            gu = lin(w.gu, x)
             inter = gu.shape[-1] // 2
-            h = h + lin(torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:], layer.mlp.down_proj.weight, pack=p_down)
-        last = self._rms(h[-1:], m.norm)
-        if self.prefill_weights == "e4m3":     # ONE row: the matrix-vector product of the decode step, on the same pack
-            return w8.gemv_w8(*packs[-1], last[0].contiguous(), self.model.lm_head.bias)[None]
-        return self._lin(last, self.model.lm_head.weight, self.model.lm_head.bias)
+            h = h + lin(w.down, torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:])
+        return lin(self.head, self._rms(h[-1:], m.norm))
 
     def _fused_ok(self, embeds):
         """The decode step as the library's fused kernels (rsvld_gemv_fused, rsvld_llama_decode_attention): 16-bit tensors on the GPU, head_dim
@@ -721,26 +773,14 @@ class FastDecoder:
         use_graph = (self.dev.type == "cuda") if use_graph is None else use_graph
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         embed = self.model.model.embed_tokens
-        if self.profile is not None:
-            import time
-            torch.cuda.current_stream().synchronize()   # (this stream only: a caller may run other work on a second stream beside the token loop)
-            t_start = time.perf_counter()
+        t_start = self._stamp()
         logits = self.forward(inputs_embeds.to(self.dt), torch.arange(T0, device=self.dev), pos0=0)
         tok = self._pick(logits, do_sample, temperature, top_k, top_p)
         out = [tok]
-        if self.profile is not None:
-            torch.cuda.current_stream().synchronize()   # (this stream only: a caller may run other work on a second stream beside the token loop)
-            t_prefill = time.perf_counter()
-        if use_graph and self._graph is None:
-            self._tok, self._pos = tok.clone(), torch.tensor([T0], device=self.dev)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                              # warm-up off the capture stream (allocator, lazy init);
-                self.forward(embed(self._tok)[None], self._pos)        # it rewrites cache slot T0 with the same values
-            torch.cuda.current_stream().wait_stream(side)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._logits = self.forward(embed(self._tok)[None], self._pos)
+        t_prefill = self._stamp()
+        if use_graph and self._graph is None:                          # (the warm-up rewrites cache slot T0 with the same values)
+            self._tok, self._pos, self._logits, self._graph = self._capture(lambda e, p: self.forward(e[None], p), tok.clone(),
+                                                                            torch.tensor([T0], device=self.dev))
         for n in range(1, max_new_tokens):
             if eos and int(tok) in eos:
                 break
@@ -754,10 +794,31 @@ class FastDecoder:
             tok = self._pick(logits, do_sample, temperature, top_k, top_p)
             out.append(tok)
         if self.profile is not None:
-            torch.cuda.current_stream().synchronize()   # (this stream only: a caller may run other work on a second stream beside the token loop)
-            self.profile.update(prompt_tokens=T0, prefill_s=t_prefill - t_start, decode_s=time.perf_counter() - t_prefill,
-                                new_tokens=len(out))
+            self.profile.update(prompt_tokens=T0, prefill_s=t_prefill - t_start, decode_s=self._stamp() - t_prefill, new_tokens=len(out))
         return torch.cat(out)
+
+    def _stamp(self):
+        """``profile`` bookkeeping: the host time once this stream's work is done (this stream only: a caller may run other work on a
+        second stream beside the token loop); None while no profile is asked for."""
+        if self.profile is None:
+            return None
+        torch.cuda.current_stream().synchronize()
+        return time.perf_counter()
+
+    def _capture(self, step, tok, pos):
+        """``step(embeddings of tok, pos)`` -- the decode step on the static buffers ``tok`` / ``pos`` -- warmed up on a side stream (off
+        the capture stream: allocator, lazy init; it rewrites the cache slots at ``pos`` with the same values), then captured as ONE
+        stream's linear chain of launches -> ``(tok, pos, logits, graph)``."""
+        embed = self.model.model.embed_tokens
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            step(embed(tok), pos)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            logits = step(embed(tok), pos)
+        return tok, pos, logits, graph
 
     # ------------------------------------------------------------------ several captions in one token loop
     def _forward_rows(self, h, pos, row0=0):
@@ -781,26 +842,16 @@ class FastDecoder:
             # them).  Per-chunk partial results: written before they are read, no initial state.
             need = int(DR.ops.L.load().rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
             self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
-        kern = {} if self.decode == "valu" else {"kernel": self.decode}     # ("valu": the call as it always was)
-        if self._packs is not None:
-            def gemv(which, w, *a, **kw):        # the same call on the pack of ``w``
-                return DR.gemv_w8_rows(*which, *a, **kw, **kern)
-        else:
-            def gemv(which, w, *a, **kw):
-                return DR.gemv_rows(w, *a, **kw, **kern)
-        packs = self._packs if self._packs is not None else [(None,) * 4] * len(self.layers) + [None]
-        for i, layer in enumerate(self.layers):
+        gemv = self._step_product
+        for i, (layer, w) in enumerate(zip(self.layers, self.table)):
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
-            p_qkv, p_o, p_gu, p_down = packs[i]
-            qkv = gemv(p_qkv, self.wqkv[i], h, self.bqkv[i], norm=(n1.weight, n1.variance_epsilon))
+            qkv = gemv(w.qkv, h, norm=(n1.weight, n1.variance_epsilon))
             o = DR.llama_decode_attention_rows(qkv, cos, sin, pos, self.k[i][row0:row0 + n], self.v[i][row0:row0 + n], self.n_q, self.n_kv, scale,
                                                ws=self._ws_rows)
-            op = layer.self_attn.o_proj
-            h = gemv(p_o, op.weight, o, op.bias, residual=h)
-            gu = gemv(p_gu, self.wgu[i], h, None, norm=(n2.weight, n2.variance_epsilon))
-            h = gemv(p_down, layer.mlp.down_proj.weight, gu, None, glu=True, residual=h)
-        head = self.model.lm_head
-        return gemv(packs[-1], head.weight, h, head.bias, norm=(m.norm.weight, m.norm.variance_epsilon))
+            h = gemv(w.o, o, residual=h)
+            gu = gemv(w.gu, h, norm=(n2.weight, n2.variance_epsilon))
+            h = gemv(w.down, gu, glu=True, residual=h)
+        return gemv(self.head, h, norm=(m.norm.weight, m.norm.variance_epsilon))
 
     def _row_generators(self, n, seeds):
         if seeds is None:
@@ -850,10 +901,7 @@ class FastDecoder:
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         embed = self.model.model.embed_tokens
         gens = self._row_generators(n, seeds)
-        if self.profile is not None:
-            import time
-            torch.cuda.current_stream().synchronize()
-            t_start = time.perf_counter()
+        t_start = self._stamp()
         first = []
         try:
             for b, e in enumerate(inputs_embeds):                      # prefill: matrix-bound, one prompt at a time, into cache row b
@@ -864,21 +912,10 @@ class FastDecoder:
             self._row = 0
         toks = torch.cat(first)                                        # [n]
         pos = torch.tensor(T0s, device=self.dev)
-        if self.profile is not None:
-            torch.cuda.current_stream().synchronize()
-            t_prefill = time.perf_counter()
+        t_prefill = self._stamp()
         st = self._rows.get(n) if use_graph else None
         if use_graph and st is None:
-            st = {"tok": toks.clone(), "pos": pos.clone()}
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                              # warm-up off the capture stream; it rewrites the cache slots
-                self._forward_rows(embed(st["tok"]), st["pos"])        # at ``pos`` with the same values
-            torch.cuda.current_stream().wait_stream(side)
-            st["graph"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(st["graph"]):                        # one stream, a linear chain of launches
-                st["logits"] = self._forward_rows(embed(st["tok"]), st["pos"])
-            self._rows[n] = st
+            st = self._rows[n] = dict(zip(("tok", "pos", "logits", "graph"), self._capture(self._forward_rows, toks.clone(), pos.clone())))
         host = toks.tolist()
         out = [[t] for t in first]
         done = [bool(eos) and host[b] in eos for b in range(n)]
@@ -913,8 +950,7 @@ class FastDecoder:
             if changed:
                 live = torch.tensor([0 if d else 1 for d in done], device=self.dev)
         if self.profile is not None:
-            torch.cuda.current_stream().synchronize()
-            self.profile.update(prompt_tokens=T0s, prefill_s=t_prefill - t_start, decode_s=time.perf_counter() - t_prefill,
+            self.profile.update(prompt_tokens=T0s, prefill_s=t_prefill - t_start, decode_s=self._stamp() - t_prefill,
                                 new_tokens=[len(o) for o in out], steps=steps, rows=n)
         return [torch.cat(o) for o in out]
 
@@ -1073,51 +1109,20 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     replayed from a hipGraph) instead of ``transformers``' ``generate``; same tokens (tests/test_llava_next.py).
     ``decode_weights`` (None = "native"): "e4m3" streams the token loop's weights as e4m3 bytes (``FastDecoder(weights=...)``, opt-in:
     other logits than the 16-bit weights give); "e4m3-only" runs the prefill on those bytes too and RELEASES the model's 16-bit decoder
-    weights (``CAPTION_WEIGHTS``, ``decoder_mode``: afterwards the model serves this mode only, until it is reloaded); both need the
+    weights (``CAPTION_WEIGHTS``, ``caption_mode``: afterwards the model serves this mode only, until it is reloaded); both need the
     fast path, anything else raises.
     ``decode_prefill`` (None = "torch"): "flash" runs the prefill's attention through the causal flash kernel
     (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too.
     ``decode_kernel`` (None = "valu"): "mfma" runs the token loop's products on MFMAs (``FastDecoder(decode=...)``, ``CAPTION_DECODES``,
     opt-in: other logits, within the summation error); it needs the fast path too."""
-    decode_kernel = "valu" if decode_kernel is None else decode_kernel
-    if decode_kernel not in CAPTION_DECODES:
-        raise ValueError(f"get_img_describe: decode_kernel={decode_kernel!r}, expected one of {CAPTION_DECODES}")
-    decode_weights = "native" if decode_weights is None else decode_weights
-    if decode_weights not in CAPTION_WEIGHTS:
-        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r}, expected one of {CAPTION_WEIGHTS}")
-    decode_prefill = "torch" if decode_prefill is None else decode_prefill
-    if decode_prefill not in FastDecoder.PREFILLS:
-        raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
-    if conv_template != "llava_llama_3":
-        raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
-    system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
-    text = llama3_prompt(tokenizer, prompt, system)
-    input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
-    mdev = next(model.parameters()).device
-    fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
-    if fast and _has_logits_warpers(model):
-        # FastDecoder implements generate()'s temperature / top_k / top_p chain; a generation_config with typical_p, min_p, penalties or
-        # banned tokens goes through transformers' generate() (~4 x slower per token), and says so
-        import warnings
-        warnings.warn("llava_next: the checkpoint's generation_config asks for logits processors FastDecoder does not implement; "
-                      "captioning through transformers' generate()")
-        fast = False
-    if decode_weights != "native" and not fast:
-        raise ValueError(f"get_img_describe: decode_weights={decode_weights!r} needs the FastDecoder token loop (a GPU model, one beam, no "
-                         f"logits processors beyond temperature / top_k / top_p)")
-    if decode_prefill != "torch" and not fast:
-        raise ValueError(f"get_img_describe: decode_prefill={decode_prefill!r} needs the FastDecoder token loop (a GPU model, one beam, no "
-                         f"logits processors beyond temperature / top_k / top_p)")
-    if decode_kernel != "valu" and not fast:
-        raise ValueError(f"get_img_describe: decode_kernel={decode_kernel!r} needs the FastDecoder token loop (a GPU model, one beam, no "
-                         f"logits processors beyond temperature / top_k / top_p)")
+    input_ids, mdev, fast, options = _describe_setup("get_img_describe", model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
+                                                     num_beams, device, fast, decode_weights, decode_prefill, decode_kernel)
 
     def run():
         if fast:   # (no_grad, not inference_mode: tensors made in inference mode cannot be updated in place by a later call
             with torch.no_grad():   # outside it, and a hipGraph capture that fails on that leaves the generator in capture state)
                 return caption_tokens_fast(model, input_ids, image_tensor, [image.size], max_new_tokens, do_sample, temperature,
-                                           _eos_ids(model, tokenizer), weights=decode_weights, prefill=decode_prefill,
-                                           **_decode_keyword(decode_kernel))
+                                           _eos_ids(model, tokenizer), **options)
         with torch.inference_mode():
             return model.generate(input_ids, images=image_tensor, image_sizes=[image.size], do_sample=do_sample,
                                   temperature=temperature, num_beams=num_beams, max_new_tokens=max_new_tokens,
@@ -1147,40 +1152,56 @@ def _has_logits_warpers(model):
             or bool(getattr(g, "suppress_tokens", None)))
 
 
-def _decoder_fields(dec):
-    """The three fields of a decoder that ``decoder_mode`` names: what ``caption_tokens_fast(_batch)`` compare to decide a rebuild."""
-    return dict(weights=dec.weights, prefill_weights=getattr(dec, "prefill_weights", "native"), release_native=getattr(dec, "release_native", False))
+def _describe_setup(who, model, tokenizer, prompt, conv_templates, image_token_index, conv_template, num_beams, device, fast, decode_weights,
+                    decode_prefill, decode_kernel):
+    """What ``get_img_describe`` and ``get_img_describe_batch`` (``who``) do before they caption: validate the three options and the
+    template, tokenise the prompt, decide ``fast`` -> ``(input_ids, the model's device, fast, the options as caption_tokens_fast(_batch)
+    keywords)``.  An option that is not its default needs the fast path and raises without it."""
+    names, options = ("decode_weights", "decode_prefill", "decode_kernel"), dict(weights=decode_weights, prefill=decode_prefill, decode=decode_kernel)
+    default = caption_mode()
+    mode = caption_mode(**options, who=who, names=names)
+    if conv_template != "llava_llama_3":
+        raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
+    system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
+    text = llama3_prompt(tokenizer, prompt, system)
+    input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
+    mdev = next(model.parameters()).device
+    fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
+    if fast and _has_logits_warpers(model):
+        # FastDecoder implements generate()'s temperature / top_k / top_p chain; a generation_config with typical_p, min_p, penalties or
+        # banned tokens goes through transformers' generate() (~4 x slower per token), and says so
+        import warnings
+        warnings.warn("llava_next: the checkpoint's generation_config asks for logits processors FastDecoder does not implement; "
+                      "captioning through transformers' generate()")
+        fast = False
+    for name, field, value in zip(names, ("weights", "prefill", "decode"), options.values()):
+        if getattr(mode, field) != getattr(default, field) and not fast:
+            raise ValueError(f"{who}: {name}={value!r} needs the FastDecoder token loop (a GPU model, one beam, no logits processors beyond "
+                             f"temperature / top_k / top_p)")
+    return input_ids, mdev, fast, options
 
 
-def _decode_keyword(decode):
-    """``decode`` as a keyword only where it is not the default: a stand-in with the earlier signature keeps working for "valu"."""
-    return {} if decode == "valu" else {"decode": decode}
-
-
-def _decoder_keywords(mode):
-    """``decoder_mode``'s keywords as the constructor gets them: the two later ones only where they are not the defaults, so that a
-    stand-in decoder class with the three-keyword signature keeps working for "native" and "e4m3"."""
-    return mode if mode["release_native"] else dict(weights=mode["weights"])
+def _decoder_for(model, need, rows, mode):
+    """The model's ``FastDecoder`` (a plain attribute, ``model._fast_decoder``: not a submodule) for ``rows`` captions of ``need`` cache
+    positions in ``mode``.  The one it has serves unless it is ``stale()`` -- the model was moved / cast / reloaded since the decoder
+    fused its weights -- or in another mode, or holds fewer rows or a shorter cache; else it is dropped -- its cache, packs and captured
+    graphs go before the new ones are allocated -- and one is built with ``rows`` rows and the cache length rounded up to 256."""
+    dec = getattr(model, "_fast_decoder", None)
+    if dec is None or dec.stale() or dec.mode != mode or dec.batch < rows or dec.max_len < need:
+        model.__dict__.pop("_fast_decoder", None)
+        del dec
+        model.__dict__["_fast_decoder"] = FastDecoder(model, -(-need // 256) * 256, batch=rows, **dataclasses.asdict(mode))
+    return model._fast_decoder
 
 
 def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
                         prefill="torch", decode="valu"):
     """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode,
-    prefill mode and decode kernel: asking for another mode rebuilds the decoder, its packs and its captured graph)."""
-    if decode not in CAPTION_DECODES:
-        raise ValueError(f"caption_tokens_fast: decode={decode!r}, expected one of {CAPTION_DECODES}")
+    prefill mode and decode kernel: asking for another mode rebuilds the decoder, its packs and its captured graph; ``_decoder_for``).
+    It goes on using a decoder with more rows than one."""
+    mode = caption_mode(weights, prefill, decode, who="caption_tokens_fast")
     embeds = model.multimodal_embeds(input_ids, images, image_sizes)
-    need = embeds.shape[1] + max_new_tokens
-    dec = getattr(model, "_fast_decoder", None)
-    if dec is not None and dec.stale():     # the model was moved / cast / reloaded since the decoder fused its weights: rebuild
-        dec = None
-    mode = decoder_mode(weights)
-    if dec is not None and (_decoder_fields(dec) != mode or dec.prefill != prefill or getattr(dec, "decode", "valu") != decode):
-        dec = None
-    if dec is None or dec.max_len < need:
-        model.__dict__.pop("_fast_decoder", None)      # (the old decoder's cache and packs go before the new ones are allocated)
-        dec = FastDecoder(model, -(-need // 256) * 256, prefill=prefill, **_decoder_keywords(mode), **_decode_keyword(decode))
-        model.__dict__["_fast_decoder"] = dec          # not a submodule: plain attribute
+    dec = _decoder_for(model, embeds.shape[1] + max_new_tokens, 1, mode)
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
 
 
@@ -1188,25 +1209,14 @@ def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tok
                               seeds=None, prefill="torch", decode="valu"):
     """``caption_tokens_fast`` for several images under ONE prompt: ``images[b]`` / ``image_sizes[b]`` are the views and the size of image
     ``b`` -> a list of token tensors, each equal to ``caption_tokens_fast`` on that image alone (under ``seeds[b]``, see
-    ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another weight mode, or
-    for a longer cache -- like ``caption_tokens_fast``, which goes on using a decoder with more rows than one.  The cache length is this
+    ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another mode, or for a
+    longer cache (``_decoder_for``).  The cache length is this
     group's longest prompt plus the new tokens, rounded up to 256 (kept if the decoder's is longer); the prefill runs over it, so the equality
     with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it) -- or, with
     ``prefill="flash"``, at any cache length: that prefill does not depend on it either.  ``decode``: as in ``caption_tokens_fast``."""
-    if decode not in CAPTION_DECODES:
-        raise ValueError(f"caption_tokens_fast_batch: decode={decode!r}, expected one of {CAPTION_DECODES}")
+    mode = caption_mode(weights, prefill, decode, who="caption_tokens_fast_batch")
     embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
-    need = max(e.shape[1] for e in embeds) + max_new_tokens
-    dec = getattr(model, "_fast_decoder", None)
-    mode = decoder_mode(weights)
-    if dec is not None and (dec.stale() or _decoder_fields(dec) != mode or dec.prefill != prefill or dec.batch < len(embeds)
-                            or getattr(dec, "decode", "valu") != decode):
-        dec = None
-    if dec is None or dec.max_len < need:
-        model.__dict__.pop("_fast_decoder", None)
-        dec = FastDecoder(model, -(-need // 256) * 256, batch=len(embeds), prefill=prefill, **_decoder_keywords(mode),
-                          **_decode_keyword(decode))
-        model.__dict__["_fast_decoder"] = dec
+    dec = _decoder_for(model, max(e.shape[1] for e in embeds) + max_new_tokens, len(embeds), mode)
     return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
 
 
@@ -1221,28 +1231,13 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     n = len(images)
     if len(image_tensors) != n or (seeds is not None and len(seeds) != n):
         raise ValueError(f"get_img_describe_batch: {len(image_tensors)} view lists and {None if seeds is None else len(seeds)} seeds for {n} images")
-    decode_weights = "native" if decode_weights is None else decode_weights
-    if decode_weights not in CAPTION_WEIGHTS:
-        raise ValueError(f"get_img_describe_batch: decode_weights={decode_weights!r}, expected one of {CAPTION_WEIGHTS}")
-    decode_prefill = "torch" if decode_prefill is None else decode_prefill
-    if decode_prefill not in FastDecoder.PREFILLS:
-        raise ValueError(f"get_img_describe_batch: decode_prefill={decode_prefill!r}, expected one of {FastDecoder.PREFILLS}")
-    decode_kernel = "valu" if decode_kernel is None else decode_kernel
-    if decode_kernel not in CAPTION_DECODES:
-        raise ValueError(f"get_img_describe_batch: decode_kernel={decode_kernel!r}, expected one of {CAPTION_DECODES}")
-    mdev = next(model.parameters()).device
-    use_fast = (mdev.type == "cuda" and num_beams == 1) if fast is None else fast
-    if not use_fast or _has_logits_warpers(model) or n > FastDecoder.MAX_BATCH:
+    input_ids, _, use_fast, options = _describe_setup("get_img_describe_batch", model, tokenizer, prompt, conv_templates, image_token_index,
+                                                      conv_template, num_beams, device, fast, decode_weights, decode_prefill, decode_kernel)
+    if not use_fast or n > FastDecoder.MAX_BATCH:
         return [get_img_describe(image_tensors[b], images[b], model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
-                                 num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], fast,
+                                 num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], use_fast,
                                  decode_weights, decode_prefill, decode_kernel)[0] for b in range(n)]
-    if conv_template != "llava_llama_3":
-        raise NotImplementedError("the pipeline's captioner is the Llama-3 LLaVA-NeXT (conv_template 'llava_llama_3')")
-    system = getattr(conv_templates[conv_template], "system", LLAMA3_SYSTEM)
-    text = llama3_prompt(tokenizer, prompt, system)
-    input_ids = tokenizer_image_token(text, tokenizer, image_token_index, return_tensors="pt").unsqueeze(0).to(device)
     with torch.no_grad():
         outs = caption_tokens_fast_batch(model, input_ids, image_tensors, [im.size for im in images], max_new_tokens, do_sample, temperature,
-                                         _eos_ids(model, tokenizer), weights=decode_weights, seeds=seeds, prefill=decode_prefill,
-                                         **_decode_keyword(decode_kernel))
+                                         _eos_ids(model, tokenizer), seeds=seeds, **options)
     return [tokenizer.decode(o.cpu().tolist(), skip_special_tokens=True).lstrip() for o in outs]

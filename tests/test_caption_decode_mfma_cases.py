@@ -9,6 +9,7 @@ import types
 import pytest
 import torch
 
+from decoder_stand_in import stand_in_decoder
 from test_decode_rows_cases import StubPipe, _processor, cpu_llama   # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,21 +106,7 @@ def test_get_img_describe_validates_and_the_mode_reaches_the_decoder(monkeypatch
     with pytest.raises(ValueError, match="decode_kernel"):
         LN.get_img_describe_batch([None], [None], None, None, "p", decode_kernel="x")
     built = []
-
-    class Dec:
-        def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", decode="valu"):
-            self.max_len, self.weights, self.batch, self.prefill, self.decode = max_len, weights, batch, prefill, decode
-            built.append(decode)
-
-        def stale(self):
-            return False
-
-        def generate(self, embeds, n, **kw):
-            return torch.zeros(1, dtype=torch.long)
-
-        def generate_batch(self, embeds, n, **kw):
-            return [torch.zeros(1, dtype=torch.long) for _ in embeds]
-    monkeypatch.setattr(LN, "FastDecoder", Dec)
+    monkeypatch.setattr(LN, "FastDecoder", stand_in_decoder(built, lambda mode: mode.decode))
     model = types.SimpleNamespace(multimodal_embeds=lambda ids, im, sizes: torch.zeros(1, 7, 4))
     LN.caption_tokens_fast(model, None, None, None, 8, False, 1.0)
     LN.caption_tokens_fast(model, None, None, None, 8, False, 1.0)

@@ -9,6 +9,8 @@ from pathlib import Path
 import pytest
 import torch
 
+from decoder_stand_in import stand_in_decoder
+
 ROOT = Path(__file__).resolve().parents[1]
 
 
@@ -103,21 +105,7 @@ def test_get_img_describe_validates_and_forwards_decode_prefill(monkeypatch):
         LN.get_img_describe_batch([None], [None], None, None, "p", decode_prefill="x")
     # the decoder of the other mode is rebuilt; the mode reaches FastDecoder
     built = []
-
-    class Dec:
-        def __init__(self, model, max_len, weights="native", batch=1, prefill="torch"):
-            self.max_len, self.weights, self.batch, self.prefill = max_len, weights, batch, prefill
-            built.append(prefill)
-
-        def stale(self):
-            return False
-
-        def generate(self, embeds, n, **kw):
-            return torch.zeros(1, dtype=torch.long)
-
-        def generate_batch(self, embeds, n, **kw):
-            return [torch.zeros(1, dtype=torch.long) for _ in embeds]
-    monkeypatch.setattr(LN, "FastDecoder", Dec)
+    monkeypatch.setattr(LN, "FastDecoder", stand_in_decoder(built, lambda mode: mode.prefill))
     model = types.SimpleNamespace(multimodal_embeds=lambda ids, im, sizes: torch.zeros(1, 7, 4))
     LN.caption_tokens_fast(model, None, None, None, 8, False, 1.0)
     LN.caption_tokens_fast(model, None, None, None, 8, False, 1.0)

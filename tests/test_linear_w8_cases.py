@@ -11,6 +11,7 @@ from pathlib import Path
 import pytest
 import torch
 
+from decoder_stand_in import stand_in_decoder
 from test_gpu_w8 import build_exact
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -204,22 +205,7 @@ def test_value_reaches_get_img_describe_and_the_decoder(tmp_path, monkeypatch):
     monkeypatch.undo()
 
     built = []
-
-    class Dec:
-        def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False):
-            self.max_len, self.weights, self.batch, self.prefill = max_len, weights, batch, prefill
-            self.prefill_weights, self.release_native = prefill_weights, release_native
-            built.append((weights, prefill_weights, release_native))
-
-        def stale(self):
-            return False
-
-        def generate(self, embeds, n, **kw):
-            return torch.zeros(1, dtype=torch.long)
-
-        def generate_batch(self, embeds, n, **kw):
-            return [torch.zeros(1, dtype=torch.long) for _ in embeds]
-    monkeypatch.setattr(LN, "FastDecoder", Dec)
+    monkeypatch.setattr(LN, "FastDecoder", stand_in_decoder(built, lambda mode: (mode.weights, mode.prefill_weights, mode.release_native)))
     model = types.SimpleNamespace(multimodal_embeds=lambda ids, im, sizes: torch.zeros(1, 7, 4))
     only, e4 = ("e4m3", "e4m3", True), ("e4m3", "native", False)
     LN.caption_tokens_fast(model, None, None, None, 8, False, 1.0, weights="e4m3-only")

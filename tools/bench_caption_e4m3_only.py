@@ -17,6 +17,7 @@ The released decoder is built LAST: it empties the model.  There is no threshold
     python tools/bench_caption_e4m3_only.py --out profiles/caption_e4m3_only_ab.txt
 """
 import argparse
+import dataclasses
 import gc
 import os
 import sys
@@ -138,7 +139,7 @@ def main(argv=None):
             return _median(out), min(out), max(out)
 
         def prefill(dec, pw):
-            dec.prefill_weights = pw
+            dec.mode = dataclasses.replace(dec.mode, prefill_weights=pw)
             dec.profile = {}
             tok = dec.generate(emb, 1, do_sample=False, use_graph=False)
             p, dec.profile = dec.profile, None
@@ -154,9 +155,9 @@ def main(argv=None):
             for pw in ("native", "e4m3"):                          # warm-up: allocator, library algorithm choices, code objects
                 prefill(dec, pw)
                 prefill(dec, pw)
-            dec.prefill_weights = "native"
+            dec.mode = dataclasses.replace(dec.mode, prefill_weights="native")
             l16 = dec.forward(emb.to(torch.float16), torch.arange(a.prompt, device=dev), pos0=0).float()
-            dec.prefill_weights = "e4m3"
+            dec.mode = dataclasses.replace(dec.mode, prefill_weights="e4m3")
             l8 = dec.forward(emb.to(torch.float16), torch.arange(a.prompt, device=dev), pos0=0).float()
             log(f"\n## prefill, attention route '{route}': prefill_s of weights='e4m3' with the 16-bit prefill (A) vs prefill_weights='e4m3' (B), alternating pairs")
             log(f"prefill logits: max |B - A| = {float((l8 - l16).abs().max()):.3e} (max |A| = {float(l16.abs().max()):.3e}); argmax equal: "
