@@ -24,17 +24,6 @@ struct AttnArgs {
     unsigned long long* dbg;   // diagnostic builds only (-DA6B_STAMP=1): per-wave cycle sums of the loop's phases, else unused
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// compile-time loop: f(std::integral_constant<int, i>) for i = 0..N-1 (inline-asm "i" operands need constants)
-template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 constexpr float A5_DEFER_LOG2 = 8.0f;   // rescale O only when a row's running max grows by more than 2^8
 
 // ---------------------------------------------------------------------------------------
@@ -54,11 +43,8 @@ constexpr float A5_DEFER_LOG2 = 8.0f;   // rescale O only when a row's running m
 // Split-KV: when the query tiles alone cannot fill the chip, blockIdx.y walks key ranges and the
 // partial (O / l, m, l) triples are merged by attn_combine_kernel.
 // ---------------------------------------------------------------------------------------
-// M0: the d = 512 kernel's LDS-DMA statements write M0 and declare it clobbered instead of saving and restoring it around every
-// piece (2 scalar instructions fewer per piece, and no restore that waits behind the DMA's own read of M0: +2.5 % at 262 144 keys,
-// profiles/r03_attn_d64_ab.txt, run 7).  hipcc reserves M0 and only warns; the build is sound because the COMPILER never touches M0
-// in this translation unit, which tools/audit_m0.py / tests/test_build_audits.py check on the assembly.  attn_d64b keeps the
-// save / restore form: with the clobber form it ran 12 % SLOWER (same run).
+// M0: the d = 512 kernels' LDS-DMA statements are the form that declares M0 clobbered, attn_d64b's the form that saves and restores it
+// (the note on the LDS-DMA helpers in rsvld_common.h).
 // A5B_KEYWRAP = n > 0 (diagnostic build, round 5; results WRONG, timing only): the steady-state LDS-DMA requests of key tile t read tile
 // t mod n (n a power of two), i.e. the whole key stream of a launch cycles over n x 32 KiB -- n = 64: 2 MiB, resident in every XCD's
 // 4 MiB L2 -- with the same loop trip count, the same LDS traffic and the same MFMAs.  What the L2-MISS traffic of the real launch
@@ -88,16 +74,74 @@ constexpr int A5B_SMEM = 4 * A5B_TILE;     // K[2] | V[2]
 //     ((lh + 2 hf) & 3) only permute chunks inside a row's own quarter.
 constexpr int A5B_SMEM_SH = 3 * A5B_TILE;  // X[3]
 __host__ __device__ constexpr int a5b_f(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 // maximum over lane and lane ^ 32: ds_bpermute (what __shfl_xor compiles to).  v_permlane32_swap lost 4 % here (one wave per SIMD:
 // its own latency and hazard padding cost more than the reads the ds_bpermute's wait drains; profiles/r03_attn_d64_ab.txt, run 17)
 __device__ __forceinline__ float a5b_halfwave_max(float mx) { return fmaxf(mx, __shfl_xor(mx, 32)); }
+
+// ---- S^T[key][q] of the d = 512 kernels (attn_d512b, attn_d512d) over the whole head dimension: one accumulation chain of 32 MFMAs
+// per tile.  The chain is issued in its VGPR form by inline asm: all 256 accumulator registers belong to O, and hipcc
+// otherwise parks the score tile in a0..a15 and shuttles one O tile through VGPRs every iteration.  Back-to-back
+// MFMAs that take the previous D whole as C need no wait states.  The K fragment reads are asm as well: hipcc
+// waits lgkmcnt(0) in front of an asm consumer, which stalls the chain on the read it has just issued; here A5_KD
+// reads are in flight and MFMA ks waits only for its own (lgkmcnt(min(KD-1, 31-ks)); LDS returns in order, and any
+// SMEM operation the compiler may have in flight only makes the count more conservative).
+// HOOK(i), i = 0..7, runs after MFMAs 3, 7, .. 31: in the steady state it carries the kernel's LDS-DMA rows and one eighth
+// of the PREVIOUS tile's softmax, pinned there with sched_barrier, so the VALU work issues beside the MFMAs.
+// The using kernel declares  uint32_t ka[8]; v8 kfr[A5_KD]; v8 qf[32]  and defines the two things that differ:
+//   A5_KADDR(KBUF, c)  the LDS address of K fragment c = 0..7 (row l31, chunk 2c + lh) of tile buffer KBUF; k-step ks reads
+//                      fragment ks & 7 at offset 256 (ks >> 3)
+//   A5_KREFILL         a constant: false = only the first A5_KD reads are issued (attn_d512b's diagnostic build A5B_ABL & 8)
+// (macros, not lambdas: clang rejects captured arrays as asm operands inside generic lambdas)
+constexpr int A5_KD = 6;
+static_assert(A5_KD == 6, "A5_CHAIN's prologue issues 6 reads");
+#define A5_KREAD(slot, ks) \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kfr[slot]) : "v"(ka[(ks) & 7]), "i"(((ks) >> 3) * 256))
+#define A5_STEP(NAME, SACC, ks)                                                                                         \
+    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, %0"                                                      \
+                 : "+v"(SACC)                                                                                           \
+                 : "v"(kfr[(ks) % A5_KD]), "v"(qf[ks]), "i"(A5_KD - 1 < 31 - (ks) ? A5_KD - 1 : 31 - (ks)));              \
+    if constexpr ((ks) + A5_KD < 32 && A5_KREFILL) A5_KREAD((ks) % A5_KD, (ks) + A5_KD)
+#define A5_STEP4(NAME, SACC, k) \
+    A5_STEP(NAME, SACC, k); A5_STEP(NAME, SACC, (k) + 1); A5_STEP(NAME, SACC, (k) + 2); A5_STEP(NAME, SACC, (k) + 3)
+#define A5_CHAIN(NAME, SACC, KBUF, HOOK)                                                                                \
+    _Pragma("unroll") for (int c = 0; c < 8; ++c) ka[c] = A5_KADDR(KBUF, c);                                            \
+    A5_KREAD(0, 0); A5_KREAD(1, 1); A5_KREAD(2, 2); A5_KREAD(3, 3); A5_KREAD(4, 4); A5_KREAD(5, 5);                     \
+    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, 0" : "=&v"(SACC) : "v"(kfr[0]), "v"(qf[0]), "i"(A5_KD - 1)); \
+    A5_KREAD(0, A5_KD);                                                                                                 \
+    A5_STEP(NAME, SACC, 1); A5_STEP(NAME, SACC, 2); A5_STEP(NAME, SACC, 3); HOOK(0);                                    \
+    A5_STEP4(NAME, SACC, 4); HOOK(1); A5_STEP4(NAME, SACC, 8); HOOK(2); A5_STEP4(NAME, SACC, 12); HOOK(3);              \
+    A5_STEP4(NAME, SACC, 16); HOOK(4); A5_STEP4(NAME, SACC, 20); HOOK(5); A5_STEP4(NAME, SACC, 24); HOOK(6);            \
+    A5_STEP4(NAME, SACC, 28); HOOK(7)
+#define A5_NOHOOK(i)
+
+// Q fragments of the lane's query row qrow (B operand of S^T: col = query row on the lane, k = d) into v8 QF[32]; rows past Nq are
+// zero.  Uses the kernel's Qb, qrow, p, lh.  (A macro: as a function over the array and p's fields it renames registers throughout
+// both kernels, -47 instruction lines.)
+#define A5_LOAD_Q(QF)                                                                                         \
+    _Pragma("unroll") for (int ks = 0; ks < 32; ++ks) {                                                       \
+        u32x4 v = {0u, 0u, 0u, 0u};                                                                           \
+        if (qrow < p.Nq) v = *(const u32x4*)(Qb + (int64_t)qrow * p.q_ts + ks * 16 + lh * 8);                 \
+        QF[ks] = __builtin_bit_cast(v8, v);                                                                   \
+    }
+// NDT 32-wide d-tiles of one query row, normalised, to DST (E = T: the 16-bit output, float: the split-KV partials).  TILE names the
+// accumulator of tile dt, whose registers 4g + e hold d = 32 dt + 8g + 4lh + e; uses the kernel's lh.  (A macro: as a function over an
+// accessor lambda attn_d512b kept its instruction stream, attn_d512d's multiplies were reordered.)
+#define A5_STORE_ROW(E, DST, NDT, TILE, INV)                                              \
+    {                                                                                     \
+        typedef E e4_ __attribute__((ext_vector_type(4)));                                \
+        E* const dst_ = (DST);                                                            \
+        _Pragma("unroll") for (int dt = 0; dt < (NDT); ++dt)                              \
+        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                   \
+            e4_ o;                                                                        \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) o[e] = (E)(TILE[4 * g + e] * (INV)); \
+            *(e4_*)(dst_ + dt * 32 + 8 * g + 4 * lh) = o;                                 \
+        }                                                                                 \
+    }
 
 template <typename T, bool SH>
 __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_per_split, float* part_o, float* part_ml) {
     constexpr int D = 512;
     typedef typename Mfma<T>::v8 v8;
-    typedef typename Mfma<T>::v4 v4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -118,14 +162,14 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
     // (1) an LDS-DMA costs the issuing wave ~60-180 cycles, so the 16 of a tile are spread between the MFMAs of the
     // S chain instead of standing in front of it; (2) hipcc puts s_waitcnt vmcnt(0) in front of the first LDS read that
     // follows an LDS-DMA it knows of, which would drain the prefetch at the start of every PV phase.  M0 (the LDS
-    // destination) is compiler-reserved: declared clobbered, see the note on M0 above.
+    // destination) is compiler-reserved: declared clobbered, see the note on M0 in rsvld_common.h.
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
     bool abl_dma_on = true;   // ablation 4: the prologue fills BOTH buffers of K and V, the loop issues no DMA (operands stay
                               // real data: zero-filled operands would raise the clock and overstate the saving)
     auto dma_one = [&](const char* base, uint32_t voff, uint32_t dst) {
         if ((A5B_ABL & 4) && !abl_dma_on) return;
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
+        rsvld_lds_dma16_m0(base, voff, dst);
     };
     // Full tiles: ONE scalar base per tensor (row 8w of the tile, advanced by 32 rows per tile with two SALU adds);
     // the row i of the piece and its source-side swizzle sit in a precomputed 32-bit lane offset.  The tail tile (rows
@@ -200,12 +244,7 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
     // ---- Q fragments (B operand: col = query row on the lane, k = d)
     const int qrow = q0 + l31;
     v8 qf[32];
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) {
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (qrow < p.Nq) v = *(const u32x4*)(Qb + (int64_t)qrow * p.q_ts + ks * 16 + lh * 8);
-        qf[ks] = __builtin_bit_cast(v8, v);
-    }
+    A5_LOAD_Q(qf)
     f32x16 oacc[16];
 #pragma unroll
     for (int dt = 0; dt < 16; ++dt)
@@ -231,46 +270,17 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // tiles 0 (K, V) and 1 (K) landed
 
-    // ---- S^T[key][q] over the whole head dimension: one accumulation chain of 32 MFMAs per tile.
-    // The chain is issued in its VGPR form by inline asm: all 256 accumulator registers belong to O, and hipcc
-    // otherwise parks the score tile in a0..a15 and shuttles one O tile through VGPRs every iteration.  Back-to-back
-    // MFMAs that take the previous D whole as C need no wait states.  The K fragment reads are asm as well: hipcc
-    // waits lgkmcnt(0) in front of an asm consumer, which stalls the chain on the read it has just issued; here KD
-    // reads are in flight and MFMA ks waits only for its own (lgkmcnt(min(KD-1, 31-ks)); LDS returns in order, and any
-    // SMEM operation the compiler may have in flight only makes the count more conservative).
-    // HOOK(i), i = 0..7, runs after MFMAs 3, 7, .. 31: in the steady state it carries two LDS-DMA rows and one eighth
-    // of the PREVIOUS tile's softmax, pinned there with sched_barrier, so the VALU work issues beside the MFMAs.
-    constexpr int KD = 6;
-    static_assert(KD == 6, "A5B_CHAIN's prologue issues 6 reads");
+    // ---- S^T[key][q] over the whole head dimension: A5_CHAIN, K fragment c of a k-step group at kbase[c]
     uint32_t ka[8];
-    v8 kfr[KD];
-    // (macros, not lambdas: clang rejects captured arrays as asm operands inside generic lambdas)
-#define A5B_KREAD(slot, ks) \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kfr[slot]) : "v"(ka[(ks) & 7]), "i"(((ks) >> 3) * 256))
-#define A5B_STEP(NAME, SACC, ks)                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, %0"                                                      \
-                 : "+v"(SACC)                                                                                           \
-                 : "v"(kfr[(ks) % KD]), "v"(qf[ks]), "i"(KD - 1 < 31 - (ks) ? KD - 1 : 31 - (ks)));                      \
-    if constexpr ((ks) + KD < 32 && !(A5B_ABL & 8)) A5B_KREAD((ks) % KD, (ks) + KD)
-#define A5B_STEP4(NAME, SACC, k) \
-    A5B_STEP(NAME, SACC, k); A5B_STEP(NAME, SACC, (k) + 1); A5B_STEP(NAME, SACC, (k) + 2); A5B_STEP(NAME, SACC, (k) + 3)
-#define A5B_CHAIN(NAME, SACC, KBUF, HOOK)                                                                               \
-    _Pragma("unroll") for (int c = 0; c < 8; ++c) ka[c] = lds0 + (uint32_t)((KBUF) * A5B_TILE + kbase[c]);              \
-    A5B_KREAD(0, 0); A5B_KREAD(1, 1); A5B_KREAD(2, 2); A5B_KREAD(3, 3); A5B_KREAD(4, 4); A5B_KREAD(5, 5);               \
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, 0" : "=&v"(SACC) : "v"(kfr[0]), "v"(qf[0]), "i"(KD - 1)); \
-    A5B_KREAD(0, KD);                                                                                                   \
-    A5B_STEP(NAME, SACC, 1); A5B_STEP(NAME, SACC, 2); A5B_STEP(NAME, SACC, 3); HOOK(0);                                 \
-    A5B_STEP4(NAME, SACC, 4); HOOK(1); A5B_STEP4(NAME, SACC, 8); HOOK(2); A5B_STEP4(NAME, SACC, 12); HOOK(3);           \
-    A5B_STEP4(NAME, SACC, 16); HOOK(4); A5B_STEP4(NAME, SACC, 20); HOOK(5); A5B_STEP4(NAME, SACC, 24); HOOK(6);         \
-    A5B_STEP4(NAME, SACC, 28); HOOK(7)
-#define A5B_MFMA_NAME(T_) (__is_same(T_, f16) ? "f16" : "bf16")
-#define A5B_NOHOOK(i)
+    v8 kfr[A5_KD];
+#define A5_KADDR(KBUF, c) (lds0 + (uint32_t)((KBUF) * A5B_TILE + kbase[c]))
+#define A5_KREFILL (!(A5B_ABL & 8))   // ablation 8: no K reads beyond the chain's first six
 
     f32x16 sacc;   // scores of the tile whose softmax is due (S runs one tile ahead of PV)
     if constexpr (__is_same(T, f16)) {
-        A5B_CHAIN("v_mfma_f32_32x32x16_f16", sacc, 0, A5B_NOHOOK);
+        A5_CHAIN("v_mfma_f32_32x32x16_f16", sacc, 0, A5_NOHOOK);
     } else {
-        A5B_CHAIN("v_mfma_f32_32x32x16_bf16", sacc, 0, A5B_NOHOOK);
+        A5_CHAIN("v_mfma_f32_32x32x16_bf16", sacc, 0, A5_NOHOOK);
     }
     asm volatile("s_nop 15\n\ts_nop 3" : "+v"(sacc));   // MFMA D -> VALU reader (cdna_hip_programming.md §5.7 item 2)
     __syncthreads();   // every wave has read K(0): iteration 0 overwrites that buffer with K(2)
@@ -280,8 +290,8 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
     // The body exists three times (attention_d512_body.inc): two steady-state copies per loop trip for tiles whose successors
     // t + 1, t + 2 exist and are full, and the general copy for the last tiles.
     f32x16 sacc2;
-#define A5B_STEADY 1
-#define A5B_PAIR 1
+#define A5_STEADY 1
+#define A5_PAIR 1
 #define dma_kb_s dma_kb_fast
 #define dma_k_s dma_k_fast
 #define dma_v_s dma_v_fast
@@ -306,13 +316,13 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
 #undef dma_kb_s
 #undef dma_k_s
 #undef dma_v_s
-#undef A5B_PAIR
-#undef A5B_STEADY
+#undef A5_PAIR
+#undef A5_STEADY
     for (; t < nt; ++t) {
-#define A5B_PAIR 0
+#define A5_PAIR 0
 #define S_CUR sacc
 #define S_NXT snext
-#define A5B_STEADY 0
+#define A5_STEADY 0
 #define dma_kb_s dma_kb
 #define dma_k_s dma_k
 #define dma_v_s dma_v
@@ -320,44 +330,22 @@ __global__ __launch_bounds__(256) void attn_d512b_kernel(AttnArgs p, int keys_pe
 #undef dma_kb_s
 #undef dma_k_s
 #undef dma_v_s
-#undef A5B_STEADY
+#undef A5_STEADY
 #undef S_CUR
 #undef S_NXT
-#undef A5B_PAIR
+#undef A5_PAIR
     }
-#undef A5B_NOHOOK
-#undef A5B_MFMA_NAME
-#undef A5B_CHAIN
-#undef A5B_STEP4
-#undef A5B_STEP
-#undef A5B_KREAD
+#undef A5_KREFILL
+#undef A5_KADDR
 
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     if (qrow >= p.Nq) return;
     const float inv = 1.0f / l_tot;
     if (nsplit == 1) {
-        T* Ob = (T*)p.out + (int64_t)b * p.o_bs + (int64_t)h * D + (int64_t)qrow * p.o_ts;
-#pragma unroll
-        for (int dt = 0; dt < 16; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                v4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (T)(oacc[dt][4 * g + e] * inv);
-                *(v4*)(Ob + dt * 32 + 8 * g + 4 * lh) = o;
-            }
+        A5_STORE_ROW(T, (T*)p.out + (int64_t)b * p.o_bs + (int64_t)h * D + (int64_t)qrow * p.o_ts, 16, oacc[dt], inv)
     } else {
         const int64_t row = ((int64_t)split * gridDim.z + blockIdx.z) * p.Nq + qrow;
-        float* Po = part_o + row * D;
-#pragma unroll
-        for (int dt = 0; dt < 16; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = oacc[dt][4 * g + e] * inv;
-                *(f32x4*)(Po + dt * 32 + 8 * g + 4 * lh) = o;
-            }
+        A5_STORE_ROW(float, part_o + row * D, 16, oacc[dt], inv)
         if (lh == 0) {
             part_ml[row * 2] = m_run;
             part_ml[row * 2 + 1] = l_tot;
@@ -392,6 +380,14 @@ __global__ __launch_bounds__(128) void attn_combine_kernel(AttnArgs p, int nspli
 }
 
 #include "attention_d512d.inc"
+
+#undef A5_STORE_ROW
+#undef A5_LOAD_Q
+#undef A5_NOHOOK
+#undef A5_CHAIN
+#undef A5_STEP4
+#undef A5_STEP
+#undef A5_KREAD
 
 }  // namespace
 
@@ -507,16 +503,10 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_d64b_kernel(AttnArgs p) {
         kvo[i] = (uint32_t)(rr * k_rowb) + (uint32_t)(((lane & 7) ^ ((r16 >> 1) & 7)) << 4);
         vvo[i] = (uint32_t)(rr * v_rowb) + (uint32_t)(((lane & 7) ^ (((r16 >> 1) & 1) << 2)) << 4);
     }
-    auto dma_fast = [&](const char* base, uint32_t voff, uint32_t dst) {
-        uint32_t keep;   // M0 saved and restored (declared clobbered instead: 12 % slower here, see the note on M0 above)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-    };
-    auto dma_slow = [&](const char* ptr, uint32_t dst) {   // per-lane 64-bit address (tail tile: clamped rows)
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(ptr), "s"(dst) : "memory");
-    };
+    // M0 saved and restored (declared clobbered instead: 12 % slower here, see the note on M0 in rsvld_common.h).  (Lambdas: with the
+    // helpers called directly from dma_tile hipcc schedules this kernel differently.)
+    auto dma_fast = [&](const char* base, uint32_t voff, uint32_t dst) { rsvld_lds_dma16(base, voff, dst); };
+    auto dma_slow = [&](const char* ptr, uint32_t dst) { rsvld_lds_dma16_addr(ptr, dst); };   // tail tile: clamped rows
     // Full tiles are requested in order t = 0, 1, 2, ...: the two scalar row pointers advance by 64 rows per request (two
     // 64-bit adds) instead of being recomputed from t with 64-bit multiplies (~20 SALU per request and wave, on a CU whose 16
     // waves share one scalar unit: the request phase was 15 % of a wave's iteration in the stamped build).
@@ -674,10 +664,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_d64b_kernel(AttnArgs p) {
                 for (int s4 = 0; s4 < 4; ++s4) {
                     if (A6B_ABL & 16) { vf[dt][s4] = abl_frag; continue; }
                     const int off = vb + voff[dt] + s4 * 2048;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off + 1024));
-                    typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-                    vf[dt][s4] = __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    vf[dt][s4] = tr16_pair<v8>(lds_read_tr16(smem + off), lds_read_tr16(smem + off + 1024));
                 }
         };
         A6B_MARK(1);

@@ -1,16 +1,15 @@
-// Included by attention.hip THREE times inside attn_d512b_kernel: the body of the key-tile loop.  A5B_STEADY = 1: tiles t + 1 and
-// t + 2 exist and are full (branch-free around the chain and the requests); A5B_PAIR = 1: the steady-state loop runs two bodies per
+// Included by attention.hip THREE times inside attn_d512b_kernel: the body of the key-tile loop.  A5_STEADY = 1: tiles t + 1 and
+// t + 2 exist and are full (branch-free around the chain and the requests); A5_PAIR = 1: the steady-state loop runs two bodies per
 // trip with the two score register sets S_CUR / S_NXT swapped, so that no S_CUR <- S_NXT copy exists (16 moves per tile -- which
 // hipcc, knowing no latency for the result of an asm MFMA, placed three instructions behind the chain's last MFMA in a branch-free
-// body: stale scores, errors of 1e-3 .. 1e-1 in the shared-tile tests).  A5B_STEADY = A5B_PAIR = 0: the general body (last tiles).
-        // A5B_STEADY (set by the including file): t + 3 < nt, i.e. tiles t + 1 and t + 2 exist and are FULL -- no branch around the S
+// body: stale scores, errors of 1e-3 .. 1e-1 in the shared-tile tests).  A5_STEADY = A5_PAIR = 0: the general body (last tiles).
+        // A5_STEADY (set by the including file): t + 3 < nt, i.e. tiles t + 1 and t + 2 exist and are FULL -- no branch around the S
         // chain, the LDS-DMA requests or the ragged-tile mask (one wave per SIMD: nobody covers a branch's instruction-fetch bubble)
-        const bool more = A5B_STEADY ? true : t + 1 < nt, more2 = A5B_STEADY ? true : t + 2 < nt;
+        const bool more = A5_STEADY ? true : t + 1 < nt, more2 = A5_STEADY ? true : t + 2 < nt;
         const int b_s = b_pv == 2 ? 0 : b_pv + 1, b_dma = b_pv == 0 ? 2 : b_pv - 1;   // (t + 1) % 3, (t + 2) % 3
         const int vb = (SH ? b_pv : (t & 1)) * A5B_TILE;
 
-        // ---- online softmax of tile t, register-local (this lane holds 16 of its query's 32 scores, lane^32 the
-        // rest), cut into 8 parts for the hooks of the S(t+1) chain
+        // ---- online softmax of tile t (attention_d512_softmax.inc) in the hooks of the S(t+1) chain
         float mx = -INFINITY, alpha = 1.0f, rs = 0.f;
         bool need = false;
         v8 pf[2];
@@ -25,49 +24,10 @@
                 }
                 return;
             }
-            if (part == 0) {
-                if (!A5B_STEADY && k_begin + (t + 1) * 32 > k_end) {   // ragged last tile (uniform branch)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int kv = k_begin + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (kv >= k_end) S_CUR[r] = -INFINITY;
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S_CUR[r]);   // on the raw scores: scale > 0 commutes with max
-                asm volatile("" : "+v"(S_CUR), "+v"(mx));
-            } else if (part == 1) {
-                mx = a5b_halfwave_max(mx) * p.scale_log2e;
-                // deferred max (T13): the reference point moves only when the tile max exceeds it by more than 2^8, so
-                // the rescale of O (256 accumulator registers through VGPRs) is skipped on almost every tile
-                need = mx > m_run + A5_DEFER_LOG2;   // true on the first tile (m_run = -inf)
-                if (need) {
-                    alpha = __builtin_amdgcn_exp2f(m_run - mx);
-                    m_run = mx;
-                }
-                asm volatile("" : "+v"(alpha), "+v"(m_run));
-            } else if (part >= 2 && part <= 5) {
-                const int r0 = 4 * (part - 2);
-#pragma unroll
-                for (int r = r0; r < r0 + 4; ++r) {
-                    S_CUR[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(S_CUR[r], p.scale_log2e, -m_run));   // one fma: no scale pass
-                    rs += S_CUR[r];
-                }
-                asm volatile("" : "+v"(S_CUR[r0]), "+v"(S_CUR[r0 + 1]), "+v"(S_CUR[r0 + 2]), "+v"(S_CUR[r0 + 3]), "+v"(rs));
-            } else if (part == 6) {
-                l_run = l_run * alpha + rs;
-                // P as the B operand of k-step s: registers 8s..8s+7 <-> keys 16s + 8(j>>2) + 4lh + (j&3)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[s2][j] = (T)S_CUR[8 * s2 + j];
-                asm volatile("" : "+v"(pf[0]), "+v"(pf[1]), "+v"(l_run));
-            }
+#include "attention_d512_softmax.inc"
         };
-        // (each part ends with an empty volatile asm naming what it produced: volatile asms keep their order, so the part
-        // is computed at its hook; without the pins hipcc sinks the whole softmax behind the chain)
 
-#if !A5B_PAIR
+#if !A5_PAIR
         f32x16 snext;
 #endif
         if (more) {
@@ -81,9 +41,9 @@
     sm(i);                                                            \
     __builtin_amdgcn_sched_barrier(0)
             if constexpr (__is_same(T, f16)) {
-                A5B_CHAIN("v_mfma_f32_32x32x16_f16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
+                A5_CHAIN("v_mfma_f32_32x32x16_f16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
             } else {
-                A5B_CHAIN("v_mfma_f32_32x32x16_bf16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
+                A5_CHAIN("v_mfma_f32_32x32x16_bf16", S_NXT, (SH ? b_s : ((t + 1) & 1)), A5B_HOOK);
             }
 #undef A5B_HOOK
         } else {
@@ -96,32 +56,19 @@
         auto vread = [&](int n) {
             const int dt = n >> 1, s2 = n & 1;
             const int off = vb + vbase[dt & 3] + (dt >> 2) * 256 + (16 * s2) * 1024;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
             // rows +8 (hf = 1): in the shared image the low swizzle bits are (lh + 2 hf) & 3, i.e. chunk bit 1 flips
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + ((SH ? (off ^ 32) : off) + 8 * 1024)));
-            typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-            return __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+            return tr16_pair<v8>(lds_read_tr16(smem + off), lds_read_tr16(smem + ((SH ? (off ^ 32) : off) + 8 * 1024)));
         };
         v8 vfr[VD];
 #pragma unroll
         for (int i = 0; i < VD; ++i) vfr[i] = vread(i);
 
         if (__builtin_expect(__any(need), 0)) {   // (cold: the rescale block is laid out behind the loop)
-            // O lives in the accumulator file; written as plain C++ (oacc *= alpha) hipcc pulls all 256 values into
-            // VGPRs at once and spills 375 registers.  One element at a time through a scratch VGPR instead; the
-            // write -> MFMA hazard (cdna_hip_programming.md §5.7 item 2) is covered by the s_nop that ends each string,
-            // the MFMA -> read hazard by the 32 S-chain MFMAs (or the epilogue of the previous PV) before this point.
+            // O lives in the accumulator file: acc_scale (written as plain C++ hipcc spills 375 registers here).  The MFMA -> read
+            // hazard is covered by the 32 S-chain MFMAs (or the epilogue of the previous PV) before this point.
             asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
 #pragma unroll
-            for (int dt = 0; dt < 16; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float x = oacc[dt][r], tmp;
-                    asm volatile("v_accvgpr_read_b32 %1, %0\n\tv_mul_f32 %1, %1, %2\n\ts_nop 0\n\tv_accvgpr_write_b32 %0, %1\n\ts_nop 1"
-                                 : "+a"(x), "=&v"(tmp)
-                                 : "v"(alpha));
-                    oacc[dt][r] = x;
-                }
+            for (int dt = 0; dt < 16; ++dt) acc_scale(oacc[dt], alpha);
         }
 
         // ---- O^T[d][q] += V^T P^T; the A operand (row = d, k = the same key order) is two transposed reads:
@@ -133,7 +80,7 @@
             if (n + VD < 32 && !(A5B_ABL & 2)) vfr[n % VD] = vread(n + VD);
             __builtin_amdgcn_sched_barrier(0);
         }
-#if !A5B_PAIR
+#if !A5_PAIR
         if (more) S_CUR = S_NXT;   // readable by VALU: 32 PV MFMAs have issued since the chain's last MFMA
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of the next tiles have landed

@@ -1,5 +1,6 @@
 // Included once by attention.hip (after attn_d512b_kernel): attn_d512d_kernel, the shared-tile (K = V = X) d = 512 kernel with
-// O split over the HEAD DIMENSION for the PV product.
+// O split over the HEAD DIMENSION for the PV product.  Its loop body is attention_d512d_body.inc; the S chain (A5_CHAIN), the Q load
+// and the store loops are attention.hip's A5_ macros and the softmax is attention_d512_softmax.inc, the text attn_d512b compiles.
 //
 // attn_d512b<T, true> lets each of its four waves own 32 query rows over all 512 head dims, so every wave reads the whole 32 KiB
 // key tile twice per tile: row-wise for S^T = K Q^T and transposed for O^T += V^T P^T.  Here the S chain and the online softmax
@@ -32,7 +33,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_per_split, float* part_o, float* part_ml) {
     constexpr int D = 512;
     typedef typename Mfma<T>::v8 v8;
-    typedef typename Mfma<T>::v4 v4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -50,9 +50,6 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
     // wave-instruction, M0 declared clobbered (tools/audit_m0.py checks that the compiler never touches M0 in this unit)
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
-    auto dma_one = [&](const char* base, uint32_t voff, uint32_t dst) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
-    };
     // (the lane offsets are formed per request -- one v_xor -- and the row step is scalar: eight offset registers of attn_d512b
     // are what this kernel's phase B needs for its P^T fragments)
     const int64_t x_rowb = p.k_ts * (int64_t)sizeof(T);
@@ -62,15 +59,15 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
         const int r = wu * 8 + i;
         const uint32_t dst = lds0 + (t & 3) * A5B_TILE + r * 1024;
         if (k_begin + t * 32 + 32 <= p.Nk) {
-            dma_one(x_tile0 + (int64_t)(t * 32 + i) * x_rowb, lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), dst);
+            rsvld_lds_dma16_m0(x_tile0 + (int64_t)(t * 32 + i) * x_rowb, lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), dst);
         } else {
             const int key = min(k_begin + t * 32 + r, p.Nk - 1);
-            dma_one((const char*)(Xb + (int64_t)key * p.k_ts), lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), dst);
+            rsvld_lds_dma16_m0((const char*)(Xb + (int64_t)key * p.k_ts), lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), dst);
         }
     };
     auto dma_x_fast = [&](int t, int i) {
         const int r = wu * 8 + i;
-        dma_one(x_tile0 + (int64_t)(t * 32 + i) * x_rowb, lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), lds0 + (t & 3) * A5B_TILE + r * 1024);
+        rsvld_lds_dma16_m0(x_tile0 + (int64_t)(t * 32 + i) * x_rowb, lane16 ^ (uint32_t)(a5b_f(r & 15) << 4), lds0 + (t & 3) * A5B_TILE + r * 1024);
     };
 #pragma unroll
     for (int i = 0; i < 8; ++i) dma_x(0, i);
@@ -86,12 +83,7 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
     // ---- Q fragments (B operand of S^T: col = query row on the lane, k = d)
     const int qrow = q0 + l31;
     v8 qf[32];
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) {
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (qrow < p.Nq) v = *(const u32x4*)(Qb + (int64_t)qrow * p.q_ts + ks * 16 + lh * 8);
-        qf[ks] = __builtin_bit_cast(v8, v);
-    }
+    A5_LOAD_Q(qf)
     // O^T: oacc[dt][j] = d-block 4w + dt (rows d = 128w + 32dt + ..) x q-block (w + j) & 3 (j = 0: this wave's own rows).
     // The q-block is rotated by w so that every register index is a compile-time constant.
     f32x16 oacc[4][4];
@@ -114,10 +106,7 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
     }
     auto vread = [&](int buf, int f, int s2) {
         const int off = buf * A5B_TILE + vbase[f] + (16 * s2) * 1024;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + ((off ^ 32) + 8 * 1024)));
-        typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-        return __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        return tr16_pair<v8>(lds_read_tr16(smem + off), lds_read_tr16(smem + ((off ^ 32) + 8 * 1024)));
     };
     // P / alpha exchange addresses: this wave's slot, and q-block (w + j) & 3's
     const int p_own = A5D_P_OFF + wu * 2048 + lane * 16, a_own = A5D_A_OFF + l31 * 16 + wu * 4;
@@ -131,35 +120,17 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // tiles 0, 1, 2 landed
 
-    // ---- S^T chain: the same asm as attn_d512b (KD = 6 K-fragment reads in flight, MFMA ks waits for its own)
-    constexpr int KD = 6;
+    // ---- S^T chain: attn_d512b's (A5_CHAIN), K fragment c of a k-step group at kb ^ (c << 5)
     uint32_t ka[8];
-    v8 kfr[KD];
-#define A5D_KREAD(slot, ks) \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kfr[slot]) : "v"(ka[(ks) & 7]), "i"(((ks) >> 3) * 256))
-#define A5D_STEP(NAME, SACC, ks)                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, %0"                                                      \
-                 : "+v"(SACC)                                                                                           \
-                 : "v"(kfr[(ks) % KD]), "v"(qf[ks]), "i"(KD - 1 < 31 - (ks) ? KD - 1 : 31 - (ks)));                      \
-    if constexpr ((ks) + KD < 32) A5D_KREAD((ks) % KD, (ks) + KD)
-#define A5D_STEP4(NAME, SACC, k) \
-    A5D_STEP(NAME, SACC, k); A5D_STEP(NAME, SACC, (k) + 1); A5D_STEP(NAME, SACC, (k) + 2); A5D_STEP(NAME, SACC, (k) + 3)
-#define A5D_CHAIN(NAME, SACC, KBUF, HOOK)                                                                               \
-    _Pragma("unroll") for (int c = 0; c < 8; ++c) ka[c] = lds0 + (((KBUF) * A5B_TILE + kb) ^ (c << 5));         \
-    A5D_KREAD(0, 0); A5D_KREAD(1, 1); A5D_KREAD(2, 2); A5D_KREAD(3, 3); A5D_KREAD(4, 4); A5D_KREAD(5, 5);               \
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\t" NAME " %0, %1, %2, 0" : "=&v"(SACC) : "v"(kfr[0]), "v"(qf[0]), "i"(KD - 1)); \
-    A5D_KREAD(0, KD);                                                                                                   \
-    A5D_STEP(NAME, SACC, 1); A5D_STEP(NAME, SACC, 2); A5D_STEP(NAME, SACC, 3); HOOK(0);                                 \
-    A5D_STEP4(NAME, SACC, 4); HOOK(1); A5D_STEP4(NAME, SACC, 8); HOOK(2); A5D_STEP4(NAME, SACC, 12); HOOK(3);           \
-    A5D_STEP4(NAME, SACC, 16); HOOK(4); A5D_STEP4(NAME, SACC, 20); HOOK(5); A5D_STEP4(NAME, SACC, 24); HOOK(6);         \
-    A5D_STEP4(NAME, SACC, 28); HOOK(7)
-#define A5D_NOHOOK(i)
+    v8 kfr[A5_KD];
+#define A5_KADDR(KBUF, c) (lds0 + (((KBUF) * A5B_TILE + kb) ^ (c << 5)))
+#define A5_KREFILL true
 
     f32x16 sacc;   // scores of the tile whose softmax is due (S runs one tile ahead of PV)
     if constexpr (__is_same(T, f16)) {
-        A5D_CHAIN("v_mfma_f32_32x32x16_f16", sacc, 0, A5D_NOHOOK);
+        A5_CHAIN("v_mfma_f32_32x32x16_f16", sacc, 0, A5_NOHOOK);
     } else {
-        A5D_CHAIN("v_mfma_f32_32x32x16_bf16", sacc, 0, A5D_NOHOOK);
+        A5_CHAIN("v_mfma_f32_32x32x16_bf16", sacc, 0, A5_NOHOOK);
     }
     asm volatile("s_nop 15\n\ts_nop 3" : "+v"(sacc));   // MFMA D -> VALU reader (cdna_hip_programming.md §5.7 item 2)
 
@@ -167,8 +138,8 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
     f32x16 sacc2;
     // steady state, two tiles per trip with the score registers swapping roles (see attention_d512_body.inc): tiles t .. t + 4
     // are full (t + 5 < nt), so neither body tests a bound
-#define A5D_STEADY 1
-#define A5D_PAIR 1
+#define A5_STEADY 1
+#define A5_PAIR 1
     for (; t + 5 < nt;) {
         {
 #define S_CUR sacc
@@ -187,24 +158,21 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
         }
         ++t;
     }
-#undef A5D_PAIR
-#undef A5D_STEADY
+#undef A5_PAIR
+#undef A5_STEADY
     for (; t < nt; ++t) {
-#define A5D_PAIR 0
-#define A5D_STEADY 0
+#define A5_PAIR 0
+#define A5_STEADY 0
 #define S_CUR sacc
 #define S_NXT snext
 #include "attention_d512d_body.inc"
 #undef S_NXT
 #undef S_CUR
-#undef A5D_STEADY
-#undef A5D_PAIR
+#undef A5_STEADY
+#undef A5_PAIR
     }
-#undef A5D_NOHOOK
-#undef A5D_CHAIN
-#undef A5D_STEP4
-#undef A5D_STEP
-#undef A5D_KREAD
+#undef A5_KREFILL
+#undef A5_KADDR
 
     // ---- row sums of every q-block through LDS (a dedicated area: other waves may still read the X ring and P buffers)
     const float l_tot = l_run + __shfl_xor(l_run, 32);
@@ -219,28 +187,10 @@ __global__ __launch_bounds__(256) void attn_d512d_kernel(AttnArgs p, int keys_pe
         const int qr = blockIdx.x * 128 + ((wu + j) & 3) * 32 + l31;
         if (qr >= p.Nq) continue;
         if (nsplit == 1) {
-            T* Ob = (T*)p.out + (int64_t)b * p.o_bs + (int64_t)h * D + (int64_t)qr * p.o_ts + wu * 128;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    v4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (T)(oacc[dt][j][4 * g + e] * inv[j]);
-                    *(v4*)(Ob + dt * 32 + 8 * g + 4 * lh) = o;
-                }
+            A5_STORE_ROW(T, (T*)p.out + (int64_t)b * p.o_bs + (int64_t)h * D + (int64_t)qr * p.o_ts + wu * 128, 4, oacc[dt][j], inv[j])
         } else {
             const int64_t row = ((int64_t)split * gridDim.z + blockIdx.z) * p.Nq + qr;
-            float* Po = part_o + row * D + wu * 128;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = oacc[dt][j][4 * g + e] * inv[j];
-                    *(f32x4*)(Po + dt * 32 + 8 * g + 4 * lh) = o;
-                }
+            A5_STORE_ROW(float, part_o + row * D + wu * 128, 4, oacc[dt][j], inv[j])
             if (j == 0 && lh == 0) {   // the row's own wave holds its running max
                 part_ml[row * 2] = m_run;
                 part_ml[row * 2 + 1] = l_tot;

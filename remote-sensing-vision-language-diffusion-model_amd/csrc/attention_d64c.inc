@@ -1,4 +1,4 @@
-// Included by attention.hip inside its anonymous namespace (uses AttnArgs, Mfma<T>, A6B_TILE, a6b_add, s16x4).
+// Included by attention.hip inside its anonymous namespace (uses AttnArgs, Mfma<T>, A6B_TILE, a6b_add).
 // ---------------------------------------------------------------------------------------
 // D = 64, the "ping-pong" form.  attn_d64b runs four waves per SIMD whose phases are left to chance: the
 // matrix pipe is busy 61 % of the time (PMC) although the kernel's vector issue (exp 8, add 4, cvt 4 cycles per instruction;
@@ -46,16 +46,14 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     const int l31 = lane & 31, lh = lane >> 5;
     const int wu = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool late = wu >= 4;   // the second wave of its SIMD
-    // XCD-aware work order: workgroups are dealt to the 8 XCDs round-robin by their linear id, so with the plain
-    // (query block, head, batch) grid the 256 concurrent workgroups spread EVERY head over all 8 L2s (at 2 x 20 heads x 16 384
-    // tokens: 8 heads x 4 MB of K / V per 4 MiB L2, four CUs per stream).  Here each XCD walks a contiguous run of (head, query
-    // block) items (the scheme of the conv / GEMM kernels): its 32 CUs work on the same head's K / V stream in step.
+    // XCD-aware work order (rsvld_xcd_item) over (head, query block) items: with the plain (query block, head, batch) grid the 256
+    // concurrent workgroups spread EVERY head over all 8 L2s (at 2 x 20 heads x 16 384 tokens: 8 heads x 4 MB of K / V per 4 MiB L2,
+    // four CUs per stream); here an XCD's 32 CUs work on the same head's K / V stream in step.
     int qblk, h, b;
     {
         const int nqb = gridDim.x, nwg = gridDim.x * gridDim.y * gridDim.z;
         const int lid = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
-        const int q = nwg >> 3, r = nwg & 7, xcd = lid & 7, slot = lid >> 3;
-        const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        const int t = rsvld_xcd_item(lid, nwg);
         qblk = t % nqb;
         const int bh = t / nqb;
         h = bh % gridDim.y;
@@ -73,27 +71,23 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
     const int drow = lane >> 3, r16 = (wu * 8 + drow) & 15;
     const uint32_t kswz = (uint32_t)(((lane & 7) ^ ((r16 >> 1) & 7)) << 4), vswz = (uint32_t)(((lane & 7) ^ (((r16 >> 1) & 1) << 2)) << 4);
     const uint32_t kvo = (uint32_t)(drow * k_rowb) + kswz, vvo = (uint32_t)(drow * v_rowb) + vswz;
-    auto dma_fast = [&](const char* base, uint32_t voff, uint32_t dst) __attribute__((always_inline)) {
-        // M0 declared clobbered instead of saved / restored (the note on M0 in attention.hip; audited by tools/audit_m0.py): +1.1-1.2 %
-        // here (profiles/r03_attn_d64_ab.txt run 16), where attn_d64b lost 12 % with it
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
-    };
+    // LDS-DMA pieces: rsvld_lds_dma16_m0, M0 declared clobbered instead of saved / restored: +1.1-1.2 % here, where attn_d64b lost 12 % with it
     const char* k_next = (const char*)(Kb + (int64_t)(wu * 8) * p.k_ts);   // requests come in tile order: two pointer adds each
     const char* v_next = (const char*)(Vb + (int64_t)(wu * 8) * p.v_ts);
     const int64_t k_step = 64 * k_rowb, v_step = 64 * v_rowb;
     auto dma_tile = [&](int t, bool known_full = false) __attribute__((always_inline)) {   // always exactly two pieces (the counted vmcnt below relies on it)
         const uint32_t kd = lds0 + (t & (NB - 1)) * A6B_TILE + wu * 1024, vd = kd + NB * A6B_TILE;
         if (known_full || t * 64 + 64 <= p.Nk) {
-            dma_fast(k_next, kvo, kd);
-            dma_fast(v_next, vvo, vd);
+            rsvld_lds_dma16_m0(k_next, kvo, kd);
+            rsvld_lds_dma16_m0(v_next, vvo, vd);
             k_next += k_step;
             v_next += v_step;
         } else {
             // ragged last tile: rows past Nk re-read the last key (their scores are masked).  Same instruction form: the scalar
             // base is the tile's FIRST row (the last tile holds at least one key), the clamped row goes into the lane offset
             const int rel = min(wu * 8 + drow, p.Nk - 1 - t * 64);   // >= 0
-            dma_fast((const char*)(Kb + (int64_t)(t * 64) * p.k_ts), (uint32_t)(rel * k_rowb) + kswz, kd);
-            dma_fast((const char*)(Vb + (int64_t)(t * 64) * p.v_ts), (uint32_t)(rel * v_rowb) + vswz, vd);
+            rsvld_lds_dma16_m0((const char*)(Kb + (int64_t)(t * 64) * p.k_ts), (uint32_t)(rel * k_rowb) + kswz, kd);
+            rsvld_lds_dma16_m0((const char*)(Vb + (int64_t)(t * 64) * p.v_ts), (uint32_t)(rel * v_rowb) + vswz, vd);
         }
     };
     dma_tile(0);
@@ -170,10 +164,7 @@ __global__ __launch_bounds__(512, 2) void attn_d64c_kernel(AttnArgs p) {
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
                 const int off = vb + voff[dt] + s4 * 2048;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off + 1024));
-                typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-                vf[dt][s4] = __builtin_bit_cast(v8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                vf[dt][s4] = tr16_pair<v8>(lds_read_tr16(smem + off), lds_read_tr16(smem + off + 1024));
             }
     };
     // the three operand tuples of the bias steps live in 12 registers, zeros written once (rebuilt per tile: 10 v_mov_b32 in the matrix segment)

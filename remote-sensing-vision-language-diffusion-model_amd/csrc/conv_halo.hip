@@ -56,8 +56,6 @@ constexpr int TH = rsvld_plan::HALO_TH, TW = rsvld_plan::HALO_TW, PW = TW + 2, P
 constexpr int PATCH_BYTES = PROWS * 128;
 constexpr int PLOADS = (PROWS * 8 + 255) / 256;                        // 11 16-byte pieces per thread
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ int swz_off(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
 // Patch image: pixel (py, px) of the (TH+2) x PW patch owns the 128-B row py*PW + px; its 16-B channel chunk c sits
@@ -284,13 +282,10 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(HaloArgs p) {
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // XCD-aware tile order (same scheme as conv_igemm): linear id -> contiguous run per XCD, x fastest
+    // XCD-aware tile order (rsvld_xcd_item), x fastest
     int tx, ty, img, tile_n;
     {
-        const int nwg = gridDim.x;
-        const int lid = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = lid & 7, slot = lid >> 3;
-        int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        int t = rsvld_xcd_item(blockIdx.x, gridDim.x);
         tx = t % p.tiles_x; t /= p.tiles_x;
         ty = t % p.tiles_y; t /= p.tiles_y;
         img = t % p.B;
@@ -475,14 +470,6 @@ constexpr int AB32_BYTES = 1024;        // one LDS-DMA wave-instruction: 512 B o
 __device__ __forceinline__ int p32_off(int py, int px, int slot) { return (py * PW + px) * 64 + ((slot ^ ((px >> 2) & 3)) << 4); }
 __device__ __forceinline__ int w32_off(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
 
-// compile-time loop: f(std::integral_constant<int, i>) for i = 0..N-1
-template <typename F, int... I> __device__ __forceinline__ void halo_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void halo_static_for(F&& f) {
-    halo_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 template <int N> __device__ __forceinline__ void halo_wait_barrier() {
     // DMA pieces older than the N youngest vector-memory operations have landed, this wave's LDS writes are done
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
@@ -535,12 +522,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_halo32_kernel(HaloArgs p) {
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    int tx, ty, img, tile_n;
+    int tx, ty, img, tile_n;   // XCD-aware tile order, as in conv_halo_kernel
     {
-        const int nwg = gridDim.x;
-        const int lid = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = lid & 7, slot = lid >> 3;
-        int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        int t = rsvld_xcd_item(blockIdx.x, gridDim.x);
         tx = t % p.tiles_x; t /= p.tiles_x;
         ty = t % p.tiles_y; t /= p.tiles_y;
         img = t % p.B;
@@ -726,7 +710,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_halo32_kernel(HaloArgs p) {
         constexpr int KIND = decltype(kind_c)::value, NEXT = decltype(next_c)::value;
         typedef std::integral_constant<int, NEXT == 2 ? 1 : 0> KN;   // the next body's kind
         const int nidx = (NEXT == 2 && KIND == 0) ? 0 : idx + 1;
-        halo_static_for<9>([&](auto st_c) {
+        static_for<9>([&](auto st_c) {
             constexpr int st = decltype(st_c)::value;   // compile-time: taps, wait counts and piece indices depend on it
             constexpr bool w_issue = (st + AHEAD < 9) || NEXT != 0;   // the slice of step s + AHEAD exists
             if constexpr (w_issue && !(HALO_ABL & 1)) {

@@ -71,8 +71,6 @@ constexpr int BK_BYTES = 128;  // 64 x 16-bit per LDS row
 
 __device__ uint4 g_zero16;  // zero page: source of padded / out-of-range chunks for the LDS-DMA path
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // byte offset of 16-byte chunk `c` (0..7) of LDS row `row` (128-B rows).  Two rows share
 // one 256-B bank row; XOR with (row>>1)&7 makes every ds_read_b128 lane group hit 16
@@ -106,14 +104,12 @@ __global__ __launch_bounds__(256 * KS) void conv_igemm_kernel(ConvArgs p) {
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    // XCD-aware tile order: linear workgroup id -> (XCD label, slot); each XCD walks a contiguous run of
-    // tiles with m fastest (bijective for any grid size, cdna_hip_programming.md §5 "XCD swizzle")
+    // XCD-aware tile order (rsvld_xcd_item), m fastest
     int tile_m, tile_n;
     {
         const int nmt = gridDim.x, nwg = gridDim.x * gridDim.y;
         const int lid = blockIdx.x + blockIdx.y * nmt;
-        const int q = nwg >> 3, r = nwg & 7, xcd = lid & 7, slot = lid >> 3;
-        const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+        const int t = rsvld_xcd_item(lid, nwg);
         tile_n = t / nmt;
         tile_m = t - tile_n * nmt;
     }

@@ -50,8 +50,6 @@ struct GemmArgs {
     int out_kind;          // SEG > 1 only: 0 = 16-bit out (fp16), 1 = fp32 out (+ fp32 residual), 2 = bf16 planes out
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 template <int MASK> using Pieces = std::integral_constant<int, MASK>;   // (mma_tile: which LDS-DMA pieces a multiply slot issues)
 
 constexpr int G_STAGE = 32 * 1024;   // X: 256 rows x 64 B | W: 256 rows x 64 B
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     const int grp = wave >> 2, wn = wave & 3;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // ---- tiles.  XCD-aware order: each XCD (= linear workgroup id mod 8) walks a contiguous run of the tile sequence.  One tile per
+    // ---- tiles.  XCD-aware order (rsvld_xcd_run): each XCD walks a contiguous run of the tile sequence.  One tile per
     // workgroup (grid = the tile grid), or PERSIST: one workgroup per CU, workgroup c of an XCD takes tiles c, c + step, ... of the run.
     const int nmt = (p.M + 255) >> 8, nnt = (p.N + 255) >> 8;
     // PERSIST, the last round of an XCD's run: when it holds rem <= half as many tiles as the XCD has workgroups, each of them is cut
@@ -135,10 +133,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     {
         const int ntiles = nmt * nnt;
         const int lid = PERSIST ? (int)blockIdx.x : (int)(blockIdx.x + blockIdx.y * gridDim.x);
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = lid & 7;
-        const int ts = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+        const int xcd = lid & 7;
+        int ts, tn;
+        rsvld_xcd_run(lid, ntiles, ts, tn);
         t_cur = ts + (lid >> 3);
-        t_end = PERSIST ? ts + q + (xcd < r ? 1 : 0) : t_cur + 1;
+        t_end = PERSIST ? ts + tn : t_cur + 1;
         t_step = PERSIST ? ((int)gridDim.x - xcd + 7) >> 3 : 1;
         if constexpr (PERSIST) {
             const int c = lid >> 3, qx = t_end - ts;
@@ -284,7 +283,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         const int ktx = (G_ABL & 8) ? (kt & 3) : xk(kt);
         const char* base = uni((j & 1) ? Wb + ((G_ABL & 8) ? (kt & 3) : wk(kt)) * 64 : Xb + ktx * 64);
         const uint32_t voff = (j & 1) ? wvo[j >> 1] : xvo[j >> 1];
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
+        rsvld_lds_dma16_m0(base, voff, dst);
     };
     auto dma_tile = [&](auto RB, int kt) {
 #pragma unroll

@@ -31,8 +31,6 @@ struct PrefillArgs {
     float scale_log2e;
 };
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 
 constexpr int PA_TILE = 64 * 256;   // 64 keys x 128 d, 16-bit
@@ -75,16 +73,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
         kvo[i] = (uint32_t)(rr * 256) + (uint32_t)(((lane & 15) ^ rr) << 4);
         vvo[i] = (uint32_t)(rr * 256) + (uint32_t)(((lane & 15) ^ ((rr & 3) << 2)) << 4);
     }
-    auto dma_fast = [&](const char* base, uint32_t voff, uint32_t dst) {
-        uint32_t keep;   // M0 (the LDS destination) saved and restored, as attn_d64b does
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-    };
-    auto dma_slow = [&](const char* ptr, uint32_t dst) {   // per-lane 64-bit address (the call's last tile: clamped rows)
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(ptr), "s"(dst) : "memory");
-    };
+    // LDS-DMA pieces: rsvld_lds_dma16 / _addr, M0 (the LDS destination) saved and restored, as attn_d64b does
     auto dma_tile = [&](int t) {
         const int buf = t & 1;
         const uint32_t kd = lds0 + buf * PA_TILE + wu * 4096, vd = kd + 2 * PA_TILE;
@@ -93,16 +82,16 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
             const char* vb = (const char*)(Vb + (int64_t)(t * 64 + wu * 16) * D);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                dma_fast(kb, kvo[i], kd + i * 1024);
-                dma_fast(vb, vvo[i], vd + i * 1024);
+                rsvld_lds_dma16(kb, kvo[i], kd + i * 1024);
+                rsvld_lds_dma16(vb, vvo[i], vd + i * 1024);
             }
         } else {   // rows above klast re-read key klast (< max_len); their scores are masked and their V rows zeroed
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int rr = 4 * i + (lane >> 4);
                 const int key = min(t * 64 + wu * 16 + rr, klast);
-                dma_slow((const char*)(Kb + (int64_t)key * D) + (((lane & 15) ^ rr) << 4), kd + i * 1024);
-                dma_slow((const char*)(Vb + (int64_t)key * D) + (((lane & 15) ^ ((rr & 3) << 2)) << 4), vd + i * 1024);
+                rsvld_lds_dma16_addr((const char*)(Kb + (int64_t)key * D) + (((lane & 15) ^ rr) << 4), kd + i * 1024);
+                rsvld_lds_dma16_addr((const char*)(Vb + (int64_t)key * D) + (((lane & 15) ^ ((rr & 3) << 2)) << 4), vd + i * 1024);
             }
         }
     };
@@ -212,9 +201,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     const int off = vb + voff[dt] + s4 * 4096;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + off + 2048));
-                    s16x8 vv = (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    s16x8 vv = tr16_pair<s16x8>(lds_read_tr16(smem + off), lds_read_tr16(smem + off + 2048));
                     if (vclean) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j)

@@ -2,7 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 #include "rsvld_hip.h"
+
+typedef const __attribute__((address_space(1))) void* gptr_t;   // LDS-DMA builtin operands: global source,
+typedef __attribute__((address_space(3))) void* lptr_t;         // LDS destination (and the 32-bit LDS address of a __shared__ pointer)
 
 typedef _Float16 f16;
 typedef __bf16 bf16;
@@ -169,6 +174,84 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
+}
+
+// compile-time loop: f(std::integral_constant<int, i>) for i = 0..N-1 (inline-asm "i" operands and register-array indices need constants)
+template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// ---- XCD-aware work order.  Workgroups are dealt to the 8 XCDs round-robin by their linear id, so a plain grid order spreads
+// neighbouring work items (the same weight tile, adjacent image rows, one head's K / V stream) over all 8 private L2s.  Instead XCD
+// x = lid & 7 walks a CONTIGUOUS run of the n items: the first n & 7 XCDs get n / 8 + 1 of them, the rest n / 8 -- a bijection for any
+// n (cdna_hip_programming.md §5 "XCD swizzle").  rsvld_xcd_run: the run of the workgroup's XCD; rsvld_xcd_item: the item of a grid of
+// one workgroup per item (slot lid >> 3 of the run).
+__device__ __forceinline__ void rsvld_xcd_run(int lid, int n, int& start, int& len) {
+    const int q = n >> 3, r = n & 7, xcd = lid & 7;
+    start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    len = q + (xcd < r ? 1 : 0);
+}
+__device__ __forceinline__ int rsvld_xcd_item(int lid, int n) {
+    int start, len;
+    rsvld_xcd_run(lid, n, start, len);
+    return start + (lid >> 3);
+}
+
+// ---- LDS-DMA, 16 bytes per lane (global_load_lds_dwordx4: lane l's 16 bytes land at LDS address dst + 16 l; M0 carries dst), as
+// inline asm: a DMA hipcc knows of (the builtin) gets an s_waitcnt vmcnt(0) in front of the first LDS read that follows it, which
+// drains the prefetch, and a per-lane 64-bit address where a scalar base would do.  The s_nop 0 covers the M0 write -> LDS-DMA hazard.
+// M0 is compiler-reserved.  Two ways to live with that:
+//   * rsvld_lds_dma16_m0 writes M0 and declares it clobbered: 2 scalar instructions fewer per piece, and no restore that waits
+//     behind the DMA's own read of M0.  hipcc only warns; the build is sound because the COMPILER never touches M0 in such a
+//     translation unit (attention.hip, gemm.hip), which tools/audit_m0.py / tests/test_build_audits.py check on the assembly.
+//     Used by attn_d512b / attn_d512d (+2.5 % at 262 144 keys, profiles/r03_attn_d64_ab.txt run 7), attn_d64c (+1.1-1.2 %, run 16)
+//     and gemm256 (profiles/r03_gemm_asmdma_ab.txt).
+//   * rsvld_lds_dma16 / rsvld_lds_dma16_addr save and restore M0 inside the statement.  Used by attn_d64b, which ran 12 % SLOWER
+//     with the clobber form (run 7), by prefill_attn_d128 and by the split attention kernels (split.hip, an unaudited unit).
+// base: wave-uniform (SGPR pair); voff: the lane's 32-bit byte offset; dst: wave-uniform LDS byte address.
+__device__ __forceinline__ void rsvld_lds_dma16_m0(const char* base, uint32_t voff, uint32_t dst) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" : : "v"(voff), "s"(dst), "s"(base) : "memory", "m0");
+}
+__device__ __forceinline__ void rsvld_lds_dma16(const char* base, uint32_t voff, uint32_t dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
+}
+// per-lane 64-bit address (ragged tiles: clamped rows)
+__device__ __forceinline__ void rsvld_lds_dma16_addr(const char* ptr, uint32_t dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(ptr), "s"(dst) : "memory");
+}
+
+// An 8-element MFMA A operand from two hardware-transposed LDS reads (ds_read_b64_tr_b16): tr16_pair<v8>(lds_read_tr16(lo), lds_read_tr16(hi))
+// holds lo's four values in elements 0..3 and hi's in 4..7.  (Two functions: each address is then formed in front of its own read, as
+// in the statement form; with both addresses as arguments of one function attn_d512d's reads are scheduled differently.)
+typedef short tr16x4 __attribute__((__vector_size__(4 * sizeof(short))));
+__device__ __forceinline__ tr16x4 lds_read_tr16(const char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr16x4*)p);
+}
+template <typename V8> __device__ __forceinline__ V8 tr16_pair(tr16x4 lo, tr16x4 hi) {
+    typedef short tr16x8 __attribute__((__vector_size__(8 * sizeof(short))));
+    return __builtin_bit_cast(V8, (tr16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// acc *= a for an accumulator tile that lives in the AccVGPR file (the online softmax's rescale of O).  Written as plain C++ hipcc pulls
+// every tile of O into VGPRs at once and spills; here one element at a time goes through a scratch VGPR.  The write -> MFMA hazard
+// (cdna_hip_programming.md §5.7 item 2) is covered by the s_nop that ends each string; the MFMA -> read hazard is the caller's: an
+// "s_nop 15; s_nop 3" or enough independent MFMAs between the last MFMA that wrote acc and this.
+__device__ __forceinline__ void acc_scale(f32x16& acc, float a) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float x = acc[r], tmp;
+        asm volatile("v_accvgpr_read_b32 %1, %0\n\tv_mul_f32 %1, %1, %2\n\ts_nop 0\n\tv_accvgpr_write_b32 %0, %1\n\ts_nop 1"
+                     : "+a"(x), "=&v"(tmp)
+                     : "v"(a));
+        acc[r] = x;
+    }
 }
 
 static inline int rsvld_check_launch() {

@@ -14,9 +14,6 @@
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split8v(const float (&f)[8], u32x4& lo, u32x4& hi) {   // split8 as two 16-byte register quads
     bf16x8 hv, lv;
@@ -254,11 +251,6 @@ __global__ __launch_bounds__(256, 2) void attn_split_d64_kernel(AttnSplitArgs p)
     // pieces of 8 rows x 128 B each = 8 pieces per tile.  Lane (row = lane>>3, pos = lane&7) fills LDS chunk `pos` of its row with
     // source chunk pos ^ ((r16>>1)&7) for K and pos ^ (((r16>>1)&1)<<2) for V (r16 = tile row & 15): the images the fragment
     // reads below expect (attention.hip).  Full tiles: one scalar base per tensor + a 32-bit lane offset.
-    auto dma_one = [&](const char* base, uint32_t voff, uint32_t dst) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-    };
     const int64_t k_rowb = p.k_ts * (int64_t)sizeof(bf16), v_rowb = p.v_ts * (int64_t)sizeof(bf16);
     const int64_t k_plb = p.k_pl * (int64_t)sizeof(bf16), v_plb = p.v_pl * (int64_t)sizeof(bf16);
     uint32_t kvo[2], vvo[2];
@@ -274,16 +266,14 @@ __global__ __launch_bounds__(256, 2) void attn_split_d64_kernel(AttnSplitArgs p)
         const int tens = j >> 2, pl = (j >> 1) & 1, i = j & 1;
         const uint32_t dst = lds0 + (4 * tens + 2 * pl + (t & 1)) * AS_TILE + (16 * w + 8 * i) * 128;
         if (t * 64 + 64 <= p.Nk) {
-            if (tens == 0) dma_one(k_tile0 + (int64_t)t * 64 * k_rowb + pl * k_plb, kvo[i], dst);
-            else dma_one(v_tile0 + (int64_t)t * 64 * v_rowb + pl * v_plb, vvo[i], dst);
+            if (tens == 0) rsvld_lds_dma16(k_tile0 + (int64_t)t * 64 * k_rowb + pl * k_plb, kvo[i], dst);
+            else rsvld_lds_dma16(v_tile0 + (int64_t)t * 64 * v_rowb + pl * v_plb, vvo[i], dst);
         } else {   // ragged last tile: rows past Nk re-read the last key (their scores are masked); per-lane 64-bit addresses
             const int rr = 8 * i + (lane >> 3), r16 = (16 * w + rr) & 15;
             const int key = min(t * 64 + 16 * w + rr, p.Nk - 1);
             const char* src = tens == 0 ? (const char*)(Kb + (int64_t)key * p.k_ts) + pl * k_plb + (((lane & 7) ^ ((r16 >> 1) & 7)) << 4)
                                         : (const char*)(Vb + (int64_t)key * p.v_ts) + pl * v_plb + (((lane & 7) ^ (((r16 >> 1) & 1) << 2)) << 4);
-            uint32_t keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+            rsvld_lds_dma16_addr(src, dst);
         }
     };
 #pragma unroll
@@ -331,10 +321,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_d64_kernel(AttnSplitArgs p)
             voff[dt] = row * 128 + (((4 * dt + 2 * g1 + (pp >> 1)) ^ (((row >> 1) & 1) << 2)) << 4) + ((pp & 1) << 3);
     }
     auto read_vt = [&](const char* base, int off) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + off));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + off + 1024));
-        typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-        return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        return tr16_pair<bf16x8>(lds_read_tr16(base + off), lds_read_tr16(base + off + 1024));
     };
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -380,8 +367,8 @@ __global__ __launch_bounds__(256, 2) void attn_split_d64_kernel(AttnSplitArgs p)
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (ST) {   // piece n: tensor n >> 2, plane (n >> 1) & 1, row group n & 1
                 const uint32_t dst = lds0 + (4 * (n >> 2) + 2 * ((n >> 1) & 1) + ((t + 1) & 1)) * AS_TILE + (16 * w + 8 * (n & 1)) * 128;
-                if ((n >> 2) == 0) dma_one(k_nxt + ((n >> 1) & 1) * k_plb, kvo[n & 1], dst);
-                else dma_one(v_nxt + ((n >> 1) & 1) * v_plb, vvo[n & 1], dst);
+                if ((n >> 2) == 0) rsvld_lds_dma16(k_nxt + ((n >> 1) & 1) * k_plb, kvo[n & 1], dst);
+                else rsvld_lds_dma16(v_nxt + ((n >> 1) & 1) * v_plb, vvo[n & 1], dst);
             } else if (more) dma_piece(t + 1, n);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -531,11 +518,6 @@ __global__ __launch_bounds__(256) void attn_split_d512_kernel(AttnSplit512Args p
     // ---- tile DMA (inline asm: the compiler must not know of it, or it drains vmcnt in front of every LDS read that follows; M0 is
     // saved and restored inside the statement).  Wave w moves key rows 8w .. 8w+7 of both planes, one 1-KiB row per piece; lane ->
     // LDS chunk position `lane`, source chunk lane ^ f(row & 15).
-    auto dma_one = [&](const char* base, uint32_t voff, uint32_t dst) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(base) : "memory");
-    };
     const int64_t rowb = p.x_ts * (int64_t)sizeof(bf16), plb = p.x_pl * (int64_t)sizeof(bf16);
     uint32_t xvo[8];
 #pragma unroll
@@ -545,10 +527,10 @@ __global__ __launch_bounds__(256) void attn_split_d512_kernel(AttnSplit512Args p
         const int i = j >> 1, pl = j & 1, r = w * 8 + i;
         const uint32_t dst = lds0 + (t & 1) * A5S_STAGE + pl * A5S_IMG + r * 1024;
         if (t * 32 + 32 <= p.Nk) {
-            dma_one(x_tile0 + (int64_t)t * 32 * rowb + pl * plb, xvo[i], dst);
+            rsvld_lds_dma16(x_tile0 + (int64_t)t * 32 * rowb + pl * plb, xvo[i], dst);
         } else {   // ragged last tile: rows past Nk re-read the last key; their scores are masked
             const int key = min(t * 32 + r, p.Nk - 1);
-            dma_one((const char*)(Xb + (int64_t)key * p.x_ts) + pl * plb, (uint32_t)((lane ^ a5s_f(r & 15)) << 4), dst);
+            rsvld_lds_dma16((const char*)(Xb + (int64_t)key * p.x_ts) + pl * plb, (uint32_t)((lane ^ a5s_f(r & 15)) << 4), dst);
         }
     };
 #pragma unroll
@@ -597,10 +579,7 @@ __global__ __launch_bounds__(256) void attn_split_d512_kernel(AttnSplit512Args p
             vbase[f] = (4 * lh + qq) * 1024 + ((f ^ qq) << 6) + (((2 * g1 + (pp >> 1)) ^ lh) << 4) + ((pp & 1) << 3);
     }
     auto read_vt = [&](const char* img, int off) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + off));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + (off ^ 32) + 8 * 1024));
-        typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-        return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        return tr16_pair<bf16x8>(lds_read_tr16(img + off), lds_read_tr16(img + (off ^ 32) + 8 * 1024));
     };
     char* xch_own = smem + A5S_XCH + w * 4096 + lane * 16;
     const char* xch_peer = smem + A5S_XCH + (w ^ 1) * 4096 + lane * 16;
@@ -645,7 +624,7 @@ __global__ __launch_bounds__(256) void attn_split_d512_kernel(AttnSplit512Args p
             sacc = mma_bf16(kh[ks % 3], ql[ks], sacc);
             sacc = mma_bf16(kh[ks % 3], qh[ks], sacc);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ST) dma_one(x_nxt + (ks & 1) * plb, xvo[ks >> 1], lds0 + ((t + 1) & 1) * A5S_STAGE + (ks & 1) * A5S_IMG + (w * 8 + (ks >> 1)) * 1024);
+            if constexpr (ST) rsvld_lds_dma16(x_nxt + (ks & 1) * plb, xvo[ks >> 1], lds0 + ((t + 1) & 1) * A5S_STAGE + (ks & 1) * A5S_IMG + (w * 8 + (ks >> 1)) * 1024);
             else if (more) dma_piece(t + 1, ks);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -695,19 +674,11 @@ __global__ __launch_bounds__(256) void attn_split_d512_kernel(AttnSplit512Args p
         if (__builtin_expect(__any(need), 0)) {
             // O lives in the accumulator file.  Written as plain C++ (oacc *= alpha) hipcc pulls all 128 values into VGPRs at once, and
             // the pressure of that one cold block makes it park Q in AccVGPRs for the WHOLE loop (every Q fragment copied back in front of
-            // its MFMA: 226 v_accvgpr_read per tile).  One element at a time through a scratch VGPR instead (attention_d512_body.inc);
+            // its MFMA: 226 v_accvgpr_read per tile).  One element at a time through a scratch VGPR instead (acc_scale);
             // the MFMA -> read hazard is covered by the 48 S-chain MFMAs since the last PV, the write -> MFMA hazard by the s_nop.
             asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
 #pragma unroll
-            for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float x = oacc[dt][r], tmp;
-                    asm volatile("v_accvgpr_read_b32 %1, %0\n\tv_mul_f32 %1, %1, %2\n\ts_nop 0\n\tv_accvgpr_write_b32 %0, %1\n\ts_nop 1"
-                                 : "+a"(x), "=&v"(tmp)
-                                 : "v"(alpha));
-                    oacc[dt][r] = x;
-                }
+            for (int dt = 0; dt < 8; ++dt) acc_scale(oacc[dt], alpha);
         }
         // ---- O^T[d][q] += X^T P^T over this wave's 8 d-blocks: 2 key steps x 3 terms each, fragments one pair ahead
         bf16x8 vl[3], vh[3];

@@ -1,4 +1,4 @@
-"""Per-kernel digests of the device assembly of attention.hip, split.hip, gemm.hip, norm.hip, f32.hip, conv_igemm.hip, conv_halo.hip and gemv.hip (the compile command of
+"""Per-kernel digests of the device assembly of attention.hip, split.hip, gemm.hip, norm.hip, f32.hip, conv_igemm.hip, conv_halo.hip, gemv.hip and prefill_attention.hip (the compile command of
 tools/audit_m0.py), to show that a source change left the shipped instruction streams alone.  A kernel's text runs from its label to
 .end_amdhsa_kernel, without ';' comments, trailing blanks and the function index in local labels (.LBB10_65 -> .LBB_65, likewise
 .Lfunc_end / .Ltmp); the digest is the first 16 hex digits of its sha256.
@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.join(ROOT, "remote-sensing-vision-language-diffusion-model_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 UNITS = {"attention.hip": ["-fno-slp-vectorize"], "split.hip": ["-fno-slp-vectorize"], "gemm.hip": [],   # the Makefile's per-unit flags
-         "norm.hip": [], "f32.hip": [], "conv_igemm.hip": [], "conv_halo.hip": [], "gemv.hip": []}
+         "norm.hip": [], "f32.hip": [], "conv_igemm.hip": [], "conv_halo.hip": [], "gemv.hip": [],
+         "prefill_attention.hip": ["-fno-slp-vectorize"]}
 # renamed kernels, per unit: (regex over the start of the old symbol, the start of its successor's symbol as a template of the match)
 N = "_ZN12_GLOBAL__N_1"
 RENAMES = {"norm.hip": [
