@@ -563,12 +563,15 @@ class FastDecoder:
         1 MiB per pack of memory that was to be freed.  So the size is probed first: a probe that came with more than its own bytes is
         held back (its hole is then out of the way) and the next one tried; the probe that fits alone is freed, and the pack's
         allocation, the same size on the same stream, takes the block it leaves (an exact fit is the smallest block that holds it).
-        After a few holes the allocator cuts from a large block or a fresh segment, which is exact; the held holes are freed again."""
+        After the holes the allocator cuts from a large block or a fresh segment, which is exact; the held holes are freed again.
+        How many holes there are depends on what the process did before (networks that pack lazily leave their packs between the
+        activations of their first forward, and the gaps stay when they are freed): the bound only ends the search, it is not expected
+        to be reached (8 was: the figure of tests/test_gpu_caption_e4m3_only.py stood 21 184 bytes above its bound behind the suite)."""
         from . import w8
         dev, nbytes = w.device, w.numel()                  # one e4m3 byte per weight
         exact = -(-nbytes // 512) * 512                      # the allocator's own rounding
         held, probe = [], None
-        for _ in range(8):
+        for _ in range(64):
             before = torch.cuda.memory_allocated(dev)
             probe = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             if torch.cuda.memory_allocated(dev) - before <= exact:

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from .... import ops
 from ...._lib import RsvldError
+from ....hipnn import precision
 
 OPENAIUNETWRAPPER = "rsvld_amd.sgm.modules.diffusionmodules.wrappers.ControlWrapper"
 
@@ -44,7 +45,7 @@ class ControlWrapper(nn.Module):
         return ops.nchw_to_nhwc(t, dt)
 
     def forward(self, x, t, c, control_scale=1, fbcache_mode="none", partial_info=None, **kwargs):
-        with ops.f32_split(self.split if self._compute_dtype() == torch.float32 else None):
+        with precision(self._compute_dtype(), self.split):
             return self._forward(x, t, c, control_scale, fbcache_mode, partial_info, **kwargs)
 
     def _forward(self, x, t, c, control_scale=1, fbcache_mode="none", partial_info=None, **kwargs):

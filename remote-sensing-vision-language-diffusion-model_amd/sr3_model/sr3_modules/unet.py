@@ -6,8 +6,8 @@ constructor arguments, same parameter names (so ``I1000000_E800_gen.pth`` loads 
 NHWC tensors that never leave HBM in NCHW form, and every layer is a kernel of librsvld_hip.so:
 
   Block            GN(32)+Swish (norm.hip) -> Conv3x3 implicit GEMM on MFMA (conv_igemm.hip)
-  FeatureWiseAffine all 26 noise-level projections in ONE stacked launch, consumed as the
-                   per-image row vector of block1's conv epilogue
+  FeatureWiseAffine all 26 noise-level projections in ONE stacked launch (HipNet.emb_rows), consumed
+                   as the per-image row vector of block1's conv epilogue
   ResnetBlock      residual / 1x1 res_conv add fused in block2's conv epilogue; the skip
                    concatenation (unet.py:257) is never materialised (two-source GN + conv)
   SelfAttention    fused qkv 1x1 GEMM -> flash attention, d = 512 (attention.hip) -> out 1x1 GEMM
@@ -15,7 +15,11 @@ NHWC tensors that never leave HBM in NCHW form, and every layer is a kernel of l
   Upsample         nearest x2 folded into the conv's gather;  Downsample: stride-2 gather
 
 The nn.Conv2d / nn.GroupNorm / nn.Linear children only HOLD parameters under the reference's
-names; their ``forward`` is never called.
+names; their ``forward`` is never called.  ``UNet`` is a ``hipnn.HipNet``: the precision record
+(``compute_dtype``, ``pack_dtype``, ``split``, ``precision_key()``), the packed weights and their
+life cycle (``pk``, ``packed``, ``pack_version``, ``invalidate_packed()``) are the base's, and each
+layer fetches its weights where it uses them.  What is SR3's own is the parsing of the five
+precision names and the two re-associated attention weights.
 """
 import math
 
@@ -24,6 +28,7 @@ from torch import nn
 
 from ... import ops
 from ..._lib import RsvldError
+from ...hipnn import HipNet
 
 
 class PositionalEncoding(nn.Module):  # parameter-free; index 0 of noise_level_mlp (unet.py:19-32)
@@ -77,6 +82,10 @@ class ResnetBlock(nn.Module):
         self.block2 = Block(dim_out, dim_out, groups=norm_groups, dropout=dropout)
         self.res_conv = nn.Conv2d(dim, dim_out, 1) if dim != dim_out else nn.Identity()
 
+    @property
+    def _emb_linear(self):  # picked up by HipNet.emb_rows
+        return self.noise_func.noise_func[0]
+
 
 class SelfAttention(nn.Module):
     def __init__(self, in_channel, n_head=1, norm_groups=32):
@@ -96,7 +105,7 @@ class ResnetBlocWithAttn(nn.Module):
             self.attn = SelfAttention(dim_out, norm_groups=norm_groups)
 
 
-class UNet(nn.Module):
+class UNet(HipNet):
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8), res_blocks=3, dropout=0,
                  with_noise_level_emb=True, image_size=128):
@@ -144,144 +153,64 @@ class UNet(nn.Module):
         self.ups = nn.ModuleList(ups)
         self.final_conv = Block(cur, self.out_channel, groups=norm_groups)
 
-        self.compute_dtype = torch.float16   # storage / MFMA operand type of the activations
-        self.pack_dtype = torch.float16      # type the weights are packed in: = compute_dtype, or fp32 masters under fp16 activations ("w2")
-        self.split = None                    # with compute_dtype fp32: the ops.SplitPolicy of the split precision ("split"), else None
-        self._pk = None                      # packed weights, built lazily on the parameters' device
-
-    # ------------------------------------------------------------------ weight packing
-    # ``pack_version`` counts invalidations: anything that holds raw pointers into the packed tensors (the sampler's
-    # captured hipGraphs) keys itself on it and is rebuilt after a weight reload / move / dtype change.
-    pack_version = 0
-
-    def invalidate_packed(self):
-        self._pk = None
-        self.pack_version += 1
-
     def set_compute_dtype(self, dt, policy=None):
         """fp16 (default) / bf16: 16-bit storage, fp32 accumulation; fp32: the fp32-operand kernel family (what the reference's
         own Stage 1 computes in: it runs without autocast); "split": fp32 tensors, matrix products on split operands (three 16-bit
         MFMAs per product) under ``policy`` (an ``ops.SplitPolicy``, default ``ops.UNET_POLICY``); "w2" (round 5): fp16 tensors like
         "fp16", but every weight as the fp16 PAIR [W_lo | W_hi] (dtype RSVLD_F16W2, two MFMAs per product) -- the rounding of the
-        WEIGHTS is the whole distance of "fp16" from the reference's CPU path after T = 50 steps."""
+        WEIGHTS is the whole distance of "fp16" from the reference's CPU path after T = 50 steps.
+        Only parses: the rules (which packs are kept, what bumps ``pack_version``) are ``HipNet.set_precision``'s."""
         split = None
-        if dt == "split":               # captured hipGraphs bake the mode in: a new version drops them
+        if dt == "split":
             split = policy or ops.UNET_POLICY
             if not isinstance(split, ops.SplitPolicy):
                 raise TypeError("set_compute_dtype: policy must be an rsvld_amd.ops.SplitPolicy")
-        if split != self.split:
-            self.split = split
-            self.pack_version += 1
         pack = torch.float32 if dt == "w2" else None
         dt = {"fp16": torch.float16, "w2": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32, "split": torch.float32}.get(dt, dt)
         if dt not in (torch.float16, torch.bfloat16, torch.float32):
             raise ValueError(f"compute_dtype {dt!r}: fp16, w2, bf16, fp32 or split")
-        pack = pack or dt
-        if dt != self.compute_dtype or pack != self.pack_dtype:
-            self.compute_dtype, self.pack_dtype = dt, pack
-            self.invalidate_packed()
+        self.set_precision(dt, pack, split)
 
-    def precision_key(self):
-        return (str(self.compute_dtype), str(self.pack_dtype), None if self.split is None else self.split.key())
-
-    def load_state_dict(self, *a, **k):
-        self.invalidate_packed()
-        return super().load_state_dict(*a, **k)
-
-    def _load_from_state_dict(self, *a, **k):   # reached when a PARENT module's load_state_dict recurses into this one
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):  # .to(device) / .half() etc. move the fp32 masters
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
-
-    def _res_blocks(self):
-        for seq in (self.downs, self.mid, self.ups):
-            for layer in seq:
-                if isinstance(layer, ResnetBlocWithAttn):
-                    yield layer
-
-    def _pack(self):
-        dev = self.noise_level_mlp[1].weight.device
-        if dev.type != "cuda":
-            raise RsvldError("SR3 UNet: parameters must be on the GPU (there is no CPU execution path)")
-        dt = self.pack_dtype
-        pk = {}
-
-        def conv(m, **kw):
-            pk[id(m)] = ops.pack_conv(m.weight, m.bias, dt, dev, **kw)
-
-        conv(self.downs[0])
-        # stacked noise-level projections: one [sum(C), emb] matrix, offsets per block
-        ws, bs, off = [], [], 0
-        for rb in self._res_blocks():
-            lin = rb.res_block.noise_func.noise_func[0]
-            pk[("nf", id(rb))] = (off, lin.out_features)
-            ws.append(lin.weight.detach().float())
-            bs.append(lin.bias.detach().float())
-            off += lin.out_features
-        pk["nf_w"] = torch.cat(ws, 0).contiguous().to(dev)
-        pk["nf_b"] = torch.cat(bs, 0).contiguous().to(dev)
-        for seq in (self.downs, self.mid, self.ups):
-            for layer in seq:
-                if isinstance(layer, (Downsample, Upsample)):
-                    conv(layer.conv)
-                elif isinstance(layer, ResnetBlocWithAttn):
-                    rb = layer.res_block
-                    c_in = rb.block1.block[0].num_channels
-                    conv(rb.block1.block[3])
-                    conv(rb.block2.block[3])
-                    if isinstance(rb.res_conv, nn.Conv2d):
-                        pk[("res", id(rb))] = c_in  # split decided at run time (skip concat or not)
-                    if layer.with_attn:
-                        if layer.attn.n_head != 1:
-                            raise NotImplementedError("SR3 SelfAttention is built with n_head=1 (unet.py:151)")
-                        self._pack_attention(pk, layer.attn, dt, dev)
-        conv(self.final_conv.block[3])
-        self._pk = pk
-        return pk
-
+    # ------------------------------------------------------------------ re-associated attention weights
+    # Single-head attention with keys and values taken from ONE tensor (csrc/attention.hip, "SH" note):
+    #     softmax(q k^T / sqrt(C)) v,  q = n Wq^T, k = n Wk^T, v = n Wv^T   (unet.py:126-141, qkv without bias)
+    #   = softmax((n Wq^T Wk) n^T / sqrt(C)) n  Wv^T
+    # so the query projection becomes Wk^T Wq (one C x C conv instead of the 3C-wide qkv conv), the keys AND values are
+    # the normalised input itself, and Wv moves into the output projection (W_out Wv).  Products in fp32 on the host.
     @staticmethod
-    def _pack_attention(pk, at, dt, dev):
-        """Single-head attention with keys and values taken from ONE tensor (csrc/attention.hip, "SH" note):
-            softmax(q k^T / sqrt(C)) v,  q = n Wq^T, k = n Wk^T, v = n Wv^T   (unet.py:126-141, qkv without bias)
-          = softmax((n Wq^T Wk) n^T / sqrt(C)) n  Wv^T
-        so the query projection becomes Wk^T Wq (one C x C conv instead of the 3C-wide qkv conv), the keys AND values are
-        the normalised input itself, and Wv moves into the output projection (W_out Wv).  Products in fp32 on the host."""
-        w = at.qkv.weight.detach().to("cpu", torch.float32).flatten(1)          # [3C, C]
-        C_ = w.shape[1]
-        wq, wk, wv = w[:C_], w[C_:2 * C_], w[2 * C_:]
+    def _wq_wk_wv(at):
+        if at.n_head != 1:
+            raise NotImplementedError("SR3 SelfAttention is built with n_head=1 (unet.py:151)")
         if at.qkv.bias is not None:
             raise NotImplementedError("SR3 SelfAttention's qkv conv has no bias (unet.py:121)")
-        pk[("attn_q", id(at))] = ops.pack_conv((wk.t() @ wq).contiguous(), None, dt, dev)
-        wo = at.out.weight.detach().to("cpu", torch.float32).flatten(1)        # [C, C]
-        pk[("attn_out", id(at))] = ops.pack_conv((wo @ wv).contiguous(), at.out.bias, dt, dev)
+        w = at.qkv.weight.detach().to("cpu", torch.float32).flatten(1)          # [3C, C]
+        C_ = w.shape[1]
+        return w[:C_], w[C_:2 * C_], w[2 * C_:]
 
-    def _res_conv_packed(self, rb, split):
-        key = ("resw", id(rb), split)
-        pk = self._pk
-        if key not in pk:
-            m = rb.res_conv
-            pk[key] = ops.pack_conv(m.weight, m.bias, self.pack_dtype, m.weight.device, cin_split=split)
-        return pk[key]
+    def _pack_attn_q(self, at):
+        wq, wk, _ = self._wq_wk_wv(at)
+        return ops.pack_conv((wk.t() @ wq).contiguous(), None, self.pack_dtype, self._dev(at.qkv.weight))
+
+    def _pack_attn_out(self, at):
+        wv = self._wq_wk_wv(at)[2]
+        wo = at.out.weight.detach().to("cpu", torch.float32).flatten(1)        # [C, C]
+        return ops.pack_conv((wo @ wv).contiguous(), at.out.bias, self.pack_dtype, self._dev(at.out.weight))
 
     # ------------------------------------------------------------------ forward pieces
     def _block(self, blk, x, x2=None, **conv_kw):
         """GN(32)+Swish+Conv3x3 as ONE fused conv call: statistics pass + conv with the normalisation applied
         while the input patch is staged (ops.conv2d norm=...); the skip concat [x | x2] is never built."""
         gn = blk.block[0]
-        return ops.conv2d(x, self._pk[id(blk.block[3])], x2=x2, norm=(gn.weight, gn.bias, gn.num_groups, gn.eps, True),
+        return ops.conv2d(x, self.pk(blk.block[3]), x2=x2, norm=(gn.weight, gn.bias, gn.num_groups, gn.eps, True),
                           **conv_kw)
 
-    def _resblock(self, layer, x, x2, nf_all):
+    def _resblock(self, layer, x, x2, rows):
+        """``rows``: ``emb_rows`` of the noise-level embedding (every FeatureWiseAffine at once)."""
         rb = layer.res_block
-        off, width = self._pk[("nf", id(layer))]
-        rowvec = nf_all[:, off:off + width]
-        h = self._block(rb.block1, x, x2, rowvec=rowvec, stats=True)     # its output feeds block2's GroupNorm
+        h = self._block(rb.block1, x, x2, rowvec=rows[id(rb)], stats=True)     # its output feeds block2's GroupNorm
         if isinstance(rb.res_conv, nn.Conv2d):
-            split = None if x2 is None else (x.shape[-1], x2.shape[-1])
-            res = ops.conv2d(x, self._res_conv_packed(rb, split), x2=x2, pad=0)
+            split = None if x2 is None else (x.shape[-1], x2.shape[-1])     # decided at run time: skip concat or not
+            res = ops.conv2d(x, self.pk(rb.res_conv, tag=split, cin_split=split), x2=x2, pad=0)
         else:
             res = x
         h = self._block(rb.block2, h, residual=res, stats=not layer.with_attn)   # ... and the next block's, unless attention follows
@@ -293,44 +222,40 @@ class UNet(nn.Module):
         B, H, W, Cc = x.shape
         # (planes / out_planes: honoured in the split precision only -- n feeds the query conv and the attention, q the attention)
         n = ops.group_norm(x, at.norm.weight, at.norm.bias, at.norm.num_groups, at.norm.eps, planes=True)
-        q = ops.conv2d(n, self._pk[("attn_q", id(at))], pad=0, out_planes=True).reshape(B, H * W, Cc)
-        kv = n.reshape(B, H * W, Cc)              # keys and values are the normalised input itself (_pack_attention)
+        wq = self.packed(("attn_q", id(at)), self._pack_attn_q, at)
+        q = ops.conv2d(n, wq, pad=0, out_planes=True).reshape(B, H * W, Cc)
+        kv = n.reshape(B, H * W, Cc)              # keys and values are the normalised input itself (see _wq_wk_wv)
         o = ops.attention(q, kv, kv, heads=1, scale=1.0 / math.sqrt(Cc))  # scale uses the full channel count (unet.py:135)
-        return ops.conv2d(o.reshape(B, H, W, Cc), self._pk[("attn_out", id(at))], pad=0, residual=x)
+        wo = self.packed(("attn_out", id(at)), self._pack_attn_out, at)
+        return ops.conv2d(o.reshape(B, H, W, Cc), wo, pad=0, residual=x)
 
     def forward_nhwc(self, x, noise_level):
         """x: 16-bit NHWC ``[B,H,W,pad8(in_channel)]``; noise_level fp32 ``[B,1]`` -> fp32 NHWC eps
         ``[B,H,W,pad8(out_channel)]`` (channels beyond out_channel are zero)."""
-        with ops.f32_split(self.split if self.compute_dtype == torch.float32 else None):
-            return self._forward_nhwc(x, noise_level)
+        with self.precision():
+            mlp = self.noise_level_mlp
+            pe = ops.sinusoidal(noise_level, mlp[0].dim, 0)
+            t = ops.linear_small(pe, mlp[1].weight, mlp[1].bias, 0, 1)   # Linear + Swish
+            t = ops.linear_small(t, mlp[3].weight, mlp[3].bias)
+            rows = self.emb_rows(t, act_in=0)
 
-    def _forward_nhwc(self, x, noise_level):
-        if self._pk is None:
-            self._pack()
-        pk = self._pk
-        mlp = self.noise_level_mlp
-        pe = ops.sinusoidal(noise_level, mlp[0].dim, 0)
-        t = ops.linear_small(pe, mlp[1].weight, mlp[1].bias, 0, 1)   # Linear + Swish
-        t = ops.linear_small(t, mlp[3].weight, mlp[3].bias)
-        nf_all = ops.linear_small(t, pk["nf_w"], pk["nf_b"])         # every FeatureWiseAffine at once
-
-        feats = []
-        for layer in self.downs:
-            if isinstance(layer, ResnetBlocWithAttn):
-                x = self._resblock(layer, x, None, nf_all)
-            elif isinstance(layer, Downsample):
-                x = ops.conv2d(x, pk[id(layer.conv)], stride=2, pad=1)
-            else:
-                x = ops.conv2d(x, pk[id(layer)], pad=1)
-            feats.append(x)
-        for layer in self.mid:
-            x = self._resblock(layer, x, None, nf_all)
-        for layer in self.ups:
-            if isinstance(layer, ResnetBlocWithAttn):
-                x = self._resblock(layer, x, feats.pop(), nf_all)
-            else:
-                x = ops.conv2d(x, pk[id(layer.conv)], pad=1, upsample=True, stats=True)
-        return self._block(self.final_conv, x, out_f32=True)
+            feats = []
+            for layer in self.downs:
+                if isinstance(layer, ResnetBlocWithAttn):
+                    x = self._resblock(layer, x, None, rows)
+                elif isinstance(layer, Downsample):
+                    x = ops.conv2d(x, self.pk(layer.conv), stride=2, pad=1)
+                else:
+                    x = ops.conv2d(x, self.pk(layer), pad=1)
+                feats.append(x)
+            for layer in self.mid:
+                x = self._resblock(layer, x, None, rows)
+            for layer in self.ups:
+                if isinstance(layer, ResnetBlocWithAttn):
+                    x = self._resblock(layer, x, feats.pop(), rows)
+                else:
+                    x = ops.conv2d(x, self.pk(layer.conv), pad=1, upsample=True, stats=True)
+            return self._block(self.final_conv, x, out_f32=True)
 
     def forward(self, x, time):
         """Reference contract (unet.py:236-261): fp32 NCHW ``[B,in,H,W]``, ``time [B,1]`` -> fp32 NCHW."""

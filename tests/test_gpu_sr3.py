@@ -41,14 +41,13 @@ def test_unet_layers_teacher_forced(sr3, cuda, golden_dir):
     from rsvld_amd import ops
     net, _ = sr3
     unet = net.denoise_fn
-    unet._pack()
     z = np.load(os.path.join(golden_dir, "sr3_unet_taps.npz"))
     lvl = torch.tensor(z["level"]).to(cuda)
     mlp = unet.noise_level_mlp
     pe = ops.sinusoidal(lvl, mlp[0].dim, 0)
     t = ops.linear_small(ops.linear_small(pe, mlp[1].weight, mlp[1].bias, 0, 1), mlp[3].weight, mlp[3].bias)
     assert _err(t, z["t_emb"]) < 1e-5
-    nf_all = ops.linear_small(t, unet._pk["nf_w"], unet._pk["nf_b"])
+    nf_all = unet.emb_rows(t, act_in=0)
     mods = dict(unet.named_modules())
     dt = unet.compute_dtype
     from rsvld_amd.sr3_model.sr3_modules import unet as U
@@ -71,13 +70,13 @@ def test_unet_layers_teacher_forced(sr3, cuda, golden_dir):
             else:
                 y = unet._resblock(m, x, None, nf_all)
         elif isinstance(m, U.Downsample):
-            y = ops.conv2d(x, unet._pk[id(m.conv)], stride=2, pad=1)
+            y = ops.conv2d(x, unet.pk(m.conv), stride=2, pad=1)
         elif isinstance(m, U.Upsample):
-            y = ops.conv2d(x, unet._pk[id(m.conv)], pad=1, upsample=True)
+            y = ops.conv2d(x, unet.pk(m.conv), pad=1, upsample=True)
         elif isinstance(m, U.Block):
             y = unet._block(m, x, out_f32=True)
         else:
-            y = ops.conv2d(x, unet._pk[id(m)], pad=1)
+            y = ops.conv2d(x, unet.pk(m), pad=1)
         got = ops.nhwc_to_nchw(y, channels=want.shape[1])
         scale = float(np.abs(want).max())
         e = _err(got, want)
