@@ -547,6 +547,39 @@ typedef struct rsvld_prefill_attention_plan {
 } rsvld_prefill_attention_plan;
 int rsvld_plan_llama_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_prefill_attention_plan* plan);
 
+/* The decode-step attention of rsvld_llama_decode_attention_rows on MFMAs (opt-in: FastDecoder(decode_attention="mfma"),
+ * --caption_attention mfma): the same operands, the same cache update, B = 1..RSVLD_DECODE_MAX_ROWS sequences with a DEVICE position
+ * each.  Replaces, like the VALU operator, the rotary embedding, cache write, scores, softmax and P V of one new token in
+ * LlamaAttention.forward behind models/util.py:17-66.  Three launches: a prologue rotates q and k (the VALU operator's own three
+ * roundings), writes k and v into the caches at the clamped pos[b] and the rotated q into the workspace; the attention kernel, one
+ * workgroup per (sequence, kv head, range of range_keys keys on absolute boundaries), only reads: K and V of its range arrive in LDS by
+ * LDS-DMA, the scores S^T = K Q^T are taken on 32x32x16 MFMAs with the group's query heads as columns (padding columns repeat a real
+ * head and store nothing), scaled in fp32 and never rounded to 16 bits, masked by selection; P is rounded to the 16-bit type only as
+ * the operand of O^T += V^T P^T; the four waves take 32 keys each and their (m, l, O) meet in LDS in wave order; the range's partial
+ * goes to the workspace and the VALU operator's combine kernel folds the ranges (in two rounds above 64 of them).
+ * ws: rsvld_llama_decode_attention_mma_rows_ws_bytes (linear in B), 16-byte aligned: [B][n_q][128] rotated q in dtype, then the partials.
+ * CONTRACT
+ * 1. out[b] and the cache rows written for sequence b are a function of qkv[b], cos[b], sin[b], pos[b] and of sequence b's cache rows
+ *    0 .. pos[b] - 1 alone, bit for bit: the same for every B in 1..8 and whatever the other sequences hold (NaN and Inf included), for
+ *    every max_len > pos[b] and whatever the cache holds above pos[b] (no cache row above pos[b] is ever requested: the rows of the
+ *    owning tile above it re-read row pos[b], their scores are -inf by selection and their V registers zero), and across runs (no
+ *    atomics; every sum has one fixed order, which range_keys -- a constant -- and the absolute boundaries decide).
+ * 2. The caches after the call equal, bit for bit, what rsvld_llama_decode_attention_rows leaves; no other byte of a cache changes.
+ * 3. out is NOT bit-equal to rsvld_llama_decode_attention_rows': that kernel rounds the scores to the 16-bit type and keeps P in fp32,
+ *    this one keeps the scores in fp32 and rounds P.  Both lie within the attention tolerance of an fp64 softmax.
+ * 4. pos outside [0, max_len) is clamped as there.  B outside 1..8, a null pointer, qkv / caches / ws not 16-byte aligned:
+ *    RSVLD_EINVAL.  head_dim != 128 or n_q / n_kv > 8: RSVLD_EUNSUPPORTED.  There is no fallback to the VALU operator. */
+size_t rsvld_llama_decode_attention_mma_rows_ws_bytes(int n_q, int n_kv, int max_len, int B);
+int rsvld_llama_decode_attention_mma_rows(const void* qkv, const void* cos, const void* sin, const int64_t* pos, void* kcache, void* vcache,
+                                          void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
+                                          void* stream);
+/* Its launch (host only, nothing is launched); takes no B.  range_keys is a constant: the same for every max_len, which only sets
+ * ranges = ceil(max_len / range_keys).  waves per workgroup, lds_bytes per workgroup, grid_x kv heads x grid_y ranges per sequence. */
+typedef struct rsvld_decode_attention_mma_plan {
+    int32_t range_keys, ranges, waves, lds_bytes, grid_x, grid_y;
+} rsvld_decode_attention_mma_plan;
+int rsvld_plan_llama_decode_attention_mma(int n_q, int n_kv, int max_len, int dtype, rsvld_decode_attention_mma_plan* plan);
+
 /* The PROJECTIONS of that prefill on the e4m3 packs of the token loop (opt-in: FastDecoder(prefill_weights="e4m3"), --caption_weights
  * e4m3-only): out[m][n] = T(scale[n] * sum_k x[m][k] e4m3(q[n][k]) + bias[n]), the formula of rsvld_gemv_w8_fused without its fused
  * neighbours, for M activation rows.  Replaces torch.nn.functional.linear on the 16-bit weights in the _lin calls of

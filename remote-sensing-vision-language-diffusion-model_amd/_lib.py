@@ -75,6 +75,13 @@ class PrefillAttentionPlan(C.Structure):
     _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("rows_per_wg", C.c_int32), ("keys_per_tile", C.c_int32)]
 
 
+class DecodeAttentionMmaPlan(C.Structure):
+    """rsvld_decode_attention_mma_plan (rsvld_plan_llama_decode_attention_mma, host only): no field depends on a sequence count, and
+    ``range_keys`` on nothing at all."""
+    _fields_ = [("range_keys", C.c_int32), ("ranges", C.c_int32), ("waves", C.c_int32), ("lds_bytes", C.c_int32), ("grid_x", C.c_int32),
+                ("grid_y", C.c_int32)]
+
+
 class GemmW8Plan(C.Structure):
     """rsvld_gemm_w8_plan (rsvld_plan_gemm_w8, host only)."""
     _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32), ("tile_k", C.c_int32),
@@ -152,6 +159,9 @@ SIGNATURES = {
     "rsvld_llama_decode_attention_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_llama_prefill_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "rsvld_plan_llama_prefill_attention": (_i, [_i, _i, _i, _i, C.POINTER(PrefillAttentionPlan)]),
+    "rsvld_llama_decode_attention_mma_rows_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "rsvld_llama_decode_attention_mma_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "rsvld_plan_llama_decode_attention_mma": (_i, [_i, _i, _i, _i, C.POINTER(DecodeAttentionMmaPlan)]),
     "rsvld_gemm_w8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rsvld_plan_gemm_w8": (_i, [_i, _i, _i, _i, C.POINTER(GemmW8Plan)]),
     "rsvld_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),

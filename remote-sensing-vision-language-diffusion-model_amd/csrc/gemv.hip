@@ -12,6 +12,7 @@
 // of 16 rows, ONE per CU with 32 KiB of weight loads in flight where ~64 KiB per CU are needed to keep HBM busy) run with the four waves
 // of a workgroup SPLITTING K for the same GV_RPW rows: four times the workgroups, partial sums through LDS.
 #include "rsvld_common.h"
+#include "decode_attention.h"   // da_rope, DA_HD, DA_GMAX, DA_PART, rsvld_da_combine_launch: shared with decode_attention_mma.hip
 #include <type_traits>
 
 namespace {
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(64 * GV_WAVES) void pack_rows_e4m3_kernel(const T* 
 // chunk maximum / exponentials / sum per head and the partial output [G][128] with its (m, l) into the workspace; da_combine_kernel
 // folds the chunks.  pos is read
 // from DEVICE memory (the step is replayed from a hipGraph): chunks beyond it write l = 0.  head_dim = 128.
-constexpr int DA_CH = 128, DA_HD = 128, DA_GMAX = 8;   // keys per workgroup: 8 kv heads x 26 chunks = 208 workgroups at the caption's ~3 300 keys
+constexpr int DA_CH = 128;   // keys per workgroup: 8 kv heads x 26 chunks = 208 workgroups at the caption's ~3 300 keys
 constexpr int DA_ROW = DA_HD * 2 + 16;                 // LDS row stride in bytes: four rows read by one wave instruction fall into different banks
 constexpr int DA_PIECES = DA_CH * 16 / 256;            // 16-byte pieces of the K (and of the V) chunk per thread
 
@@ -312,14 +313,7 @@ __global__ __launch_bounds__(256) void da_kernel(const T* __restrict__ qkv, cons
             kr[i] = *(const u32x4*)(kc + off);
             vr[i] = *(const u32x4*)(vc + off);
         }
-        // rotary embedding as the unfused sequence rounds it: T(x cos) + T(rot(x) sin) -> T
-        auto rope = [&](const T* src, int i) {
-#pragma clang fp contract(off)   // (three roundings, as three torch kernels leave them: hipcc otherwise demotes the sum to ONE 16-bit fma)
-            const float xr = i < half ? -(float)src[i + half] : (float)src[i - half];
-            const T a = (T)((float)src[i] * (float)cosv[i]);
-            const T b = (T)(xr * (float)sinv[i]);
-            return (float)(T)((float)a + (float)b);
-        };
+        auto rope = [&](const T* src, int i) { return da_rope(src, cosv, sinv, half, i); };   // (decode_attention.h)
         for (int i = tid; i < G * DA_HD; i += 256) qs[i / DA_HD][i % DA_HD] = rope(qkv + (size_t)(kvh * G + i / DA_HD) * DA_HD, i % DA_HD);
 #pragma unroll
         for (int i = 0; i < DA_PIECES; ++i) {
@@ -700,6 +694,15 @@ extern "C" int rsvld_llama_decode_attention_rows(const void* qkv, const void* co
         return 0;
     });
     return rsvld_check_launch();
+}
+
+// da_combine_kernel for the MFMA form of the step (decode_attention_mma.hip), whose partials have da_kernel's layout
+void rsvld_da_combine_launch(const float* ws, void* out, int n_q, int n_kv, int nchunk, int B, int dtype, hipStream_t stream) {
+    by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        hipLaunchKernelGGL((da_combine_kernel<T>), dim3(n_q, B), dim3(DA_HD), 0, stream, ws, (T*)out, n_q, n_kv, nchunk);
+        return 0;
+    });
 }
 
 extern "C" int rsvld_llama_decode_attention(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,

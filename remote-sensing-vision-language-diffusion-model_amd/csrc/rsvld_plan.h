@@ -371,6 +371,27 @@ inline int plan_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_
 }
 
 // ---------------------------------------------------------------------------------------
+// the decode-step attention on MFMAs (decode_attention_mma.hip): a workgroup owns (sequence, kv head, one range of DAM_RANGE keys on
+// absolute boundaries); its DAM_WAVES waves take DAM_RANGE / DAM_WAVES consecutive keys each.  DAM_RANGE is a constant -- no function
+// of the number of sequences, of max_len or of a position -- so the key order of a sequence's sum is the same in every call; max_len
+// only decides how many ranges there are (those above the position write neutral partials).  The number of sequences is no argument.
+// ---------------------------------------------------------------------------------------
+constexpr int DAM_RANGE = 128, DAM_WAVES = 4, DAM_TILE_KEYS = 64;
+constexpr int DAM_LDS_BYTES = 2 * DAM_RANGE * 128 * 2;   // K and V of the range, 16-bit
+static_assert(DAM_RANGE % 64 == 0 && DAM_RANGE % DAM_TILE_KEYS == 0 && DAM_RANGE / DAM_WAVES == 32, "a wave takes one 32-key MFMA block");
+inline int plan_decode_attention_mma(int n_q, int n_kv, int max_len, int dtype, rsvld_decode_attention_mma_plan* p) {
+    *p = rsvld_decode_attention_mma_plan{};
+    if (n_q < 1 || n_kv < 1 || max_len < 1 || n_q % n_kv != 0 || n_kv > 65535) return RSVLD_EINVAL;
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
+    if (n_q / n_kv > 8) return RSVLD_EUNSUPPORTED;
+    const int64_t ranges = ((int64_t)max_len + DAM_RANGE - 1) / DAM_RANGE;
+    if (ranges > 65535) return RSVLD_EUNSUPPORTED;                            // grid_y
+    p->range_keys = DAM_RANGE, p->ranges = (int32_t)ranges, p->waves = DAM_WAVES, p->lds_bytes = DAM_LDS_BYTES;
+    p->grid_x = n_kv, p->grid_y = (int32_t)ranges;
+    return RSVLD_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // 16-bit rows x e4m3 packs (gemm_w8.hip): ONE tile shape, ONE K order (ascending steps of GW_BK, no split over K), whatever the shape
 // is -- so there is nothing here that M could move: it enters grid_x alone, and a row's bits do not depend on the rows around it.
 // Grid = (row tiles, column tiles): the row tiles of one column tile are dispatched together and share its weight bytes in L2.

@@ -30,8 +30,21 @@ def plan_gemv_mma(N, K, w8=False, dtype=None):
     return pl
 
 
-def llama_decode_attention_rows(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None):
+def llama_decode_attention_rows(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None, kernel="valu"):
     """``ops.llama_decode_attention`` for ``B`` sequences with a position each (rsvld_llama_decode_attention_rows): ``qkv [B, (n_q + 2 n_kv)
     * 128]``, ``cos`` / ``sin [B, 128]``, ``pos [B]`` DEVICE int64, caches ``[B, n_kv, max_len, 128]`` updated at ``pos[b]`` in sequence
-    ``b``'s slice only; ``ws`` (optional, re-usable): fp32, ``B`` times the single workspace.  -> ``[B, n_q * 128]``."""
-    return ops._decode_attention_rows("llama_decode_attention_rows", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, False)
+    ``b``'s slice only; ``ws`` (optional, re-usable): fp32, ``B`` times the single workspace.  -> ``[B, n_q * 128]``.
+    ``kernel="mfma"`` (opt-in, ``ops.DECODE_ATTENTION_KERNELS``): the attention on MFMAs (rsvld_llama_decode_attention_mma_rows,
+    csrc/decode_attention_mma.hip; launch name ``llama_decode_attention_mma_rows``), at every ``B`` including 1: the caches end bit for
+    bit as "valu" leaves them, sequence ``b``'s output is bit-identical among ITS ``B``, ``max_len`` and neighbours, not to "valu" (fp32
+    scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P); ``ws`` then has rsvld_llama_decode_attention_mma_rows_ws_bytes."""
+    return ops._decode_attention_rows("llama_decode_attention_rows", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, False, kernel)
+
+
+def plan_decode_attention_mma(n_q, n_kv, max_len, dtype=None):
+    """The launch of the ``kernel="mfma"`` attention (rsvld_plan_llama_decode_attention_mma, host only): ``_lib.DecodeAttentionMmaPlan``.
+    There is no sequence count to pass, and ``range_keys`` is the same for every ``max_len``."""
+    pl = L.DecodeAttentionMmaPlan()
+    L.check(L.load().rsvld_plan_llama_decode_attention_mma(int(n_q), int(n_kv), int(max_len), L.F16 if dtype is None else ops._DT[dtype], pl),
+            "rsvld_plan_llama_decode_attention_mma")
+    return pl

@@ -75,10 +75,11 @@ class PipelineConfig:
     caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8), "e4m3-only" = the prefill on them too and the 16-bit decoder weights released (llava_next.CAPTION_WEIGHTS)
     caption_prefill: str = "torch"    # attention of the caption pass's prefill: "torch" = the stock-torch sequence over the whole cache, "flash" = the causal flash kernel (opt-in, rsvld_amd.prefill_attention)
     caption_decode: str = "valu"      # kernels of the token loop's products: "valu" = the vector-ALU ones, "mfma" = on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in, csrc/gemv_mma.hip; llava_next.CAPTION_DECODES)
+    caption_attention: str = "valu"   # attention of the token loop: "valu" = da_kernel on the vector ALU, "mfma" = key tiles by LDS-DMA, scores and P V on MFMAs (opt-in, csrc/decode_attention_mma.hip; llava_next.CAPTION_ATTENTIONS)
 
     def __post_init__(self):
-        caption_mode(self.caption_weights, self.caption_prefill, self.caption_decode, who="PipelineConfig",
-                     names=("caption_weights", "caption_prefill", "caption_decode"))
+        caption_mode(self.caption_weights, self.caption_prefill, self.caption_decode, self.caption_attention, who="PipelineConfig",
+                     names=("caption_weights", "caption_prefill", "caption_decode", "caption_attention"))
         self.output_dir = Path(self.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
         self.input_path = Path(self.input_img)
@@ -170,7 +171,7 @@ class SuperResolutionPipeline:
         return LN.get_img_describe(image_tensor=views, image=sr_image, model=self.llava_model, tokenizer=self.llava_tokenizer,
                                    prompt=img_prompt, max_new_tokens=256, device=dev, seed=seed,
                                    decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill,
-                                   decode_kernel=self.cfg.caption_decode)[0]
+                                   decode_kernel=self.cfg.caption_decode, decode_attention=self.cfg.caption_attention)[0]
 
     def run_stage2_captioning_batch(self, sr_images):
         """``run_stage2_captioning`` for the Stage-1 images of several inputs in ONE token loop (``infer_dir --caption_batch``) -> a list
@@ -193,7 +194,7 @@ class SuperResolutionPipeline:
         return LN.get_img_describe_batch(image_tensors=views, images=list(sr_images), model=self.llava_model, tokenizer=self.llava_tokenizer,
                                          prompt=img_prompt, max_new_tokens=256, device=dev, seeds=seeds,
                                          decode_weights=self.cfg.caption_weights, decode_prefill=self.cfg.caption_prefill,
-                                         decode_kernel=self.cfg.caption_decode)
+                                         decode_kernel=self.cfg.caption_decode, decode_attention=self.cfg.caption_attention)
 
     def _stage2_input(self, sr_image):
         if self.cfg.device_io:
@@ -291,7 +292,7 @@ def main(argv=None):
                          img_threshold=a.img_threshold, edm_steps=a.edm_steps, sr3_steps=a.sr3_steps, caption=a.caption,
                          no_llava=a.no_llava, llava_path=a.llava_path, llava_adapter=a.llava_adapter, use_tile_vae=a.use_tile_vae,
                          device_io=a.device_io, caption_weights=a.caption_weights, caption_prefill=a.caption_prefill,
-                         caption_decode=a.caption_decode,
+                         caption_decode=a.caption_decode, caption_attention=a.caption_attention,
                          **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if a.fp32 else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if a.tolerance else
                             dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if a.split else

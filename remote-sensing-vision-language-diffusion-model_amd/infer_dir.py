@@ -28,7 +28,7 @@ EXTS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 class ImageBatchProcessor:
     def __init__(self, image_dir, save_dir, upscale=8, num_steps=50, seed=42, img_threshold=0.3, sr3_steps=0, device="cuda:0",
                  no_llava=False, fp32=False, split=False, vae_split=False, tolerance=False, device_io=False, caption_weights="native",
-                 caption_batch=1, caption_prefill="torch", caption_decode="valu"):
+                 caption_batch=1, caption_prefill="torch", caption_decode="valu", caption_attention="valu"):
         if not isinstance(caption_batch, int) or not 1 <= caption_batch <= 8:
             raise ValueError(f"ImageBatchProcessor: caption_batch={caption_batch!r}, expected 1..8")
         self.caption_batch = caption_batch
@@ -39,6 +39,7 @@ class ImageBatchProcessor:
         self.kw = dict(output_dir=str(self.save_dir), upscale_factor=upscale, edm_steps=num_steps, seed=seed,
                        img_threshold=img_threshold, sr3_steps=sr3_steps, sr_model_device=device, base_model_device=device,
                        no_llava=no_llava, device_io=device_io, caption_weights=caption_weights, caption_prefill=caption_prefill, caption_decode=caption_decode,
+                       caption_attention=caption_attention,
                        **(dict(ae_dtype="fp32", diff_dtype="fp32", sr3_dtype="fp32") if fp32 else
                                                 dict(ae_dtype="split", diff_dtype="split", sr3_dtype="w2") if tolerance else
                                                 dict(ae_dtype="split", diff_dtype="split", sr3_dtype="split") if split else
@@ -153,7 +154,8 @@ def main(argv=None):
     proc = ImageBatchProcessor(a.image_dir, a.save_dir, a.upscale, a.num_steps, a.seed, a.img_threshold, a.sr3_steps,
                                device=f"cuda:{local}", no_llava=a.no_llava, fp32=a.fp32, split=a.split, vae_split=a.vae_split,
                                tolerance=a.tolerance, device_io=a.device_io, caption_weights=a.caption_weights,
-                               caption_batch=a.caption_batch, caption_prefill=a.caption_prefill, caption_decode=a.caption_decode)
+                               caption_batch=a.caption_batch, caption_prefill=a.caption_prefill, caption_decode=a.caption_decode,
+                               caption_attention=a.caption_attention)
     done, failed = proc.run(rank, world)
     print(f"[rank {rank}] wrote {len(done)} images, {len(failed)} failures")
 

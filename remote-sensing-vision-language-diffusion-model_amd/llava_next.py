@@ -48,15 +48,18 @@ DEFAULT_ADAPTER = "./CKPT_PTH/Llava-next"           # models/util.py:115
 # "e4m3-only": the prefill on the packs too and the 16-bit decoder weights released, CaptionMode(weights="e4m3", prefill_weights="e4m3",
 # release_native=True).  Decodes: "valu" runs the weight-streaming products on the vector ALU (csrc/gemv.hip); "mfma" (opt-in) on MFMAs
 # (csrc/gemv_mma.hip), whose arithmetic does not grow with the captions of a batch.  The two sum in different orders: other logits, the
-# same contract each.
+# same contract each.  A fourth switch, caption_attention / --caption_attention / decode_attention / attention, picks the token loop's
+# ATTENTION: "valu" is da_kernel of csrc/gemv.hip, "mfma" (opt-in) csrc/decode_attention_mma.hip -- key tiles by LDS-DMA, scores and P V
+# on MFMAs, fp32 scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P: other logits again, the same caches.
 CAPTION_WEIGHTS = ("native", "e4m3", "e4m3-only")
 CAPTION_PREFILLS = ("torch", "flash")
 CAPTION_DECODES = ("valu", "mfma")
+CAPTION_ATTENTIONS = ("valu", "mfma")
 
 
 @dataclasses.dataclass(frozen=True)
 class CaptionMode:
-    """What a ``FastDecoder`` runs on, beyond its model and the size of its cache: the five switches its docstring describes.  The record
+    """What a ``FastDecoder`` runs on, beyond its model and the size of its cache: the six switches its docstring describes.  The record
     owns every check of a value or a combination that needs no model; two decoders serve the same calls exactly when their records are
     equal (``_decoder_for``)."""
     weights: str = "native"
@@ -64,12 +67,13 @@ class CaptionMode:
     prefill_weights: str = "native"
     release_native: bool = False
     decode: str = "valu"
+    decode_attention: str = "valu"
 
     WEIGHTS = PREFILL_WEIGHTS = ("native", "e4m3")      # (un-annotated: class constants, not fields)
 
     def __post_init__(self):
         for name, allowed in (("decode", CAPTION_DECODES), ("weights", self.WEIGHTS), ("prefill", CAPTION_PREFILLS),
-                              ("prefill_weights", self.PREFILL_WEIGHTS)):
+                              ("prefill_weights", self.PREFILL_WEIGHTS), ("decode_attention", CAPTION_ATTENTIONS)):
             if getattr(self, name) not in allowed:
                 raise ValueError(f"FastDecoder: {name}={getattr(self, name)!r}, expected one of {allowed}")
         if self.prefill_weights == "e4m3" and self.weights != "e4m3":
@@ -80,17 +84,19 @@ class CaptionMode:
                              "nothing reads them)")
 
 
-def caption_mode(weights=None, prefill=None, decode=None, who="caption_mode", names=("weights", "prefill", "decode")):
-    """The user-level triple (a ``CAPTION_WEIGHTS``, a ``CAPTION_PREFILLS`` and a ``CAPTION_DECODES`` value; None = the default, the first
-    of its tuple) -> its ``CaptionMode``.  ``who`` / ``names``: the caller and what IT calls the three, for the error."""
-    tuples = (CAPTION_WEIGHTS, CAPTION_PREFILLS, CAPTION_DECODES)
-    weights, prefill, decode = (allowed[0] if v is None else v for v, allowed in zip((weights, prefill, decode), tuples))
-    for name, v, allowed in zip(names, (weights, prefill, decode), tuples):
+def caption_mode(weights=None, prefill=None, decode=None, attention=None, who="caption_mode", names=("weights", "prefill", "decode", "attention")):
+    """The user-level values (a ``CAPTION_WEIGHTS``, a ``CAPTION_PREFILLS``, a ``CAPTION_DECODES`` and a ``CAPTION_ATTENTIONS`` value; None =
+    the default, the first of its tuple) -> their ``CaptionMode``.  ``who`` / ``names``: the caller and what IT calls them, for the error
+    (three names: the fourth is "attention")."""
+    tuples = (CAPTION_WEIGHTS, CAPTION_PREFILLS, CAPTION_DECODES, CAPTION_ATTENTIONS)
+    names = tuple(names) + ("attention",) * (len(tuples) - len(names))
+    weights, prefill, decode, attention = (allowed[0] if v is None else v for v, allowed in zip((weights, prefill, decode, attention), tuples))
+    for name, v, allowed in zip(names, (weights, prefill, decode, attention), tuples):
         if v not in allowed:
             raise ValueError(f"{who}: {name}={v!r}, expected one of {allowed}")
     only = weights == "e4m3-only"
     return CaptionMode(weights="e4m3" if only else weights, prefill=prefill, prefill_weights="e4m3" if only else "native", release_native=only,
-                       decode=decode)
+                       decode=decode, decode_attention=attention)
 
 
 def decoder_mode(caption_weights):
@@ -100,7 +106,7 @@ def decoder_mode(caption_weights):
 
 
 def add_caption_arguments(p, batch=False):
-    """``--caption_weights``, ``--caption_prefill``, ``--caption_decode`` and (``batch``: the directory runner) ``--caption_batch`` on an
+    """``--caption_weights``, ``--caption_prefill``, ``--caption_decode``, ``--caption_attention`` and (``batch``: the directory runner) ``--caption_batch`` on an
     argparse parser; the runner's help texts say what the option means for a group of captions."""
     p.add_argument("--caption_weights", choices=CAPTION_WEIGHTS, default="native", help="weights of the caption pass's token loop: " + (
         "the checkpoint's 16-bit ones, e4m3 bytes with a scale per row, or e4m3-only: the prefill on them too and the 16-bit "
@@ -118,6 +124,11 @@ def add_caption_arguments(p, batch=False):
         "of --caption_batch N stay those of N = 1 inside the mode; see DESIGN.md section 8)" if batch else
         "on the vector ALU, or on MFMAs (another summation order: other logits, within the fp32 summation error; opt-in: "
         "fidelity on the real checkpoint is unmeasured)"))
+    p.add_argument("--caption_attention", choices=CAPTION_ATTENTIONS, default="valu", help="attention of the token loop: " + (
+        "on the vector ALU, or on MFMAs with key tiles by LDS-DMA (opt-in: other logits; the captions of --caption_batch N stay "
+        "those of N = 1 inside the mode; see DESIGN.md section 8)" if batch else
+        "on the vector ALU, or on MFMAs with key tiles by LDS-DMA (fp32 scores and a 16-bit P instead of 16-bit scores and an fp32 "
+        "P: other logits; opt-in: fidelity on the real checkpoint is unmeasured)"))
     if batch:
         p.add_argument("--caption_batch", type=int, default=1, choices=range(1, 9), metavar="N", help="caption the Stage-1 images of N (1..8) "
                        "inputs in one token loop (the captioner's weights are streamed once per token for all of them); the same captions "
@@ -429,8 +440,15 @@ class FastDecoder:
     either.  Attention, the prefill and sampling are untouched; it combines with every other switch.  The mode needs the fused decode
     step (``_fused_ok``); where that fails the decoder raises -- it never falls back to "valu" or to torch silently.
 
-    The five switches are ONE frozen record, ``self.mode`` (a ``CaptionMode``, which checks every value and combination that needs no
-    model); ``weights`` .. ``decode`` read it.  The weights are ONE table: per layer the products ``qkv``, ``o``, ``gu``, ``down``, then
+    ``decode_attention``: "valu" (default) runs the decode step's attention through da_kernel (csrc/gemv.hip).  "mfma" (opt-in) sends it
+    through csrc/decode_attention_mma.hip (``decode_rows.llama_decode_attention_rows(..., kernel="mfma")``) at EVERY row count,
+    ``generate``'s single row included, so that inside the mode ``generate_batch`` still equals ``generate`` per prompt: key and value
+    tiles by LDS-DMA, scores and P V on MFMAs, fp32 scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P -- other logits,
+    the same cache rows bit for bit.  It combines with every other switch and, like ``decode="mfma"``, needs the fused decode step
+    (``_fused_ok``): where that fails the decoder raises.
+
+    The six switches are ONE frozen record, ``self.mode`` (a ``CaptionMode``, which checks every value and combination that needs no
+    model); ``weights`` .. ``decode_attention`` read it.  The weights are ONE table: per layer the products ``qkv``, ``o``, ``gu``, ``down``, then
     ``head``, each a ``(w, b, pack)`` -- the 16-bit weight, the bias, the e4m3 pack, None where the mode has none -- which
     ``_prefill_product`` and ``_step_product`` take."""
 
@@ -442,12 +460,13 @@ class FastDecoder:
     Product = collections.namedtuple("Product", "w b pack")            # one matrix product: 16-bit weight | None, bias | None, (q, scale) | None
     LayerProducts = collections.namedtuple("LayerProducts", "qkv o gu down")
 
-    weights, prefill, prefill_weights, release_native, decode = (
-        property(lambda self, f=f: getattr(self.mode, f)) for f in ("weights", "prefill", "prefill_weights", "release_native", "decode"))
+    weights, prefill, prefill_weights, release_native, decode, decode_attention = (
+        property(lambda self, f=f: getattr(self.mode, f))
+        for f in ("weights", "prefill", "prefill_weights", "release_native", "decode", "decode_attention"))
 
     def __init__(self, model, max_len, weights="native", batch=1, prefill="torch", prefill_weights="native", release_native=False,
-                 decode="valu"):
-        mode = CaptionMode(weights, prefill, prefill_weights, bool(release_native), decode)
+                 decode="valu", decode_attention="valu"):
+        mode = CaptionMode(weights, prefill, prefill_weights, bool(release_native), decode, decode_attention)
         if not isinstance(batch, int) or not 1 <= batch <= self.MAX_BATCH:
             raise ValueError(f"FastDecoder: batch={batch!r}, expected 1..{self.MAX_BATCH}")
         parked = model.__dict__.get(self.PARKED)
@@ -687,6 +706,9 @@ class FastDecoder:
         if T == 1 and self.decode != "valu":
             raise RuntimeError(f"FastDecoder(decode={self.decode!r}): the fused decode step is not available for this model / input "
                                "(see _fused_ok) and the mode has no other path; use decode='valu'")
+        if T == 1 and self.decode_attention != "valu":
+            raise RuntimeError(f"FastDecoder(decode_attention={self.decode_attention!r}): the fused decode step is not available for this "
+                               "model / input (see _fused_ok) and the mode has no other path; use decode_attention='valu'")
         if T == 1 and self._packs is not None:
             raise RuntimeError("FastDecoder(weights='e4m3'): the fused decode step is not available for this model / input "
                                "(see _fused_ok) and the e4m3 weights have no other path; use weights='native'")
@@ -843,14 +865,16 @@ class FastDecoder:
             # ONE workspace for the decoder's life, sized for ``batch`` rows: the captured steps of ``_rows`` hold its address, so it is
             # never replaced (a buffer grown per row count would be freed under the graphs captured with fewer rows, ``_graph`` among
             # them).  Per-chunk partial results: written before they are read, no initial state.
-            need = int(DR.ops.L.load().rsvld_llama_decode_attention_rows_ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
+            lib = DR.ops.L.load()
+            ws_bytes = lib.rsvld_llama_decode_attention_mma_rows_ws_bytes if self.decode_attention == "mfma" else lib.rsvld_llama_decode_attention_rows_ws_bytes
+            need = int(ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
             self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
         gemv = self._step_product
         for i, (layer, w) in enumerate(zip(self.layers, self.table)):
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
             qkv = gemv(w.qkv, h, norm=(n1.weight, n1.variance_epsilon))
             o = DR.llama_decode_attention_rows(qkv, cos, sin, pos, self.k[i][row0:row0 + n], self.v[i][row0:row0 + n], self.n_q, self.n_kv, scale,
-                                               ws=self._ws_rows)
+                                               ws=self._ws_rows, kernel=self.decode_attention)
             h = gemv(w.o, o, residual=h)
             gu = gemv(w.gu, h, norm=(n2.weight, n2.variance_epsilon))
             h = gemv(w.down, gu, glu=True, residual=h)
@@ -886,6 +910,9 @@ class FastDecoder:
             if self.decode != "valu":
                 raise RuntimeError(f"FastDecoder(decode={self.decode!r}).generate_batch: the fused decode step is not available for this "
                                    "model / device (see _fused_ok) and the mode has no other path; use decode='valu'")
+            if self.decode_attention != "valu":
+                raise RuntimeError(f"FastDecoder(decode_attention={self.decode_attention!r}).generate_batch: the fused decode step is not "
+                                   "available for this model / device (see _fused_ok) and the mode has no other path; use decode_attention='valu'")
             import warnings
             warnings.warn("FastDecoder.generate_batch: the fused decode step is not available for this model / device; the prompts are "
                           "captioned one after another (same tokens)")
@@ -1102,7 +1129,7 @@ def _eos_ids(model, tokenizer):
 def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templates=conv_templates,
                      image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
                      do_sample=True, max_new_tokens=512, device="cuda", seed=None, fast=None, decode_weights=None, decode_prefill=None,
-                     decode_kernel=None):
+                     decode_kernel=None, decode_attention=None):
     """models/util.py:17-66 -> ``[caption]``.  ``seed`` (an addition) makes the caption a function of (image, prompt,
     weights, seed): sampling then runs inside ``torch.random.fork_rng`` with the CPU and the model's device generator seeded
     THERE, so the caller's generators -- which Stage 2 draws its noise from right afterwards, and in the reference live on
@@ -1117,9 +1144,11 @@ def get_img_describe(image_tensor, image, model, tokenizer, prompt, conv_templat
     ``decode_prefill`` (None = "torch"): "flash" runs the prefill's attention through the causal flash kernel
     (``FastDecoder(prefill=...)``, opt-in: other logits than the torch prefill gives); it needs the fast path too.
     ``decode_kernel`` (None = "valu"): "mfma" runs the token loop's products on MFMAs (``FastDecoder(decode=...)``, ``CAPTION_DECODES``,
-    opt-in: other logits, within the summation error); it needs the fast path too."""
+    opt-in: other logits, within the summation error); it needs the fast path too.
+    ``decode_attention`` (None = "valu"): "mfma" runs the token loop's attention on MFMAs (``FastDecoder(decode_attention=...)``,
+    ``CAPTION_ATTENTIONS``, opt-in: other logits); it needs the fast path too."""
     input_ids, mdev, fast, options = _describe_setup("get_img_describe", model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
-                                                     num_beams, device, fast, decode_weights, decode_prefill, decode_kernel)
+                                                     num_beams, device, fast, decode_weights, decode_prefill, decode_kernel, decode_attention)
 
     def run():
         if fast:   # (no_grad, not inference_mode: tensors made in inference mode cannot be updated in place by a later call
@@ -1156,11 +1185,12 @@ def _has_logits_warpers(model):
 
 
 def _describe_setup(who, model, tokenizer, prompt, conv_templates, image_token_index, conv_template, num_beams, device, fast, decode_weights,
-                    decode_prefill, decode_kernel):
-    """What ``get_img_describe`` and ``get_img_describe_batch`` (``who``) do before they caption: validate the three options and the
+                    decode_prefill, decode_kernel, decode_attention=None):
+    """What ``get_img_describe`` and ``get_img_describe_batch`` (``who``) do before they caption: validate the four options and the
     template, tokenise the prompt, decide ``fast`` -> ``(input_ids, the model's device, fast, the options as caption_tokens_fast(_batch)
     keywords)``.  An option that is not its default needs the fast path and raises without it."""
-    names, options = ("decode_weights", "decode_prefill", "decode_kernel"), dict(weights=decode_weights, prefill=decode_prefill, decode=decode_kernel)
+    names = ("decode_weights", "decode_prefill", "decode_kernel", "decode_attention")
+    options = dict(weights=decode_weights, prefill=decode_prefill, decode=decode_kernel, attention=decode_attention)
     default = caption_mode()
     mode = caption_mode(**options, who=who, names=names)
     if conv_template != "llava_llama_3":
@@ -1177,7 +1207,7 @@ def _describe_setup(who, model, tokenizer, prompt, conv_templates, image_token_i
         warnings.warn("llava_next: the checkpoint's generation_config asks for logits processors FastDecoder does not implement; "
                       "captioning through transformers' generate()")
         fast = False
-    for name, field, value in zip(names, ("weights", "prefill", "decode"), options.values()):
+    for name, field, value in zip(names, ("weights", "prefill", "decode", "decode_attention"), options.values()):
         if getattr(mode, field) != getattr(default, field) and not fast:
             raise ValueError(f"{who}: {name}={value!r} needs the FastDecoder token loop (a GPU model, one beam, no logits processors beyond "
                              f"temperature / top_k / top_p)")
@@ -1193,31 +1223,34 @@ def _decoder_for(model, need, rows, mode):
     if dec is None or dec.stale() or dec.mode != mode or dec.batch < rows or dec.max_len < need:
         model.__dict__.pop("_fast_decoder", None)
         del dec
-        model.__dict__["_fast_decoder"] = FastDecoder(model, -(-need // 256) * 256, batch=rows, **dataclasses.asdict(mode))
+        switches = dataclasses.asdict(mode)
+        if mode.decode_attention == CaptionMode.decode_attention:      # (said only where it is asked for: a decoder class with the
+            del switches["decode_attention"]                           # five-switch constructor goes on serving the default attention)
+        model.__dict__["_fast_decoder"] = FastDecoder(model, -(-need // 256) * 256, batch=rows, **switches)
     return model._fast_decoder
 
 
 def caption_tokens_fast(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
-                        prefill="torch", decode="valu"):
+                        prefill="torch", decode="valu", attention="valu"):
     """Multimodal prompt -> generated token ids through the model's ``FastDecoder`` (built once per model, cache size, weight mode,
-    prefill mode and decode kernel: asking for another mode rebuilds the decoder, its packs and its captured graph; ``_decoder_for``).
+    prefill mode, decode kernel and decode attention: asking for another mode rebuilds the decoder, its packs and its captured graph; ``_decoder_for``).
     It goes on using a decoder with more rows than one."""
-    mode = caption_mode(weights, prefill, decode, who="caption_tokens_fast")
+    mode = caption_mode(weights, prefill, decode, attention, who="caption_tokens_fast")
     embeds = model.multimodal_embeds(input_ids, images, image_sizes)
     dec = _decoder_for(model, embeds.shape[1] + max_new_tokens, 1, mode)
     return dec.generate(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids)
 
 
 def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tokens, do_sample, temperature, eos_ids=None, weights="native",
-                              seeds=None, prefill="torch", decode="valu"):
+                              seeds=None, prefill="torch", decode="valu", attention="valu"):
     """``caption_tokens_fast`` for several images under ONE prompt: ``images[b]`` / ``image_sizes[b]`` are the views and the size of image
     ``b`` -> a list of token tensors, each equal to ``caption_tokens_fast`` on that image alone (under ``seeds[b]``, see
     ``FastDecoder.generate_batch``).  The model's decoder is rebuilt when it cannot hold this many rows, for another mode, or for a
     longer cache (``_decoder_for``).  The cache length is this
     group's longest prompt plus the new tokens, rounded up to 256 (kept if the decoder's is longer); the prefill runs over it, so the equality
     with the single call holds where both prefill the image at the same cache length (the decode step does not depend on it) -- or, with
-    ``prefill="flash"``, at any cache length: that prefill does not depend on it either.  ``decode``: as in ``caption_tokens_fast``."""
-    mode = caption_mode(weights, prefill, decode, who="caption_tokens_fast_batch")
+    ``prefill="flash"``, at any cache length: that prefill does not depend on it either.  ``decode``, ``attention``: as in ``caption_tokens_fast``."""
+    mode = caption_mode(weights, prefill, decode, attention, who="caption_tokens_fast_batch")
     embeds = [model.multimodal_embeds(input_ids, im, [size]) for im, size in zip(images, image_sizes)]
     dec = _decoder_for(model, max(e.shape[1] for e in embeds) + max_new_tokens, len(embeds), mode)
     return dec.generate_batch(embeds, max_new_tokens, do_sample=do_sample, temperature=temperature, eos_token_id=eos_ids, seeds=seeds)
@@ -1226,7 +1259,7 @@ def caption_tokens_fast_batch(model, input_ids, images, image_sizes, max_new_tok
 def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv_templates=conv_templates,
                            image_token_index=IMAGE_TOKEN_INDEX, conv_template="llava_llama_3", num_beams=1, temperature=0.2,
                            do_sample=True, max_new_tokens=512, device="cuda", seeds=None, fast=None, decode_weights=None, decode_prefill=None,
-                           decode_kernel=None):
+                           decode_kernel=None, decode_attention=None):
     """``get_img_describe`` for a list of images (``image_tensors[b]``: the views of ``images[b]``) under one prompt -> a list of captions,
     caption ``b`` being what ``get_img_describe(image_tensors[b], images[b], ..., seed=seeds[b])[0]`` returns: with the FastDecoder the
     token loops of all images run as one (the decoder's weights are streamed once per step for all of them); without it the images
@@ -1235,11 +1268,12 @@ def get_img_describe_batch(image_tensors, images, model, tokenizer, prompt, conv
     if len(image_tensors) != n or (seeds is not None and len(seeds) != n):
         raise ValueError(f"get_img_describe_batch: {len(image_tensors)} view lists and {None if seeds is None else len(seeds)} seeds for {n} images")
     input_ids, _, use_fast, options = _describe_setup("get_img_describe_batch", model, tokenizer, prompt, conv_templates, image_token_index,
-                                                      conv_template, num_beams, device, fast, decode_weights, decode_prefill, decode_kernel)
+                                                      conv_template, num_beams, device, fast, decode_weights, decode_prefill, decode_kernel,
+                                                      decode_attention)
     if not use_fast or n > FastDecoder.MAX_BATCH:
         return [get_img_describe(image_tensors[b], images[b], model, tokenizer, prompt, conv_templates, image_token_index, conv_template,
                                  num_beams, temperature, do_sample, max_new_tokens, device, None if seeds is None else seeds[b], use_fast,
-                                 decode_weights, decode_prefill, decode_kernel)[0] for b in range(n)]
+                                 decode_weights, decode_prefill, decode_kernel, decode_attention)[0] for b in range(n)]
     with torch.no_grad():
         outs = caption_tokens_fast_batch(model, input_ids, image_tensors, [im.size for im in images], max_new_tokens, do_sample, temperature,
                                          _eos_ids(model, tokenizer), seeds=seeds, **options)

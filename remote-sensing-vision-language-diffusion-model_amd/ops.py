@@ -1416,8 +1416,16 @@ def gemv_fused(w, x, bias=None, *, norm=None, residual=None, glu=False):
     return _gemv_rows("gemv_fused", "gemv", w, None, x, bias, norm, residual, glu, w8=False, single=True)
 
 
-def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, single):
-    """``fn`` on ``B`` sequences with caches ``[B, n_kv, max_len, 128]``; ``single``: caches ``[n_kv, max_len, 128]``, one sequence."""
+DECODE_ATTENTION_KERNELS = ("valu", "mfma")    # the two decode-step attentions: da_kernel of csrc/gemv.hip / csrc/decode_attention_mma.hip
+
+
+def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, single, kernel="valu"):
+    """``fn`` on ``B`` sequences with caches ``[B, n_kv, max_len, 128]``; ``single``: caches ``[n_kv, max_len, 128]``, one sequence.
+    ``kernel="mfma"``: the same operands, checks and errors, launched through rsvld_llama_decode_attention_mma_rows (one sequence is its
+    ``B = 1`` call) under the launch name ``llama_decode_attention_mma_rows``, with that entry's own workspace size."""
+    if kernel not in DECODE_ATTENTION_KERNELS:
+        raise ValueError(f"{fn}: kernel={kernel!r}, expected one of {DECODE_ATTENTION_KERNELS}")
+    mma = kernel == "mfma"
     _arg(fn, "kcache", kcache, _HALF, shape=(n_kv, None, None) if single else (None, n_kv, None, None))
     hd, max_len = kcache.shape[-1], kcache.shape[-2]
     B = 1 if single else kcache.shape[0]
@@ -1436,26 +1444,26 @@ def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, sc
     _arg(fn, "ws", ws, torch.float32, shape=(None,), optional=True)
     _need_gpu(qkv, cos, sin, pos, kcache, vcache, ws)
     lib = L.load()
-    ws_n = int(lib.rsvld_llama_decode_attention_rows_ws_bytes(n_q, n_kv, max_len, B)) // 4
+    ws_n = int((lib.rsvld_llama_decode_attention_mma_rows_ws_bytes if mma else lib.rsvld_llama_decode_attention_rows_ws_bytes)(n_q, n_kv, max_len, B)) // 4
     if ws is None:
         ws = torch.empty(ws_n, device=qkv.device, dtype=torch.float32)
     elif ws.numel() < ws_n:
         _bad(fn, "ws", f"has {ws.numel()} fp32 elements, the step needs {ws_n}")
     out = torch.empty(n_q * hd if single else (B, n_q * hd), device=qkv.device, dtype=qkv.dtype)
-    entry = "rsvld_llama_decode_attention" if single else "rsvld_llama_decode_attention_rows"
+    entry = "rsvld_llama_decode_attention_mma_rows" if mma else "rsvld_llama_decode_attention" if single else "rsvld_llama_decode_attention_rows"
     args = (_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(ws), n_q, n_kv, hd, max_len)
-    args += (float(scale), _dt(qkv), _stream()) if single else (B, float(scale), _dt(qkv), _stream())
+    args += (float(scale), _dt(qkv), _stream()) if single and not mma else (B, float(scale), _dt(qkv), _stream())
     call = getattr(lib, entry)
-    _launch(fn, 0.0, 0.0, lambda: L.check(call(*args), entry))
+    _launch("llama_decode_attention_mma_rows" if mma else fn, 0.0, 0.0, lambda: L.check(call(*args), entry))
     return out
 
 
-def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None):
+def llama_decode_attention(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws=None, kernel="valu"):
     """One decode step of grouped-query attention over a static cache (rsvld_llama_decode_attention): ``qkv`` = the new token's q | k | v rows,
     ``pos`` a DEVICE int64 scalar; the caches ``[n_kv, max_len, 128]`` are updated at ``pos``; ``ws`` (optional, re-usable): an fp32
     tensor of rsvld_llama_decode_attention_ws_bytes (scratch: no initial state).  A position outside ``[0, max_len)`` is clamped by the kernel.
-    -> ``[n_q * 128]``.  ``decode_rows.llama_decode_attention_rows`` on one sequence."""
-    return _decode_attention_rows("llama_decode_attention", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, True)
+    -> ``[n_q * 128]``.  ``decode_rows.llama_decode_attention_rows`` on one sequence; ``kernel``: as there."""
+    return _decode_attention_rows("llama_decode_attention", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, True, kernel)
 
 
 def _prefill_attention(fn, q, kcache, vcache, n_q, n_kv, scale, pos0):

@@ -9,7 +9,7 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "remote-sensing-vision-language-diffusion-model_amd", "csrc")
 UNITS = {"conv_igemm.hip": [], "conv_halo.hip": [], "gemm.hip": [], "split.hip": ["-fno-slp-vectorize"],
-         "prefill_attention.hip": ["-fno-slp-vectorize"], "gemm_w8.hip": []}
+         "prefill_attention.hip": ["-fno-slp-vectorize"], "gemm_w8.hip": [], "decode_attention_mma.hip": []}
 # kernels allowed a few scratch instructions OUTSIDE their loops (none today); name fragment -> max count
 ALLOW = {}
 
