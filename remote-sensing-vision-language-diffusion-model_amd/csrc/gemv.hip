@@ -1,4 +1,5 @@
 // gemv.hip -- y[b][n] = sum_k W[n][k] x[b][k] (+ bias[n]) for B = 1 .. RSVLD_DECODE_MAX_ROWS activation rows: the weight-streaming products
+// (16-bit weights, or e4m3 bytes with a scale per row and the quantiser that makes them, pack_rows_e4m3_kernel)
 // of the caption pass's token loop (reference: models/util.py:17-66 -> llava/model/language_model/llava_llama.py:118-137 -> Llama decode;
 // 7 linear layers per decoder layer and the 128 256-row lm_head with M = 1; B > 1: the batched token loop).  One host path -- one validation,
 // one launcher -- behind the four entry points, the single-row ones being its B = 1 call; one row runs gemv_kernel / gemv_w8_kernel, two and
@@ -12,7 +13,6 @@
 // of 16 rows, ONE per CU with 32 KiB of weight loads in flight where ~64 KiB per CU are needed to keep HBM busy) run with the four waves
 // of a workgroup SPLITTING K for the same GV_RPW rows: four times the workgroups, partial sums through LDS.
 #include "rsvld_common.h"
-#include "decode_attention.h"   // da_rope, DA_HD, DA_GMAX, DA_PART, rsvld_da_combine_launch: shared with decode_attention_mma.hip
 #include <type_traits>
 
 namespace {
@@ -256,180 +256,6 @@ __global__ __launch_bounds__(64 * GV_WAVES) void pack_rows_e4m3_kernel(const T* 
     }
 }
 
-// ---- one decode step of grouped-query attention over a static key / value cache (rsvld_llama_decode_attention): rotary embedding of the
-// new q and k (half-split form), the cache write at ``pos``, scores, softmax and P V for the G = n_q / n_kv query heads that share a
-// kv head.  Workgroup (kv head, chunk of DA_CH keys): every thread requests its pieces of the chunk's K and V rows FIRST (the cache of a
-// 32-layer decoder does not stay in L2 between steps: one memory latency per launch, not one per key), the rows go to LDS, then scores,
-// chunk maximum / exponentials / sum per head and the partial output [G][128] with its (m, l) into the workspace; da_combine_kernel
-// folds the chunks.  pos is read
-// from DEVICE memory (the step is replayed from a hipGraph): chunks beyond it write l = 0.  head_dim = 128.
-constexpr int DA_CH = 128;   // keys per workgroup: 8 kv heads x 26 chunks = 208 workgroups at the caption's ~3 300 keys
-constexpr int DA_ROW = DA_HD * 2 + 16;                 // LDS row stride in bytes: four rows read by one wave instruction fall into different banks
-constexpr int DA_PIECES = DA_CH * 16 / 256;            // 16-byte pieces of the K (and of the V) chunk per thread
-
-// sum over the 16 lanes of a DPP row, in every lane: four cross-lane VALU steps (quad swaps, half-row and row mirrors) where
-// __shfl_xor would be four dependent ds_bpermute round trips -- 16 of them per key group and wave made the score phase the kernel's longest
-__device__ __forceinline__ float da_row16_sum(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});     // quad_perm [1, 0, 3, 2]
-    v += dpp(v, std::integral_constant<int, 0x4E>{});     // quad_perm [2, 3, 0, 1]
-    v += dpp(v, std::integral_constant<int, 0x141>{});    // row_half_mirror
-    v += dpp(v, std::integral_constant<int, 0x140>{});    // row_mirror
-    return v;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void da_kernel(const T* __restrict__ qkv, const T* __restrict__ cosv, const T* __restrict__ sinv,
-                                                 const long long* __restrict__ pos_p, T* __restrict__ kc, T* __restrict__ vc,
-                                                 float* __restrict__ ws, int n_q, int n_kv, int max_len, float scale) {
-    __shared__ __attribute__((aligned(16))) char ks[DA_CH * DA_ROW], vs[DA_CH * DA_ROW];
-    __shared__ float qs[DA_GMAX][DA_HD];        // rotated queries of this kv head's group
-    __shared__ float sc[DA_GMAX][DA_CH];        // scores, then exp(s - m)
-    __shared__ float ml[DA_GMAX][2];
-    const int kvh = blockIdx.x, c = blockIdx.y, nchunk = gridDim.y;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // blockIdx.z: the sequence (rsvld_llama_decode_attention_rows; one sequence = the single entry point).  Every operand of a sequence is a
-    // whole slice, so the code below is the single-sequence step on offset pointers: no byte of another sequence is read or written.
-    const size_t seq = blockIdx.z;
-    qkv += seq * (size_t)(n_q + 2 * n_kv) * DA_HD;
-    cosv += seq * DA_HD;
-    sinv += seq * DA_HD;
-    kc += seq * (size_t)n_kv * max_len * DA_HD;
-    vc += seq * (size_t)n_kv * max_len * DA_HD;
-    ws += seq * (size_t)n_q * nchunk * (DA_HD + 2);
-    const int G = n_q / n_kv, p = (int)min(max(pos_p[seq], 0ll), (long long)max_len - 1), half = DA_HD / 2;   // (a position outside the cache is clamped, never written past it)
-    float* out = ws + ((size_t)(kvh * nchunk + c) * G) * (DA_HD + 2);
-    const int j0 = c * DA_CH, nkeys = min(DA_CH, p + 1 - j0);
-    const bool owner = p >= j0 && p < j0 + DA_CH;
-    if (nkeys > 0) {
-        // ---- the chunk's rows: all requests of a thread in flight at once (rows past the prefix re-read its last row: finite, masked below)
-        u32x4 kr[DA_PIECES], vr[DA_PIECES];
-#pragma unroll
-        for (int i = 0; i < DA_PIECES; ++i) {
-            const int pc = tid + 256 * i, row = min(pc >> 4, nkeys - 1), col = pc & 15;
-            const size_t off = ((size_t)kvh * max_len + j0 + row) * DA_HD + col * 8;
-            kr[i] = *(const u32x4*)(kc + off);
-            vr[i] = *(const u32x4*)(vc + off);
-        }
-        auto rope = [&](const T* src, int i) { return da_rope(src, cosv, sinv, half, i); };   // (decode_attention.h)
-        for (int i = tid; i < G * DA_HD; i += 256) qs[i / DA_HD][i % DA_HD] = rope(qkv + (size_t)(kvh * G + i / DA_HD) * DA_HD, i % DA_HD);
-#pragma unroll
-        for (int i = 0; i < DA_PIECES; ++i) {
-            const int pc = tid + 256 * i;
-            *(u32x4*)(ks + (pc >> 4) * DA_ROW + (pc & 15) * 16) = kr[i];
-            *(u32x4*)(vs + (pc >> 4) * DA_ROW + (pc & 15) * 16) = vr[i];
-        }
-        __syncthreads();
-        if (owner && tid < DA_HD) {   // the new token's key (rotated) and value: into the cache AND over the (stale) row of the LDS image
-            const T kn = (T)rope(qkv + (size_t)(n_q + kvh) * DA_HD, tid), vn = qkv[(size_t)(n_q + n_kv + kvh) * DA_HD + tid];
-            kc[((size_t)kvh * max_len + p) * DA_HD + tid] = kn;
-            vc[((size_t)kvh * max_len + p) * DA_HD + tid] = vn;
-            ((T*)(ks + (p - j0) * DA_ROW))[tid] = kn;
-            ((T*)(vs + (p - j0) * DA_ROW))[tid] = vn;
-        }
-        __syncthreads();
-        // ---- scores: a wave takes four keys per step, 16 lanes x 16 bytes per key row
-        const int sub = lane >> 4, l16 = lane & 15;
-        for (int jj = wv * (DA_CH / 4); jj < (wv + 1) * (DA_CH / 4); jj += 4) {
-            const int j = jj + sub;
-            float kf[8];
-            unpack8<T>(*(const u32x4*)(ks + j * DA_ROW + l16 * 16), kf);
-            for (int g = 0; g < G; ++g) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d = __builtin_fmaf(kf[e], qs[g][l16 * 8 + e], d);
-                d = da_row16_sum(d);
-                if (l16 == 0) sc[g][j] = j < nkeys ? (float)(T)d * scale : -INFINITY;    // (the unfused path holds the scores in T)
-            }
-        }
-        __syncthreads();
-        for (int g = wv; g < G; g += 4) {          // chunk maximum, exponentials, sum: one wave per head
-            constexpr int PER = DA_CH / 64;
-            float v[PER], m = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < PER; ++i) { v[i] = sc[g][lane + 64 * i]; m = fmaxf(m, v[i]); }
-            m = wave_max(m);
-            float l = 0.f;
-#pragma unroll
-            for (int i = 0; i < PER; ++i) { v[i] = __expf(v[i] - m); l += v[i]; sc[g][lane + 64 * i] = v[i]; }
-            l = wave_sum(l);
-            if (lane == 0) { ml[g][0] = m; ml[g][1] = l; }
-        }
-        __syncthreads();
-        // ---- P V: wave = head (groups of four); four value rows per LDS instruction, each lane its eight channels over the keys of its quarter
-        for (int g = wv; g < G; g += 4) {
-            float acc[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-            for (int jb = 0; jb < nkeys; jb += 4) {
-                const int j = jb + sub;
-                float vf[8];
-                unpack8<T>(*(const u32x4*)(vs + j * DA_ROW + l16 * 16), vf);     // (rows past nkeys: copies of the last row, weight exp(-inf) = 0)
-                const float pw = sc[g][j];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] = __builtin_fmaf(pw, vf[e], acc[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                acc[e] += __shfl_xor(acc[e], 16);
-                acc[e] += __shfl_xor(acc[e], 32);
-            }
-            float* o = out + (size_t)g * (DA_HD + 2);
-            if (sub == 0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[l16 * 8 + e] = acc[e];
-            }
-            if (lane == 0) { o[DA_HD] = ml[g][0]; o[DA_HD + 1] = ml[g][1]; }
-        }
-    } else {                                   // nothing of this chunk is visible yet
-        for (int i = tid; i < G * (DA_HD + 2); i += 256) out[i] = (i % (DA_HD + 2)) == DA_HD ? -INFINITY : 0.f;
-    }
-}
-
-// folds the chunks of one query head: out = sum_c exp(m_c - M) acc_c / sum_c exp(m_c - M) l_c.  (A second launch, not a "last workgroup"
-// ticket inside da_kernel: the partials of one head are written on several XCDs, and making them visible to one another inside a launch
-// costs every workgroup an L2 write-back -- measured 41 us per call against 21 + 13 for two launches.)  The chunk loop is unrolled so that
-// its loads are in flight together: one L2 latency, not one per chunk.
-template <typename T>
-__global__ __launch_bounds__(DA_HD) void da_combine_kernel(const float* __restrict__ ws, T* __restrict__ out, int n_q, int n_kv, int nchunk) {
-    __shared__ float wsh[64];
-    const int h = blockIdx.x, G = n_q / n_kv, kvh = h / G, g = h % G, d = threadIdx.x;
-    ws += (size_t)blockIdx.y * n_q * nchunk * (DA_HD + 2);     // blockIdx.y: the sequence, as in da_kernel
-    out += (size_t)blockIdx.y * n_q * DA_HD;
-    const float* base = ws + ((size_t)kvh * nchunk * G + g) * (DA_HD + 2);
-    const size_t cs = (size_t)G * (DA_HD + 2);
-    float l = 0.f, acc = 0.f;
-    for (int c0 = 0; c0 < nchunk; c0 += 64) {              // (<= 64 chunks per round: 8 192 keys)
-        const int nc = min(64, nchunk - c0);
-        float mc = -INFINITY, lc = 0.f;
-        if (d < nc) { mc = base[(c0 + d) * cs + DA_HD]; lc = base[(c0 + d) * cs + DA_HD + 1]; }
-        // running maximum across rounds is not needed for <= 64 chunks; for more, rescale
-        const float Mr = wave_max(d < 64 ? mc : -INFINITY);
-        __shared__ float Msh, Lsh, Ash;
-        if (d == 0) { Msh = Mr; }
-        __syncthreads();
-        const float wgt = (d < nc && mc != -INFINITY) ? __expf(mc - Msh) : 0.f;
-        if (d < 64) wsh[d] = wgt;
-        const float lsum = wave_sum(d < 64 ? wgt * lc : 0.f);
-        if (d == 0) Lsh = lsum;
-        __syncthreads();
-        float a = 0.f;
-#pragma unroll 8
-        for (int c = 0; c < nc; ++c) a = __builtin_fmaf(wsh[c], base[(c0 + c) * cs + d], a);
-        if (c0 == 0) { acc = a; l = Lsh; Ash = Msh; }
-        else {   // a later round: bring both to the larger maximum
-            const float Mo = Ash, Mn = fmaxf(Mo, Msh), so = __expf(Mo - Mn), sn = __expf(Msh - Mn);
-            acc = acc * so + a * sn; l = l * so + Lsh * sn;
-            __syncthreads();
-            if (d == 0) Ash = Mn;
-        }
-        __syncthreads();
-    }
-    out[(size_t)h * DA_HD + d] = (T)(acc / l);
-}
-
 // ---- the same products for NB activation rows at once (rsvld_gemv_rows_fused, rsvld_gemv_w8_rows_fused): the batched token loop streams a
 // weight piece ONCE into registers and uses it for every row.  Per activation row the arithmetic is gemv_kernel's / gemv_w8_kernel's, operation
 // for operation: the row is staged by gv_stage_x (its own K elements of LDS), lane l of a wave accumulates the same k in the same ascending
@@ -664,49 +490,4 @@ extern "C" int rsvld_gemv_fused(const void* w, const void* x, const void* bias, 
 extern "C" int rsvld_gemv_w8_fused(const void* q, const float* scale, const void* x, const void* bias, const void* norm_w, float norm_eps,
                                    const void* residual, int glu, void* y, int N, int K, int dtype, void* stream) {
     return rsvld_gemv_w8_rows_fused(q, scale, x, bias, norm_w, norm_eps, residual, glu, y, N, K, 1, dtype, stream);
-}
-
-// ---- the decode attention for B sequences (da_kernel takes the sequence from blockIdx.z); one sequence is the B = 1 call
-extern "C" size_t rsvld_llama_decode_attention_rows_ws_bytes(int n_q, int n_kv, int max_len, int B) {
-    if (n_q <= 0 || n_kv <= 0 || max_len <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return 0;
-    return (size_t)B * n_q * ((max_len + DA_CH - 1) / DA_CH) * (DA_HD + 2) * sizeof(float);
-}
-
-extern "C" size_t rsvld_llama_decode_attention_ws_bytes(int n_q, int n_kv, int max_len) {
-    return rsvld_llama_decode_attention_rows_ws_bytes(n_q, n_kv, max_len, 1);
-}
-
-extern "C" int rsvld_llama_decode_attention_rows(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
-                                                 void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, int B, float scale, int dtype,
-                                                 void* stream) {
-    if (!qkv || !cosv || !sinv || !pos || !kcache || !vcache || !out || !ws) return RSVLD_EINVAL;
-    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16) return RSVLD_EINVAL;
-    if (n_q <= 0 || n_kv <= 0 || max_len <= 0 || B < 1 || B > RSVLD_DECODE_MAX_ROWS) return RSVLD_EINVAL;
-    if (head_dim != DA_HD || n_q % n_kv != 0 || n_q / n_kv > DA_GMAX) return RSVLD_EUNSUPPORTED;
-    if (((uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)qkv) & 15) return RSVLD_EINVAL;
-    const int nchunk = (max_len + DA_CH - 1) / DA_CH;
-    hipStream_t s = (hipStream_t)stream;
-    by_dtype(dtype, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL((da_kernel<T>), dim3(n_kv, nchunk, B), dim3(256), 0, s, (const T*)qkv, (const T*)cosv, (const T*)sinv,
-                           (const long long*)pos, (T*)kcache, (T*)vcache, ws, n_q, n_kv, max_len, scale);
-        hipLaunchKernelGGL((da_combine_kernel<T>), dim3(n_q, B), dim3(DA_HD), 0, s, ws, (T*)out, n_q, n_kv, nchunk);
-        return 0;
-    });
-    return rsvld_check_launch();
-}
-
-// da_combine_kernel for the MFMA form of the step (decode_attention_mma.hip), whose partials have da_kernel's layout
-void rsvld_da_combine_launch(const float* ws, void* out, int n_q, int n_kv, int nchunk, int B, int dtype, hipStream_t stream) {
-    by_dtype(dtype, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL((da_combine_kernel<T>), dim3(n_q, B), dim3(DA_HD), 0, stream, ws, (T*)out, n_q, n_kv, nchunk);
-        return 0;
-    });
-}
-
-extern "C" int rsvld_llama_decode_attention(const void* qkv, const void* cosv, const void* sinv, const int64_t* pos, void* kcache, void* vcache,
-                                            void* out, float* ws, int n_q, int n_kv, int head_dim, int max_len, float scale, int dtype,
-                                            void* stream) {
-    return rsvld_llama_decode_attention_rows(qkv, cosv, sinv, pos, kcache, vcache, out, ws, n_q, n_kv, head_dim, max_len, 1, scale, dtype, stream);
 }

@@ -5,8 +5,9 @@
 // House style of attention.hip's attn_d64b: S^T = K Q^T "swapped" (keys on the accumulator registers, the query row on the lane), so the
 // online softmax is register-local (one exchange with lane ^ 32) and the converted score tile is the B operand of O^T += V^T P^T in
 // place; K and V tiles of 64 keys go through a double-buffered LDS ring filled by LDS-DMA alone, K is read row-wise (ds_read_b128), V
-// through the hardware transpose (ds_read_b64_tr_b16), both images XOR-swizzled on the DMA's source side; one barrier per tile.  What
-// is different here:
+// through the hardware transpose (ds_read_b64_tr_b16), both images XOR-swizzled on the DMA's source side; one barrier per tile.  The
+// tile layout, its swizzles, the Q fragments and the register -> key map are attention_d128.h's, shared with the decode step (dam_kernel);
+// the tile walk, the double buffering and the online softmax (exp2) are this kernel's.  What is different from attn_d64b:
 //   * rows are (position, head-in-group) pairs of ONE kv head in the [T g] order FastDecoder.forward forms: row r = t g + j is query head
 //     kvh g + j at position pos0 + t.  A workgroup (4 waves x 32 rows) owns 128 such rows, so one K / V tile serves all g query heads;
 //   * causal: a workgroup walks key tiles 0 .. (its last position) / 64 in ascending order on absolute 64-key boundaries, a wave skips
@@ -18,6 +19,7 @@
 // fragment registers (0 x NaN would be NaN) and K / V rows above the call's last position are never even requested.
 #include "rsvld_common.h"
 #include "rsvld_plan.h"
+#include "attention_d128.h"
 
 namespace {
 
@@ -31,16 +33,12 @@ struct PrefillArgs {
     float scale_log2e;
 };
 
-typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-
-constexpr int PA_TILE = 64 * 256;   // 64 keys x 128 d, 16-bit
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p) {
     constexpr int D = 128;
     typedef typename Mfma<T>::v8 v8;
     typedef typename Mfma<T>::v4 v4;
-    __shared__ __attribute__((aligned(16))) char smem[4 * PA_TILE];   // K[2] | V[2]
+    __shared__ __attribute__((aligned(16))) char smem[4 * A128_TILE];   // K[2] | V[2]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
@@ -60,23 +58,19 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
     const T* Kb = (const T*)p.k + (int64_t)kvh * p.max_len * D;
     const T* Vb = (const T*)p.v + (int64_t)kvh * p.max_len * D;
 
-    // ---- tile DMA.  Wave w moves key rows 16 w .. 16 w + 15 of the tile: 4 wave-instructions of 4 rows x 256 B per tensor.  Lane (row =
-    // lane >> 4, pos = lane & 15) of piece i fills LDS chunk `pos` of tile row r = 16 w + 4 i + row with source chunk pos ^ (r & 15) for K
-    // (16 rows of a ds_read_b128 wavefront quarter land in 16 distinct 16-byte positions of the 256-byte bank period) and
-    // pos ^ ((r & 3) << 2) for V (the four rows of a transposed read land in four distinct 64-byte quarters).
+    // ---- tile DMA (attention_d128.h): tile t goes to buffer t & 1; nothing above klast is requested
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
     uint32_t kvo[4], vvo[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int rr = 4 * i + (lane >> 4);
-        kvo[i] = (uint32_t)(rr * 256) + (uint32_t)(((lane & 15) ^ rr) << 4);
-        vvo[i] = (uint32_t)(rr * 256) + (uint32_t)(((lane & 15) ^ ((rr & 3) << 2)) << 4);
+        kvo[i] = (uint32_t)(rr * 256) + (uint32_t)a128_k_swz(lane, rr);
+        vvo[i] = (uint32_t)(rr * 256) + (uint32_t)a128_v_swz(lane, rr);
     }
-    // LDS-DMA pieces: rsvld_lds_dma16 / _addr, M0 (the LDS destination) saved and restored, as attn_d64b does
     auto dma_tile = [&](int t) {
         const int buf = t & 1;
-        const uint32_t kd = lds0 + buf * PA_TILE + wu * 4096, vd = kd + 2 * PA_TILE;
+        const uint32_t kd = lds0 + buf * A128_TILE + wu * 4096, vd = kd + 2 * A128_TILE;
         if (t * 64 + 63 <= klast) {
             const char* kb = (const char*)(Kb + (int64_t)(t * 64 + wu * 16) * D);
             const char* vb = (const char*)(Vb + (int64_t)(t * 64 + wu * 16) * D);
@@ -85,13 +79,13 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
                 rsvld_lds_dma16(kb, kvo[i], kd + i * 1024);
                 rsvld_lds_dma16(vb, vvo[i], vd + i * 1024);
             }
-        } else {   // rows above klast re-read key klast (< max_len); their scores are masked and their V rows zeroed
+        } else {   // rows above klast re-read key klast (< max_len)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int rr = 4 * i + (lane >> 4);
                 const int key = min(t * 64 + wu * 16 + rr, klast);
-                rsvld_lds_dma16_addr((const char*)(Kb + (int64_t)key * D) + (((lane & 15) ^ rr) << 4), kd + i * 1024);
-                rsvld_lds_dma16_addr((const char*)(Vb + (int64_t)key * D) + (((lane & 15) ^ ((rr & 3) << 2)) << 4), vd + i * 1024);
+                rsvld_lds_dma16_addr((const char*)(Kb + (int64_t)key * D) + a128_k_swz(lane, rr), kd + i * 1024);
+                rsvld_lds_dma16_addr((const char*)(Vb + (int64_t)key * D) + a128_v_swz(lane, rr), vd + i * 1024);
             }
         }
     };
@@ -100,8 +94,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
     // ---- Q fragments (B operand: col = the row on the lane, k = d)
     const T* Qr = (const T*)p.q + (int64_t)tq * p.q_ts + (int64_t)hq * D;
     v8 qf[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) qf[ks] = __builtin_bit_cast(v8, *(const u32x4*)(Qr + ks * 16 + lh * 8));
+    a128_load_q<T>(Qr, lh, qf);
     f32x16 oacc[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -109,23 +102,17 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;   // (tile 0 holds key 0, which every row attends: m_run is finite from there on)
 
-    // per-lane read offsets.  K (ds_read_b128): row kt 32 + l31, chunk 2 ks + lh, swizzled by row & 15 = l31 & 15
-    int koff[8];
+    // per-lane read offsets, kept over the loop: K of row kt 32 + l31, V of the 16-key group s4 at + s4 * 4096
+    int koff[8], voff[4];
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) koff[ks] = l31 * 256 + (((2 * ks + lh) ^ (l31 & 15)) << 4);
-    // V (transposed read): lane 16 g1 + 4 qq + pp supplies row 16 s4 + 8 hf + 4 lh + qq, d = 32 dt + 16 (g1 & 1) + 4 pp .. + 3
-    int voff[4];
-    {
+    for (int ks = 0; ks < 8; ++ks) koff[ks] = a128_k_off(l31, lh, ks);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {   // V (attention_d128.h: the transposed read)
         const int qq = (lane >> 2) & 3, pp = lane & 3, g1 = (lane >> 4) & 1;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-            voff[dt] = 2 * PA_TILE + (4 * lh + qq) * 256 + ((dt ^ qq) << 6) + ((2 * g1 + (pp >> 1)) << 4) + ((pp & 1) << 3);
+        voff[dt] = 2 * A128_TILE + (4 * lh + qq) * 256 + ((dt ^ qq) << 6) + ((2 * g1 + (pp >> 1)) << 4) + ((pp & 1) << 3);
     }
 
-    // the Q fragments are consumed here, so that hipcc's wait for their loads does not land inside the loop (see attn_d64b)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) asm volatile("" : "+v"(qf[ks]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    a128_pin_q(qf);    // (the wait for the Q loads stays out of the loop)
     __syncthreads();   // tile 0 landed
 
     for (int t = 0; t < nt; ++t) {
@@ -133,8 +120,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
         // tile t + 1 goes to the buffer tile t - 1 was read from, i.e. before the last barrier
         if (t + 1 < nt) dma_tile(t + 1);
         if (wave_on && t * 64 <= p_max) {   // (wave-uniform) else: every key of the tile lies above every row of this wave
-            const char* Ks = smem + buf * PA_TILE;
-            const int vb = buf * PA_TILE;
+            const char* Ks = smem + buf * A128_TILE;
+            const int vb = buf * A128_TILE;
             // ---- S^T[key][row]: two 32-key halves x 8 k-steps
             f32x16 sacc[2];
 #pragma unroll
@@ -159,8 +146,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int key = t * 64 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (key > my_pos) sacc[kt][r] = -INFINITY;
+                        if (t * 64 + kt * 32 + a128_key(r, lh) > my_pos) sacc[kt][r] = -INFINITY;
                     }
             }
             // ---- online softmax, register-local (this lane: 32 of its row's 64 scores, lane ^ 32 the rest)
@@ -193,8 +179,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
             for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[s4][j] = (T)sacc[s4 >> 1][8 * (s4 & 1) + j];
-            // ---- O^T[d][row] += V^T P^T.  A operand (row = d, k = key in P's register order): elements 0..3 = keys 16 s4 + 4 lh + 0..3,
-            // elements 4..7 = keys 16 s4 + 8 + 4 lh + 0..3
+            // ---- O^T[d][row] += V^T P^T
             const bool vclean = t * 64 + 63 > p_max;   // (wave-uniform) the tile holds keys above every row of this wave: their V rows -> 0
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4)
@@ -202,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_d128_kernel(PrefillArgs p
                 for (int dt = 0; dt < 4; ++dt) {
                     const int off = vb + voff[dt] + s4 * 4096;
                     s16x8 vv = tr16_pair<s16x8>(lds_read_tr16(smem + off), lds_read_tr16(smem + off + 2048));
-                    if (vclean) {
+                    if (vclean) {   // (in place, not in a function of attention_d128.h: see there)
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
                             if (t * 64 + 16 * s4 + 8 * (j >> 2) + 4 * lh + (j & 3) > p_max) vv[j] = 0;

@@ -371,7 +371,7 @@ inline int plan_prefill_attention(int T, int n_q, int n_kv, int head_dim, rsvld_
 }
 
 // ---------------------------------------------------------------------------------------
-// the decode-step attention on MFMAs (decode_attention_mma.hip): a workgroup owns (sequence, kv head, one range of DAM_RANGE keys on
+// the decode-step attention on MFMAs (dam_kernel of decode_attention.hip): a workgroup owns (sequence, kv head, one range of DAM_RANGE keys on
 // absolute boundaries); its DAM_WAVES waves take DAM_RANGE / DAM_WAVES consecutive keys each.  DAM_RANGE is a constant -- no function
 // of the number of sequences, of max_len or of a position -- so the key order of a sequence's sum is the same in every call; max_len
 // only decides how many ranges there are (those above the position write neutral partials).  The number of sequences is no argument.

@@ -35,10 +35,18 @@ def llama_decode_attention_rows(qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, s
     * 128]``, ``cos`` / ``sin [B, 128]``, ``pos [B]`` DEVICE int64, caches ``[B, n_kv, max_len, 128]`` updated at ``pos[b]`` in sequence
     ``b``'s slice only; ``ws`` (optional, re-usable): fp32, ``B`` times the single workspace.  -> ``[B, n_q * 128]``.
     ``kernel="mfma"`` (opt-in, ``ops.DECODE_ATTENTION_KERNELS``): the attention on MFMAs (rsvld_llama_decode_attention_mma_rows,
-    csrc/decode_attention_mma.hip; launch name ``llama_decode_attention_mma_rows``), at every ``B`` including 1: the caches end bit for
+    csrc/decode_attention.hip; launch name ``llama_decode_attention_mma_rows``), at every ``B`` including 1: the caches end bit for
     bit as "valu" leaves them, sequence ``b``'s output is bit-identical among ITS ``B``, ``max_len`` and neighbours, not to "valu" (fp32
-    scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P); ``ws`` then has rsvld_llama_decode_attention_mma_rows_ws_bytes."""
+    scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P); ``ws``: ``decode_attention_ws_floats`` of the kernel."""
     return ops._decode_attention_rows("llama_decode_attention_rows", qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, False, kernel)
+
+
+def decode_attention_ws_floats(n_q, n_kv, max_len, B, kernel="valu"):
+    """fp32 elements of the workspace one step of ``B`` sequences needs with ``kernel`` (rsvld_llama_decode_attention_rows_ws_bytes /
+    rsvld_llama_decode_attention_mma_rows_ws_bytes): the one place that picks the symbol."""
+    lib = L.load()
+    ws_bytes = lib.rsvld_llama_decode_attention_mma_rows_ws_bytes if kernel == "mfma" else lib.rsvld_llama_decode_attention_rows_ws_bytes
+    return int(ws_bytes(int(n_q), int(n_kv), int(max_len), int(B))) // 4
 
 
 def plan_decode_attention_mma(n_q, n_kv, max_len, dtype=None):

@@ -75,7 +75,7 @@ class PipelineConfig:
     caption_weights: str = "native"   # weights of the caption pass's token loop: "native" = the checkpoint's 16-bit ones, "e4m3" = e4m3 bytes + a scale per row (opt-in, rsvld_amd.w8), "e4m3-only" = the prefill on them too and the 16-bit decoder weights released (llava_next.CAPTION_WEIGHTS)
     caption_prefill: str = "torch"    # attention of the caption pass's prefill: "torch" = the stock-torch sequence over the whole cache, "flash" = the causal flash kernel (opt-in, rsvld_amd.prefill_attention)
     caption_decode: str = "valu"      # kernels of the token loop's products: "valu" = the vector-ALU ones, "mfma" = on MFMAs, whose arithmetic does not grow with --caption_batch (opt-in, csrc/gemv_mma.hip; llava_next.CAPTION_DECODES)
-    caption_attention: str = "valu"   # attention of the token loop: "valu" = da_kernel on the vector ALU, "mfma" = key tiles by LDS-DMA, scores and P V on MFMAs (opt-in, csrc/decode_attention_mma.hip; llava_next.CAPTION_ATTENTIONS)
+    caption_attention: str = "valu"   # attention of the token loop: "valu" = da_kernel on the vector ALU, "mfma" = key tiles by LDS-DMA, scores and P V on MFMAs (opt-in, dam_kernel of csrc/decode_attention.hip; llava_next.CAPTION_ATTENTIONS)
 
     def __post_init__(self):
         caption_mode(self.caption_weights, self.caption_prefill, self.caption_decode, self.caption_attention, who="PipelineConfig",

@@ -49,7 +49,7 @@ DEFAULT_ADAPTER = "./CKPT_PTH/Llava-next"           # models/util.py:115
 # release_native=True).  Decodes: "valu" runs the weight-streaming products on the vector ALU (csrc/gemv.hip); "mfma" (opt-in) on MFMAs
 # (csrc/gemv_mma.hip), whose arithmetic does not grow with the captions of a batch.  The two sum in different orders: other logits, the
 # same contract each.  A fourth switch, caption_attention / --caption_attention / decode_attention / attention, picks the token loop's
-# ATTENTION: "valu" is da_kernel of csrc/gemv.hip, "mfma" (opt-in) csrc/decode_attention_mma.hip -- key tiles by LDS-DMA, scores and P V
+# ATTENTION: "valu" is da_kernel of csrc/decode_attention.hip, "mfma" (opt-in) dam_kernel of the same unit -- key tiles by LDS-DMA, scores and P V
 # on MFMAs, fp32 scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P: other logits again, the same caches.
 CAPTION_WEIGHTS = ("native", "e4m3", "e4m3-only")
 CAPTION_PREFILLS = ("torch", "flash")
@@ -440,8 +440,8 @@ class FastDecoder:
     either.  Attention, the prefill and sampling are untouched; it combines with every other switch.  The mode needs the fused decode
     step (``_fused_ok``); where that fails the decoder raises -- it never falls back to "valu" or to torch silently.
 
-    ``decode_attention``: "valu" (default) runs the decode step's attention through da_kernel (csrc/gemv.hip).  "mfma" (opt-in) sends it
-    through csrc/decode_attention_mma.hip (``decode_rows.llama_decode_attention_rows(..., kernel="mfma")``) at EVERY row count,
+    ``decode_attention``: "valu" (default) runs the decode step's attention through da_kernel (csrc/decode_attention.hip).  "mfma" (opt-in) sends it
+    through dam_kernel of the same unit (``decode_rows.llama_decode_attention_rows(..., kernel="mfma")``) at EVERY row count,
     ``generate``'s single row included, so that inside the mode ``generate_batch`` still equals ``generate`` per prompt: key and value
     tiles by LDS-DMA, scores and P V on MFMAs, fp32 scores and a 16-bit P where "valu" has 16-bit scores and an fp32 P -- other logits,
     the same cache rows bit for bit.  It combines with every other switch and, like ``decode="mfma"``, needs the fused decode step
@@ -865,9 +865,7 @@ class FastDecoder:
             # ONE workspace for the decoder's life, sized for ``batch`` rows: the captured steps of ``_rows`` hold its address, so it is
             # never replaced (a buffer grown per row count would be freed under the graphs captured with fewer rows, ``_graph`` among
             # them).  Per-chunk partial results: written before they are read, no initial state.
-            lib = DR.ops.L.load()
-            ws_bytes = lib.rsvld_llama_decode_attention_mma_rows_ws_bytes if self.decode_attention == "mfma" else lib.rsvld_llama_decode_attention_rows_ws_bytes
-            need = int(ws_bytes(self.n_q, self.n_kv, self.max_len, self.batch)) // 4
+            need = DR.decode_attention_ws_floats(self.n_q, self.n_kv, self.max_len, self.batch, self.decode_attention)
             self._ws_rows = torch.empty(need, device=self.dev, dtype=torch.float32)
         gemv = self._step_product
         for i, (layer, w) in enumerate(zip(self.layers, self.table)):

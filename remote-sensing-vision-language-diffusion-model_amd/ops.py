@@ -1416,7 +1416,7 @@ def gemv_fused(w, x, bias=None, *, norm=None, residual=None, glu=False):
     return _gemv_rows("gemv_fused", "gemv", w, None, x, bias, norm, residual, glu, w8=False, single=True)
 
 
-DECODE_ATTENTION_KERNELS = ("valu", "mfma")    # the two decode-step attentions: da_kernel of csrc/gemv.hip / csrc/decode_attention_mma.hip
+DECODE_ATTENTION_KERNELS = ("valu", "mfma")    # the two decode-step attentions of csrc/decode_attention.hip: da_kernel / dam_kernel
 
 
 def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, scale, ws, single, kernel="valu"):
@@ -1443,8 +1443,9 @@ def _decode_attention_rows(fn, qkv, cos, sin, pos, kcache, vcache, n_q, n_kv, sc
         _arg(fn, "pos", pos, torch.int64, shape=(B,))
     _arg(fn, "ws", ws, torch.float32, shape=(None,), optional=True)
     _need_gpu(qkv, cos, sin, pos, kcache, vcache, ws)
+    from .decode_rows import decode_attention_ws_floats   # (that module imports this one)
     lib = L.load()
-    ws_n = int((lib.rsvld_llama_decode_attention_mma_rows_ws_bytes if mma else lib.rsvld_llama_decode_attention_rows_ws_bytes)(n_q, n_kv, max_len, B)) // 4
+    ws_n = decode_attention_ws_floats(n_q, n_kv, max_len, B, kernel)
     if ws is None:
         ws = torch.empty(ws_n, device=qkv.device, dtype=torch.float32)
     elif ws.numel() < ws_n:

@@ -1,5 +1,5 @@
 """Exact and adversarial inputs for the caption's two softmax attentions -- the decode step (da_kernel + da_combine_kernel of
-csrc/gemv.hip, through ops.llama_decode_attention / decode_rows.llama_decode_attention_rows) and the flash prefill
+csrc/decode_attention.hip, through ops.llama_decode_attention / decode_rows.llama_decode_attention_rows) and the flash prefill
 (prefill_attn_d128_kernel of csrc/prefill_attention.hip): the input builders, the fp64 references, the assertions and the
 preconditions behind tests/test_gpu_caption_attention.py, walked without a GPU by tests/test_caption_attention_cases.py.
 

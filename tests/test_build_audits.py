@@ -32,3 +32,19 @@ def test_lds_dma_kernels_use_no_scratch(unit):
         assert len(res) == 2 and any("attn_split_d64_kernel" in k for k in res) and any("attn_split_d512_kernel" in k for k in res), res
     bad = {k: v for k, v in res.items() if v > 0}
     assert not bad, bad
+
+
+def test_the_device_unit_table_is_the_makefiles():
+    """tools/device_units.py (the compile command of isa_digest.py, audit_scratch.py and audit_m0.py) names every unit of csrc/Makefile's
+    SRCS, in its order, with the flags of the unit's EXTRA line -- and nothing else -- so the audits read the code the library ships."""
+    import re
+    import device_units
+    mk = open(os.path.join(device_units.CSRC, "Makefile")).read()
+    srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
+    extra = {m.group(1) + ".hip": m.group(2).split() for m in re.finditer(r"^\$\(ROOT\)/build/(\w+)\.o: EXTRA := (.*)$", mk, re.M)}
+    assert len(srcs) >= 15 and extra, (srcs, extra)             # the two patterns still match the Makefile
+    assert set(extra) <= set(srcs), extra
+    assert list(device_units.UNITS) == srcs
+    assert {u: list(f) for u, f in device_units.UNITS.items()} == {u: extra.get(u, []) for u in srcs}
+    import audit_m0, audit_scratch, isa_digest
+    assert set(audit_m0.UNITS) | set(audit_scratch.UNITS) <= set(srcs) and list(isa_digest.UNITS) == srcs

@@ -139,7 +139,7 @@ def test_the_attention_kernels_use_no_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import audit_scratch
-    res = audit_scratch.audit("decode_attention_mma.hip")
+    res = audit_scratch.audit("decode_attention.hip")
     assert len(res) == 2 and all("dam_kernel" in k for k in res), res
     assert not any(res.values()), res
 

@@ -1,4 +1,4 @@
-"""The decode-step attention on MFMAs (csrc/decode_attention_mma.hip through ops.llama_decode_attention(kernel="mfma") and
+"""The decode-step attention on MFMAs (dam_kernel of csrc/decode_attention.hip through ops.llama_decode_attention(kernel="mfma") and
 decode_rows.llama_decode_attention_rows(kernel="mfma")), fp16 and bf16, against its contract in include/rsvld_hip.h.
 
   1  the exact families of tests/caption_attention_cases.py at every group size 1 .. 8 and at the positions

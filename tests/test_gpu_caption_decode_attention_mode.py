@@ -1,4 +1,4 @@
-"""``FastDecoder(decode_attention="mfma")``: the token loop's attention on MFMAs (csrc/decode_attention_mma.hip).  Inside the mode a
+"""``FastDecoder(decode_attention="mfma")``: the token loop's attention on MFMAs (dam_kernel of csrc/decode_attention.hip).  Inside the mode a
 batched caption is the one-at-a-time caption token for token (a sequence's bits do not depend on the row count: ``generate``'s single
 row runs the MFMA attention too), with 16-bit and e4m3 weights and with the products on either family of kernels; against the default
 attention the logits move by the rounding of P where the scores used to be rounded -- within the token loop's own tolerance, 2e-2 x the

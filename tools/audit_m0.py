@@ -3,36 +3,29 @@ hipcc reserves M0 and warns that clobbering it "may lead to undefined behaviour"
 COMPILER itself never reads or writes M0 in that translation unit.  Compiles the units to assembly and fails if M0 appears
 anywhere outside an ;;#ASMSTART .. ;;#ASMEND block.   python tools/audit_m0.py [extra hipcc flags]
 (tests/test_build_audits.py runs it for gemm.hip, whose shipped build has such statements.)"""
-import os, subprocess, sys, tempfile
+import os, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "remote-sensing-vision-language-diffusion-model_amd", "csrc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import device_units
 
-
-# translation units whose inline-asm LDS-DMA statements clobber M0, with the flags they are built with
-UNITS = {"attention.hip": ["-fno-slp-vectorize"], "gemm.hip": []}
+# translation units whose inline-asm LDS-DMA statements clobber M0 (flags and compile command: device_units)
+UNITS = ["attention.hip", "gemm.hip"]
 
 
 def audit(unit="attention.hip", extra=()):
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "unit.s")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", *UNITS[unit],
-               f"-I{SRC}", f"-I{os.path.join(ROOT, 'include')}", "-S", "--cuda-device-only", "-o", out,
-               os.path.join(SRC, unit), *extra]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-        bad, inasm, dma = [], False, 0
-        for n, line in enumerate(open(out), 1):
-            if "#ASMSTART" in line:
-                inasm = True
-            elif "#ASMEND" in line:
-                inasm = False
-            else:
-                code = line.split(";")[0]
-                if inasm and "global_load_lds" in code:
-                    dma += 1
-                if not inasm and "m0" in code.replace("vm0", "") and not code.strip().startswith("."):
-                    bad.append((n, line.strip()))
-        return bad, dma
+    bad, inasm, dma = [], False, 0
+    for n, line in enumerate(device_units.assembly(unit, extra=extra).splitlines(), 1):
+        if "#ASMSTART" in line:
+            inasm = True
+        elif "#ASMEND" in line:
+            inasm = False
+        else:
+            code = line.split(";")[0]
+            if inasm and "global_load_lds" in code:
+                dma += 1
+            if not inasm and "m0" in code.replace("vm0", "") and not code.strip().startswith("."):
+                bad.append((n, line.strip()))
+    return bad, dma
 
 
 if __name__ == "__main__":

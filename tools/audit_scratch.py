@@ -4,23 +4,19 @@ in front of the reload and drains the prefetch inside the K loop.  Round 4 lost 
 ``split`` flag in the source selection) before the per-kernel bench table showed it.  Compiles the units to assembly and reports, per
 kernel with matrix instructions, the number of scratch_ instructions.
     python tools/audit_scratch.py            (tests/test_build_audits.py runs it)"""
-import os, re, subprocess, sys, tempfile
+import os, re, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "remote-sensing-vision-language-diffusion-model_amd", "csrc")
-UNITS = {"conv_igemm.hip": [], "conv_halo.hip": [], "gemm.hip": [], "split.hip": ["-fno-slp-vectorize"],
-         "prefill_attention.hip": ["-fno-slp-vectorize"], "gemm_w8.hip": [], "decode_attention_mma.hip": []}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import device_units
+
+# the units with LDS-DMA kernels (flags and compile command: device_units)
+UNITS = ["conv_igemm.hip", "conv_halo.hip", "gemm.hip", "split.hip", "prefill_attention.hip", "gemm_w8.hip", "decode_attention.hip"]
 # kernels allowed a few scratch instructions OUTSIDE their loops (none today); name fragment -> max count
 ALLOW = {}
 
 
 def audit(unit):
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "unit.s")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", *UNITS[unit],
-               f"-I{SRC}", f"-I{os.path.join(ROOT, 'include')}", "-S", "--cuda-device-only", "-o", out, os.path.join(SRC, unit)]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-        txt = open(out).read()
+    txt = device_units.assembly(unit)
     parts = re.split(r"^(_Z[^\s:]+):[^\n]*$", txt, flags=re.M)
     res = {}
     for i in range(1, len(parts) - 1, 2):

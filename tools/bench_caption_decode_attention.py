@@ -1,5 +1,5 @@
-"""A-B of the token loop's decode attention: the VALU operator (da_kernel + da_combine_kernel of csrc/gemv.hip) against the MFMA
-operator (prologue + attention + combine of csrc/decode_attention_mma.hip, ``FastDecoder(decode_attention="mfma")``) at B = 1, 2, 4, 8
+"""A-B of the token loop's decode attention: the VALU operator (da_kernel + da_combine_kernel of csrc/decode_attention.hip) against the MFMA
+operator (dam_prologue_kernel + dam_kernel + da_combine_kernel of the same unit, ``FastDecoder(decode_attention="mfma")``) at B = 1, 2, 4, 8
 sequences, in ONE process on one device, on the shape of the full-size seeded 8 B decoder of tools/synthetic_models.py: 32 query heads
 on 8 kv heads, max_len 3 328, positions from 3 047 (the bench's prompt: profiles/r06_bench_c4.json).  The protocol of
 tools/bench_caption_decode_mfma.py: six alternated pairs per cell, three in each order, the median per mode.
@@ -9,7 +9,7 @@ tools/bench_caption_decode_mfma.py: six alternated pairs per cell, three in each
       token loop replays its step -- fp16; beside each the key / value bytes the call has to read and the TB/s they imply;
   (b) ``--loop``: ms per step of the token loop (``FastDecoder.profile``, ``decode="mfma"``) for the 16-bit and the e4m3 weights,
       ``decode_attention`` valu against mfma, and whether row 0 of the batched loop equals the mode's single loop;
-  ``--resources`` (no GPU needed): the compiler's resource report of csrc/decode_attention_mma.hip.
+  ``--resources`` (no GPU needed): the compiler's resource report of csrc/decode_attention.hip.
 
     python tools/bench_caption_decode_attention.py --launches --loop --resources --out profiles/caption_decode_attention_ab.txt
 """
@@ -44,9 +44,7 @@ def launches(dev, log, max_len, pos0, pairs, iters=LAYERS * 8):
     qkv = torch.randn(B8, (N_Q + 2 * N_KV) * HD, device=dev, dtype=dt, generator=g)
     ang = torch.rand(B8, HD // 2, device=dev, generator=g) * 6
     cos, sin = torch.cat([ang.cos(), ang.cos()], dim=1).to(dt), torch.cat([ang.sin(), ang.sin()], dim=1).to(dt)
-    lib = ops.L.load()
-    ws = {"valu": torch.empty(int(lib.rsvld_llama_decode_attention_rows_ws_bytes(N_Q, N_KV, max_len, B8)) // 4, device=dev),
-          "mfma": torch.empty(int(lib.rsvld_llama_decode_attention_mma_rows_ws_bytes(N_Q, N_KV, max_len, B8)) // 4, device=dev)}
+    ws = {k: torch.empty(DR.decode_attention_ws_floats(N_Q, N_KV, max_len, B8, k), device=dev) for k in MODES}
     log(f"\n## (a) us per call of the operator (all its launches), fp16, {N_Q} heads on {N_KV}, max_len {max_len}, positions {pos0} + b, "
         f"{LAYERS} cache pairs in one replayed hipGraph; K/V bytes = 2 x B x {N_KV} x (pos + 1) x {HD} x 2 B")
     summary = []
@@ -144,14 +142,14 @@ def loop(dev, log, save, prompt, new_tokens, pairs):
 
 
 def resources(log):
-    """The compiler's report of csrc/decode_attention_mma.hip (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel."""
+    """The compiler's report of csrc/decode_attention.hip (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel."""
     src = os.path.join(ROOT, "remote-sensing-vision-language-diffusion-model_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", f"-I{src}",
                f"-I{os.path.join(ROOT, 'include')}", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-               "-o", os.path.join(tmp, "unit.s"), os.path.join(src, "decode_attention_mma.hip")]
+               "-o", os.path.join(tmp, "unit.s"), os.path.join(src, "decode_attention.hip")]
         err = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, text=True).stderr
-    log("\n## compiler report of csrc/decode_attention_mma.hip (gfx950)")
+    log("\n## compiler report of csrc/decode_attention.hip (gfx950)")
     cur = {}
     for line in err.splitlines():
         m = re.search(r"remark: \s*(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs|LDS Size \[bytes/block\]): (\S+)", line)

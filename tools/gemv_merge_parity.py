@@ -5,6 +5,8 @@ parent commit's librsvld_hip.so), one on this tree's build; the parent process c
 group of cases.  The single-row functions reach each build's single-row entry points, the ``_rows`` functions its multi-row ones.
 
     python tools/gemv_merge_parity.py --other /path/to/other/librsvld_hip.so [--out profiles/gemv_merge_parity.txt]
+
+tools/caption_attention_parity.py is the same run (``main`` below) over the caption's attention kernels.
 """
 import argparse
 import os
@@ -99,8 +101,10 @@ def compute(path):
     torch.save(out, path)
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+def main(argv=None, compute=compute, script=os.path.abspath(__file__), what="decode operators", doc=__doc__):
+    """``compute(path)`` saves {case: CPU tensor} in a child process per build (``script --child path``); the cases are grouped by their
+    first three words (four for a product)."""
+    ap = argparse.ArgumentParser(description=doc.split("\n")[0])
     ap.add_argument("--other", help="the other build of librsvld_hip.so")
     ap.add_argument("--out", default=None, help="also write the summary to this file")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
@@ -108,7 +112,7 @@ def main(argv=None):
     if a.child:
         return compute(a.child)
     if not a.other or not os.path.exists(a.other):
-        sys.exit("gemv_merge_parity.py: --other must name the other build of the library")
+        sys.exit(f"{os.path.basename(script)}: --other must name the other build of the library")
     import torch
     with tempfile.TemporaryDirectory() as tmp:
         got = {}
@@ -118,9 +122,9 @@ def main(argv=None):
             if lib:
                 env["RSVLD_LIB"] = lib
             path = os.path.join(tmp, name + ".pt")
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, check=True, timeout=600)
+            subprocess.run([sys.executable, script, "--child", path], env=env, check=True, timeout=600)
             got[name] = torch.load(path)
-    lines = [f"# decode operators, the other build against this tree's, torch.equal per case ({torch.__version__}); "
+    lines = [f"# {what}, the other build against this tree's, torch.equal per case ({torch.__version__}); "
              f"single-row functions on each build's single-row entry points"]
     groups, bad = {}, []
     assert got["other"].keys() == got["tree"].keys()
