@@ -309,7 +309,12 @@ def upload_u8(img, device):
     arr = np.array(img, dtype=np.uint8)          # (a copy: PIL's buffer is read-only)
     if arr.ndim != 3:
         raise L.RsvldOperandError(f"an RGB image is expected, got an array of shape {arr.shape}")
-    return _torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+    host = _torch.from_numpy(np.ascontiguousarray(arr))
+    if _torch.device(device).type != "cuda":
+        return host.to(device)
+    # from pinned memory, queued like a kernel: an upload from pageable memory makes the host wait for everything that is queued on
+    # the current stream (the pinned block is the host allocator's: it is not handed out again before the copy has run)
+    return host.pin_memory().to(device, non_blocking=True)
 
 
 def load_sr_input(image, scale=1, device="cuda:0", plan=None):

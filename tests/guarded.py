@@ -28,9 +28,14 @@ lives in a buffer of its own,
   3. every returned tensor is finite in every element: nothing left unwritten, no poison consumed;
   4. the returned tensors are bit-identical to those of the same call on ordinary tensors (``same_bits``).
 
+``run_guarded`` then repeats the guarded run on a side stream behind a gate, with operands that arrive late (``run_streamed``): the
+same four verdicts there show that every launch of the call went to the stream the wrapper handed to the library.
+
 No kernel is ever made to misbehave for the sake of this module: tests/test_guarded_instrument.py shows on the CPU, with writes
 through ``Region.raw``, that each verdict rejects what it is for."""
 import contextlib
+import math
+import time
 import types
 
 import torch
@@ -88,13 +93,26 @@ class Region:
 
 
 class Arena:
-    def __init__(self):
+    """``Arena()``: every buffer is filled and every operand copied on the current stream.  ``Arena(early, late)``: the arena of a
+    streamed run (``run_streamed``).  The 0xFF fill of every buffer runs on ``early`` -- the stream that was current before the
+    side stream ``late`` was entered, whose work is not held back by the gate -- and ``late`` waits for it; an operand placed
+    before ``arrive()`` keeps a 0xFF payload until ``arrive()`` queues its copy on the current stream."""
+
+    def __init__(self, early=None, late=None):
+        assert (early is None) == (late is None)
         self.regions = []
+        self.early, self.late = early, late
+        self.pending = None if late is None else []     # operands whose payload has not been queued yet
 
     # ------------------------------------------------------------------ allocation
     def _region(self, nbytes, pitch, device, name, kind):
         guard = guard_bytes(pitch)
-        raw = torch.full((guard + ALIGN + nbytes + guard,), POISON, dtype=torch.uint8, device=device)
+        if self.late is None:
+            raw = torch.full((guard + ALIGN + nbytes + guard,), POISON, dtype=torch.uint8, device=device)
+        else:      # poison at once, whatever the side stream is waiting for: a launch that strays from it finds 0xFF, not stale bytes
+            with torch.cuda.stream(self.early):
+                raw = torch.full((guard + ALIGN + nbytes + guard,), POISON, dtype=torch.uint8, device=device)
+            self.late.wait_stream(self.early)
         start = guard + (-(raw.data_ptr() + guard)) % ALIGN
         r = Region(raw, start, start + nbytes, guard, name, kind)
         assert (raw.data_ptr() + start) % ALIGN == 0 and start >= guard and raw.numel() - r.end >= guard
@@ -137,17 +155,21 @@ class Arena:
         span = 0 if t.numel() == 0 else 1 + sum((n - 1) * s for n, s in zip(shape, strides))
         r = self._region(span * isz, _row_pitch(shape, strides, isz), t.device, name, "operand")
         dense = t.is_contiguous()
+        r.placed = torch.full((span * isz,), POISON, dtype=torch.uint8, device=t.device)     # the payload as placed
         if span:
             if dense or poison_gaps:
                 src = t.detach().contiguous().view(-1).view(torch.uint8).view(shape + (isz,))
-                _byte_view(r.raw, shape, strides, r.start, isz).copy_(src)
+                _byte_view(r.placed, shape, strides, 0, isz).copy_(src)
             else:
                 src = torch.as_strided(t.detach(), (span,), (1,), t.storage_offset())
-                r.payload.copy_(src.contiguous().view(torch.uint8))
+                r.placed.copy_(src.contiguous().view(torch.uint8))
+        if self.pending is not None:
+            self.pending.append(r)
+        else:
+            r.payload.copy_(r.placed)
         r.view = self._typed(r, t.dtype, shape, strides)
         assert r.view.shape == t.shape and r.view.stride() == t.stride() and r.view.dtype == t.dtype
         assert t.numel() == 0 or r.view.data_ptr() % ALIGN == 0
-        r.placed = r.payload.clone()
         if not dense:
             r.is_data = torch.zeros(span * isz, dtype=torch.uint8, device=t.device)
             _byte_view(r.is_data, shape, strides, 0, isz).fill_(1)
@@ -162,6 +184,12 @@ class Arena:
             if hasattr(t, attr):
                 setattr(r.view, attr, getattr(t, attr))
         return r.view
+
+    def arrive(self):
+        """Streamed run: queue, on the current stream, the payload of every operand placed so far; later operands are copied at once."""
+        for r in self.pending:
+            r.payload.copy_(r.placed)
+        self.pending = None
 
     def place_view(self, t, name, inplace=None):
         """``place`` for a view the wrappers accept (column slices of a fused tensor, a channel slice of a stacked one): the storage
@@ -373,7 +401,9 @@ class Op:
         self.value, self.inplace, self.view, self.forms = value, inplace, view, tuple(forms)
 
 
-def _place_value(arena, v, name, op):
+def _place_value(arena, v, name, op, later=None):
+    """``later``: None, or the list of a streamed run: the lazy forms of a PackedConv are then packed by the thunk appended to it
+    (behind the gate, from the late-arriving ``w`` of the arena) instead of at once."""
     from rsvld_amd import ops
     if v is None or isinstance(v, (int, float, bool, str)):
         return v
@@ -386,18 +416,26 @@ def _place_value(arena, v, name, op):
             g._gn_part = (arena.place(part[0], name + "._gn_part"), part[1])
         return g
     if isinstance(v, ops.Planes):
-        return ops.Planes(_place_value(arena, v.t, name + ".t", op))
+        return ops.Planes(_place_value(arena, v.t, name + ".t", op, later))
     if isinstance(v, ops.Q8Rows):
-        return ops.Q8Rows(_place_value(arena, v.t, name + ".t", op))
+        return ops.Q8Rows(_place_value(arena, v.t, name + ".t", op, later))
     if isinstance(v, ops.PackedConv):
         g = copy_packed(v)
         packers = {"w1": ops._w1, "w2": ops._w2, "w3": ops._w3, "wq8": ops._wq8}
-        with torch_proxy(arena):
-            for f in op.forms:
-                packers[f](g)
-        return relocate(g, arena, name)
+
+        def pack():
+            with torch_proxy(arena):
+                for f in op.forms:
+                    packers[f](g)
+            relocate(g, arena, name)
+        if later is None:
+            pack()
+        else:
+            relocate(g, arena, name)      # ``w`` / ``bias``: placed now, arriving late
+            later.append(pack)
+        return g
     if isinstance(v, (tuple, list)):
-        return type(v)(_place_value(arena, e, f"{name}[{i}]", op) for i, e in enumerate(v))
+        return type(v)(_place_value(arena, e, f"{name}[{i}]", op, later) for i, e in enumerate(v))
     raise TypeError(f"operand '{name}': cannot place a {type(v).__name__}")
 
 
@@ -408,31 +446,19 @@ def _plain_value(v, op):
     return v
 
 
-def run_guarded(fn, operands, *, expect=None, finite=None, compare_inplace=True):
-    """Place the operands, call ``fn(**operands)`` under the allocation proxy, call it on ordinary tensors, give the verdict.
-    ``operands``: {name: tensor | Op | anything ``Op`` may hold}; identical objects (``k is v``) stay identical.
-    ``expect``: name(s) of kernels that must have been launched (``LaunchRecorder``).  Returns (guarded result, recorder); the
-    recorder carries the arena (``rec.arena``)."""
+def _place_all(arena, ops_, later=None):
+    placed, seen = {}, {}
+    for k, o in ops_.items():
+        key = id(o.value)
+        if key not in seen:
+            seen[key] = _place_value(arena, o.value, k, o, later)
+        placed[k] = seen[key]
+    return placed
+
+
+def _judge(arena, ops_, got, guarded_in, plain, plain_in, finite, compare_inplace):
+    """The four verdicts of one guarded run against the plain run, the in-place operands and the packed forms included."""
     from rsvld_amd import ops
-    ops_ = {k: (v if isinstance(v, Op) else Op(v)) for k, v in operands.items()}
-    plain_in, seen = {}, {}
-    for k, o in ops_.items():
-        key = id(o.value)
-        if key not in seen:
-            seen[key] = _plain_value(o.value, o)
-        plain_in[k] = seen[key]
-    plain = fn(**plain_in)
-    arena = Arena()
-    guarded_in, seen = {}, {}
-    for k, o in ops_.items():
-        key = id(o.value)
-        if key not in seen:
-            seen[key] = _place_value(arena, o.value, k, o)
-        guarded_in[k] = seen[key]
-    rec = LaunchRecorder()
-    rec.arena = arena
-    with torch_proxy(arena), ops.tuning(profiler=rec):
-        got = fn(**guarded_in)
     for (name, t) in tensors_of(got):
         assert arena.owns(t) or t.numel() == 0, f"returned tensor '{name}' was not allocated through ops' torch.empty / zeros"
     arena.verdict(got, plain, finite)
@@ -446,7 +472,214 @@ def run_guarded(fn, operands, *, expect=None, finite=None, compare_inplace=True)
                 a, b = getattr(guarded_in[k], f), getattr(plain_in[k], f)
                 if b is not None:
                     same_bits({f"{k}.{f}": a}, {f"{k}.{f}": b})
+
+
+def run_guarded(fn, operands, *, expect=None, finite=None, compare_inplace=True, streamed=None):
+    """Place the operands, call ``fn(**operands)`` under the allocation proxy, call it on ordinary tensors, give the verdict; with
+    device operands (or ``streamed=True``: a case that makes its device tensors itself) the same again on a gated side stream
+    (``run_streamed``).  ``operands``: {name: tensor | Op | anything ``Op`` may hold}; identical objects (``k is v``) stay identical.
+    ``expect``: name(s) of kernels that must have been launched (``LaunchRecorder``).  Returns (guarded result, recorder); the
+    recorder carries the arena (``rec.arena``) and, after a streamed run, its record (``rec.streamed``)."""
+    from rsvld_amd import ops
+    ops_ = {k: (v if isinstance(v, Op) else Op(v)) for k, v in operands.items()}
+    plain_in, seen = {}, {}
+    for k, o in ops_.items():
+        key = id(o.value)
+        if key not in seen:
+            seen[key] = _plain_value(o.value, o)
+        plain_in[k] = seen[key]
+    t0 = time.perf_counter()
+    plain = fn(**plain_in)
+    plain_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    arena = Arena()
+    guarded_in = _place_all(arena, ops_)
+    rec = LaunchRecorder()
+    rec.arena = arena
+    with torch_proxy(arena), ops.tuning(profiler=rec):
+        got = fn(**guarded_in)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    _judge(arena, ops_, got, guarded_in, plain, plain_in, finite, compare_inplace)
     if expect is not None:
         for e in ((expect,) if isinstance(expect, str) else expect):
             assert rec.ran(e), f"kernel '{e}' did not run; launched: {rec.names}"
+    if streamed is None:
+        streamed = any(_device_tensors(o.value) for o in ops_.values()) or any(t.is_cuda for _, t in tensors_of(got))
+    if streamed:
+        rec.streamed = run_streamed(fn, ops_, plain, plain_in, host_ms=host_ms, plain_ms=plain_ms, finite=finite,
+                                    compare_inplace=compare_inplace, names=rec.names)
     return got, rec
+
+
+# ---------------------------------------------------------------------- the streamed run
+class Inconclusive(AssertionError):
+    """The gate of a streamed run had finished before the host had queued the whole call: a launch on another stream would not have
+    been told from one on the side stream, so the run proves nothing.  Never a pass, never a skip."""
+
+
+GATE_N = 4096            # one link of the gate: an fp16 matrix product of this order (0.14 TFLOP)
+GATE_MARGIN = 4.0        # gate = GATE_MARGIN x the host time of the case's guarded run + GATE_FLOOR_MS; then 4 x that, once
+GATE_FLOOR_MS = 2.0
+STREAM_LOG = []          # one record per streamed run of this process (the tests print them; a summary reads them)
+_GATES, _SIDE = {}, {}
+
+
+def side_stream(device):
+    """THE side stream of this process on ``device``: one, so that no test run ever holds more than two streams."""
+    key = torch.device(device).index or 0
+    if key not in _SIDE:
+        _SIDE[key] = torch.cuda.Stream(device=device)
+    return _SIDE[key]
+
+
+class Gate:
+    """A finite chain of fp16 matrix products on the current stream: plain torch work that ends by itself, whatever becomes of the
+    test that queued it (no kernel here waits for a flag).  ``ms_per_link`` is measured once per process, with events."""
+
+    def __init__(self, device):
+        self.a = torch.full((GATE_N, GATE_N), 1.0 / GATE_N, dtype=torch.float16, device=device)
+        self.b = torch.full((GATE_N, GATE_N), 1.0, dtype=torch.float16, device=device)
+        self.c = torch.empty((GATE_N, GATE_N), dtype=torch.float16, device=device)
+        self.queue(links=3)       # the library's own first-call work
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        self.queue(links=32)
+        e1.record()
+        e1.synchronize()
+        self.ms_per_link = e0.elapsed_time(e1) / 32
+
+    def queue(self, ms=None, links=None):
+        links = max(1, math.ceil(ms / self.ms_per_link)) if links is None else links
+        for _ in range(links):
+            torch.mm(self.a, self.b, out=self.c)
+        return links
+
+
+def gate_for(device):
+    key = torch.device(device).index or 0
+    if key not in _GATES:
+        _GATES[key] = Gate(device)
+    return _GATES[key]
+
+
+class StreamedRecorder(LaunchRecorder):
+    """``LaunchRecorder`` that asks, after every launch is queued, whether the gate is still running."""
+
+    def __init__(self, gate_done):
+        super().__init__()
+        self.gate_done, self.pending = gate_done, []
+
+    def run(self, name, flops, nbytes, fn):
+        self.names.append(name)
+        out = fn()
+        self.pending.append(not self.gate_done.query())
+        return out
+
+
+class GatedStream:
+    """``with GatedStream(device, gate_ms) as g:`` -- inside the block THE side stream is current; it waits for the stream that was
+    current before, then for a gate of about ``gate_ms`` (0: none).  ``g.pending()``: is the gate still running?"""
+
+    def __init__(self, device, gate_ms):
+        self.early, self.side, self.gate = torch.cuda.current_stream(device), side_stream(device), gate_for(device)
+        assert self.side != self.early and self.side != torch.cuda.default_stream(device)
+        self.want_ms, self.done, self.links = gate_ms, torch.cuda.Event(), 0
+
+    def __enter__(self):
+        self.side.wait_stream(self.early)
+        self._ctx = torch.cuda.stream(self.side)
+        self._ctx.__enter__()
+        self.t0 = time.perf_counter()
+        if self.want_ms > 0:
+            self.links = self.gate.queue(ms=self.want_ms)
+        self.done.record(self.side)
+        return self
+
+    @property
+    def gate_ms(self):
+        return self.links * self.gate.ms_per_link
+
+    def pending(self):
+        return not self.done.query()
+
+    def __exit__(self, *exc):
+        self.host_ms = (time.perf_counter() - self.t0) * 1e3
+        return self._ctx.__exit__(*exc)
+
+
+def _streamed_once(fn, ops_, gate_ms, device):
+    """One streamed run -> (arena, operands as placed, result, recorder, was the gate pending throughout?, the GatedStream)."""
+    from rsvld_amd import ops
+    g = GatedStream(device, gate_ms)
+    arena, later = Arena(g.early, g.side), []
+    guarded_in = _place_all(arena, ops_, later)        # buffers poisoned, payloads staged: nothing has arrived
+    with g:
+        arena.arrive()                                  # the operands: behind the gate
+        for pack in later:                              # the lazy weight forms: packed behind the gate, from what arrived
+            pack()
+        rec = StreamedRecorder(g.done)
+        rec.arena = arena
+        with torch_proxy(arena), ops.tuning(profiler=rec):
+            got = fn(**guarded_in)
+        pending = g.pending() and all(rec.pending)
+    g.side.synchronize()
+    return arena, guarded_in, got, rec, pending, g
+
+
+def run_streamed(fn, ops_, plain, plain_in, *, host_ms, plain_ms=float("nan"), finite=None, compare_inplace=True, names=None,
+                 gate_ms=None, device=None):
+    """The guarded run again, on a side stream behind a gate.
+
+    A second, non-blocking stream ``s`` waits for the current one; the first thing queued on it is the gate (``Gate``), sized from
+    the host time of the case's own guarded run (``host_ms``: placement and call, the same host work as here; ``plain_ms``, the
+    plain call's, is printed beside it -- it lacks the arena's allocations and, for the first call of a process, carries one-time
+    costs).  Every buffer of a fresh arena is poisoned at once, but the operands' payloads are copied on ``s`` BEHIND the gate, the
+    lazy PackedConv forms are packed there, and only then is ``fn`` called, inside ``torch.cuda.stream(s)``.  After
+    ``s.synchronize()`` the four verdicts of ``run_guarded`` apply.
+
+    What this catches: a launch that does not go to the stream ``ops._stream()`` hands to the library -- a dropped argument, a 0, the
+    second launch of a multi-kernel op, a packer -- does not wait for the gate.  It reads operands that are still 0xFF, or a
+    workspace its predecessor on ``s`` has not written, and a result is non-finite or differs from the plain run; if it only WRITES
+    early, the late arrival or its successor on ``s`` overwrites it.  That needs no luck PROVIDED the gate is still running when
+    the host has queued the whole call, which is checked: an event recorded behind the gate must be pending after every launch
+    (``StreamedRecorder``) and after ``fn`` returns.  If it is not, the run is repeated ONCE with a gate four times as long; if
+    it still is not, ``Inconclusive`` is raised -- a wrapper that synchronises the host inside the call always ends there."""
+    if device is None:
+        devs = [t.device for o in ops_.values() for _, t in _device_tensors(o.value)] + [t.device for _, t in tensors_of(plain) if t.is_cuda]
+        device = devs[0] if devs else torch.device("cuda", torch.cuda.current_device())
+    first = GATE_MARGIN * host_ms + GATE_FLOOR_MS if gate_ms is None else gate_ms
+    tries = []
+    for ms in (first, 4 * first):
+        arena, guarded_in, got, rec, pending, g = _streamed_once(fn, ops_, ms, device)
+        tries.append(dict(gate_ms=g.gate_ms, links=g.links, host_ms=g.host_ms, pending=pending))
+        if pending:
+            break
+    log = dict(tries=tries, guarded_host_ms=host_ms, plain_ms=plain_ms, names=list(rec.names), conclusive=pending)
+    STREAM_LOG.append(log)
+    last = tries[-1]
+    print(f"streamed: gate {last['gate_ms']:.2f} ms ({last['links']} links), host {last['host_ms']:.2f} ms (guarded run {host_ms:.2f} ms, "
+          f"plain run {plain_ms:.2f} ms), {len(tries)} attempt(s), launched {rec.names}")
+    if not pending:
+        raise Inconclusive(f"the gate ({last['gate_ms']:.2f} ms, after {tries[0]['gate_ms']:.2f} ms) had finished before the call was queued "
+                           f"(host {last['host_ms']:.2f} ms): the host waits for the stream inside the call?  launched {rec.names}, "
+                           f"gate pending after each: {rec.pending}")
+    if names is not None:
+        assert rec.names == list(names), f"the streamed run launched {rec.names}, the guarded run {list(names)}"
+    try:
+        _judge(arena, ops_, got, guarded_in, plain, plain_in, finite, compare_inplace)
+    except GuardError as e:
+        raise GuardError(f"on a gated side stream (launched {rec.names}): {e}") from None
+    return log
+
+
+def _device_tensors(v):
+    from rsvld_amd import ops
+    if isinstance(v, torch.Tensor):
+        return [("", v)] if v.is_cuda else []
+    if isinstance(v, (ops.Planes, ops.Q8Rows)):
+        return _device_tensors(v.t)
+    if isinstance(v, ops.PackedConv):
+        return _device_tensors(v.w)
+    if isinstance(v, (tuple, list)):
+        return [p for e in v for p in _device_tensors(e)]
+    return []

@@ -172,7 +172,9 @@ def test_fast_decoder_fused_decode_step_equals_the_torch_sequence(cuda):
 
 def test_pipeline_with_live_caption_end_to_end(cuda, tmp_path):
     """BASELINE configs[3] in miniature: Stage 1 -> uint8 hand-off -> LIVE LLaVA-NeXT caption (tiny seeded model on the device)
-    -> Stage 2 with that caption -> PNG, through SuperResolutionPipeline.process() exactly as the CLI runs it."""
+    -> Stage 2 with that caption -> PNG, through SuperResolutionPipeline.process() exactly as the CLI runs it.  Twice on one pipeline:
+    with Stage 2's VAE front on a second stream beside the caption loop (``overlap_vae_with_caption``, the default) and in the serial
+    order -- the same caption, the same PNG bytes and the same state of the global generators afterwards."""
     from PIL import Image
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import llava_common as C
@@ -214,10 +216,31 @@ def test_pipeline_with_live_caption_end_to_end(cuda, tmp_path):
         for p_ in pipe.refinement_model.parameters():
             if p_.dim() >= 2 and float(p_.abs().max()) == 0.0:
                 p_.copy_((torch.randn(p_.shape, generator=g) * 0.02).to(p_.device))
+    import guarded
+    pipe._side_stream = guarded.side_stream(cuda)           # the one side stream of the test process
+    assert pipe.cfg.overlap_vae_with_caption                 # the default: Stage 2's VAE front runs beside the caption loop
+    start = torch.get_rng_state(), torch.cuda.get_rng_state()
+    fronts = []
+    orig_front = pipe.start_vae_front
+    pipe.start_vae_front = lambda img: fronts.append(1) or orig_front(img)
     outs = pipe.process()
     assert isinstance(seen["caption"], str) and len(seen["caption"]) > 0          # the live caption reached Stage 2
     assert [os.path.basename(o) for o in outs] == ["tile_final_0.png"]
     assert np.asarray(Image.open(outs[0])).std() > 1.0
+    # the same image again in the serial order: the same caption, the same pixels, the same random draws (the caption samples inside
+    # a forked generator, so the posterior noise of the VAE front is the same draw before or after it)
+    overlapped = seen.pop("caption"), np.asarray(Image.open(outs[0])).copy(), np.asarray(Image.open(tmp_path / "out" / "sr3_tile.png")).copy()
+    after = torch.get_rng_state(), torch.cuda.get_rng_state()
+    torch.set_rng_state(start[0])
+    torch.cuda.set_rng_state(start[1])
+    pipe.cfg.overlap_vae_with_caption = False
+    outs2 = pipe.process()
+    assert fronts == [1] and outs2 == outs                    # the front ran in the first pass only
+    assert seen["caption"] == overlapped[0]
+    assert np.array_equal(np.asarray(Image.open(tmp_path / "out" / "sr3_tile.png")), overlapped[2])
+    final = np.asarray(Image.open(outs2[0]))
+    assert np.array_equal(final, overlapped[1]), f"{int((final != overlapped[1]).sum())} bytes of the PNG differ between the overlapped and the serial order"
+    assert torch.equal(torch.get_rng_state(), after[0]) and torch.equal(torch.cuda.get_rng_state(), after[1])
 
 
 def test_build_then_smoke_in_one_process(cuda):

@@ -217,9 +217,11 @@ def test_run_guarded_end_to_end_with_a_cpu_wrapper(monkeypatch):
         return out
     g = torch.Generator().manual_seed(1)
     wide = torch.randn(6, 16, generator=g)
+    streamed_before = len(G.STREAM_LOG)
     got, rec = G.run_guarded(wrapper, dict(x=torch.randn(6, 8, generator=g), y=G.Op(wide[:, 8:], view=True), acc=G.Op(torch.zeros(3), inplace=True)),
                              expect="stand_in")
     assert rec.names == ["stand_in [2x3]"] and got._nhwc and ops.context().profiler is None and ops.torch is torch
+    assert not hasattr(rec, "streamed") and len(G.STREAM_LOG) == streamed_before      # host operands: no side stream, no device is touched
     with pytest.raises(AssertionError, match="did not run"):
         G.run_guarded(wrapper, dict(x=wide, y=wide, acc=G.Op(torch.zeros(3), inplace=True)), expect="stand_in_w2")
     def leaky(x, y):                                                          # reads one row past ``x``: the poison reaches the result
