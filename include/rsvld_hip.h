@@ -38,7 +38,7 @@ extern "C" {
 
 #define RSVLD_F16 0
 #define RSVLD_BF16 1
-#define RSVLD_F32 2   /* accepted ONLY by the *_f32 entry points at the end of this header */
+#define RSVLD_F32 2   /* accepted ONLY by the *_f32 entry points at the end of this header (and by rsvld_clip_views_u8, as its output type) */
 #define RSVLD_SPLIT 3 /* split-operand precision on the 16-bit tilings (rsvld_conv_desc.dtype; the *_split entry points below) */
 #define RSVLD_F16W2 4 /* fp16 activations x fp16 weight PAIRS [W_lo | W_hi] (rsvld_conv_desc.dtype; see below): two MFMAs per product */
 #define RSVLD_F16Q8 6 /* fp16 hi x hi + the two cross terms of the split product in e4m3 on the block-scaled matrix instruction (see below) */
@@ -696,6 +696,14 @@ int rsvld_nchw_f32_to_u8_hwc(const float* src, uint8_t* dst, int H, int W, int c
  * (models/util.py:159-166); idx_* [n][4] clamped tap indices, w_* [n][4] fp32 weights per output row / column */
 int rsvld_bicubic_f32_to_u8_hwc(const float* src, uint8_t* dst, const int32_t* idx_y, const float* w_y, const int32_t* idx_x,
                                 const float* w_x, int channels, int H, int W, int h0, int w0, void* stream);
+/* The caption's anyres views after their two resizes (llava_next.py process_anyres_image; llava/mm_utils.py:154-190, 245-296), RGB only:
+ * whole uint8 [S][S][3] (the image squashed to S x S), fit uint8 [nh][nw][3] (the aspect-preserving resize), lut [3][256] and
+ * dst [1 + gx gy][3][S][S] in `dtype` (RSVLD_F16 / RSVLD_BF16 / RSVLD_F32; the table is CLIP's rescale + normalise per channel, read off
+ * the image processor on the host).  dst[0][c][y][x] = lut[c][whole[y][x][c]]; view 1 + ty gx + tx reads the canvas pixel
+ * (X, Y) = (tx S + x, ty S + y): fit[Y - oy][X - ox][c] inside [ox, ox + nw) x [oy, oy + nh), byte 0 -- lut[c][0], not 0.0 -- outside.
+ * Every element of dst is written once; no alignment is assumed.  RSVLD_EINVAL if the rectangle leaves the gx S x gy S canvas. */
+int rsvld_clip_views_u8(const uint8_t* whole, const uint8_t* fit, const void* lut, void* dst, int S, int nw, int nh, int ox, int oy,
+                        int gx, int gy, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,7 @@ SIGNATURES = {
     "rsvld_u8_hwc_to_nchw_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "rsvld_nchw_f32_to_u8_hwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "rsvld_bicubic_f32_to_u8_hwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "rsvld_clip_views_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

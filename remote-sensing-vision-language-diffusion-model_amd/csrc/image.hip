@@ -138,6 +138,38 @@ __global__ __launch_bounds__(256) void bicubic_to_u8_kernel(const float* __restr
     }
 }
 
+// The caption's anyres views (llava_next.process_anyres_image after its two resizes): view 0 is the squashed image, view 1 + ty gx + tx
+// the S x S tile (tx, ty) of a black canvas on which `fit` sits at (ox, oy); every byte goes through the table of its channel.  One
+// thread per output pixel, the three planes written contiguously in x.  E carries the BITS of the output type (the table holds values of
+// that type already), so fp16 and bf16 are one instantiation; the table and the output arrive untyped, so that both instantiations are
+// one function type and one launch site.  A canvas pixel outside the pasted rectangle is byte 0, i.e. lut[c][0];
+// the rectangle test is also what keeps every read inside `fit`, and p < S * S what keeps it inside `whole`.
+template <typename E>
+__global__ __launch_bounds__(256) void clip_views_kernel(const uint8_t* __restrict__ whole, const uint8_t* __restrict__ fit,
+                                                         const void* __restrict__ lut, void* __restrict__ dst, int S, int nw, int nh,
+                                                         int ox, int oy, int gx, int64_t pixels) {
+    __shared__ E tab[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) tab[i] = ((const E*)lut)[i];
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // pixel of [view][y][x]
+    if (g >= pixels) return;
+    const int64_t SS = (int64_t)S * S;
+    const int v = (int)(g / SS);
+    const int p = (int)(g - v * SS);
+    const uint8_t* s = nullptr;
+    if (v == 0) {
+        s = whole + (int64_t)p * 3;
+    } else {
+        const int y = p / S, x = p - y * S;
+        const int ty = (v - 1) / gx, tx = (v - 1) - ty * gx;
+        const int X = tx * S + x - ox, Y = ty * S + y - oy;
+        if (X >= 0 && X < nw && Y >= 0 && Y < nh) s = fit + ((int64_t)Y * nw + X) * 3;
+    }
+    E* d = (E*)dst + (int64_t)v * 3 * SS + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c * SS] = tab[c * 256 + (s ? s[c] : 0)];
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
@@ -157,12 +189,10 @@ extern "C" int rsvld_resample_u8(const uint8_t* src, uint8_t* dst, const int32_t
                            src, dst, bounds, coeffs, in_w, channels, out_len, first, ksize);
     } else {
         const int64_t pitch = (int64_t)in_w * channels;
-        if (pitch % 16 == 0 && aligned16(src) && aligned16(dst))
-            hipLaunchKernelGGL(resample_v_kernel<true>, dim3((unsigned)cdiv64(pitch / 16, 256), (unsigned)out_len), dim3(256), 0, s,
-                               src, dst, bounds, coeffs, in_h, pitch, first, ksize);
-        else
-            hipLaunchKernelGGL(resample_v_kernel<false>, dim3((unsigned)cdiv64(pitch, 256), (unsigned)out_len), dim3(256), 0, s,
-                               src, dst, bounds, coeffs, in_h, pitch, first, ksize);
+        const bool vec = pitch % 16 == 0 && aligned16(src) && aligned16(dst);
+        const auto kern = vec ? resample_v_kernel<true> : resample_v_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cdiv64(vec ? pitch / 16 : pitch, 256), (unsigned)out_len), dim3(256), 0, s, src, dst,
+                           bounds, coeffs, in_h, pitch, first, ksize);
     }
     return rsvld_check_launch();
 }
@@ -193,5 +223,21 @@ extern "C" int rsvld_bicubic_f32_to_u8_hwc(const float* src, uint8_t* dst, const
     if (h0 > 65535) return RSVLD_EUNSUPPORTED;                                // rows ride on gridDim.y
     hipLaunchKernelGGL(bicubic_to_u8_kernel, dim3((unsigned)((w0 + 255) / 256), (unsigned)h0), dim3(256), 0, (hipStream_t)stream,
                        src, dst, idx_y, w_y, idx_x, w_x, channels, H, W, w0);
+    return rsvld_check_launch();
+}
+
+extern "C" int rsvld_clip_views_u8(const uint8_t* whole, const uint8_t* fit, const void* lut, void* dst, int S, int nw, int nh,
+                                   int ox, int oy, int gx, int gy, int dtype, void* stream) {
+    if (!whole || !fit || !lut || !dst || S <= 0 || nw <= 0 || nh <= 0 || ox < 0 || oy < 0 || gx <= 0 || gy <= 0) return RSVLD_EINVAL;
+    if ((int64_t)ox + nw > (int64_t)gx * S || (int64_t)oy + nh > (int64_t)gy * S) return RSVLD_EINVAL;      // the paste leaves the canvas
+    if (dtype != RSVLD_F16 && dtype != RSVLD_BF16 && dtype != RSVLD_F32) return RSVLD_EUNSUPPORTED;
+    if (S > 32768 || gx > 32768 || gy > 32768 || (int64_t)gx * S > INT32_MAX / 4 || (int64_t)gy * S > INT32_MAX / 4)
+        return RSVLD_EUNSUPPORTED;
+    const int64_t pixels = (1 + (int64_t)gx * gy) * S * S;
+    if (pixels * 3 > INT32_MAX) return RSVLD_EUNSUPPORTED;                    // (also: the workgroups ride on gridDim.x)
+    const dim3 grid((unsigned)cdiv64(pixels, 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    const auto kern = dtype == RSVLD_F32 ? clip_views_kernel<uint32_t> : clip_views_kernel<uint16_t>;
+    hipLaunchKernelGGL(kern, grid, block, 0, s, whole, fit, lut, dst, S, nw, nh, ox, oy, gx, pixels);
     return rsvld_check_launch();
 }

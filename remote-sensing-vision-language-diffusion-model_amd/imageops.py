@@ -7,7 +7,9 @@ coefficients and bounds of Pillow's ``precompute_coeffs`` / ``normalize_coeffs_8
 256-entry look-up tables (the host functions' very expressions on ``arange(256)``) and ATen's bicubic tap indices and weights (fp32).
 The kernels only gather, multiply-accumulate and store, so the resize, both converters and ``tensor2img`` equal the host route bit
 for bit; the fp32 bicubic of ``Tensor2PIL`` sums its taps in a fixed order that is not ATen's vectorised one and differs from it by
-one 8-bit step in a few bytes per 100 000.
+one 8-bit step in a few bytes per 100 000.  The caption's views (``caption_views``: ``llava_next.process_anyres_image`` of the device
+hand-off image) follow the same rule: the two Pillow resizes, then one gather through a 3 x 256 table that is read off the CLIP image
+processor itself (``clip_lut``), bit for bit the host route's views.
 
 Same rules as ``ops.py``: operand contracts through ``ops._arg``, outputs through ``ops.torch``, launches through ``ops._launch`` on
 the current stream, no CPU fallback, no mutable module global.  Tables are cached on an ``ImagePlan`` its user owns."""
@@ -157,6 +159,87 @@ def bicubic_quantise_numpy(x, h0, w0):
     return quantise_numpy(v, MODE_TENSOR2PIL).transpose(1, 2, 0)
 
 
+# ----------------------------------------------------------------------------- the caption's views (host side; no GPU)
+def anyres_layout(image_size, edge, grid_pinpoints):
+    """Where ``llava_next.process_anyres_image`` puts an image of ``image_size`` = (width, height) for tiles of ``edge`` pixels ->
+    ``(tw, th, nw, nh, ox, oy)``: the canvas, the aspect-preserving size and the paste offset (``llava_next``'s own arithmetic)."""
+    from . import llava_next as LN
+    size = (int(image_size[0]), int(image_size[1]))
+    tw, th = LN.select_best_resolution(size, LN._resolutions(grid_pinpoints, edge))
+    return (tw, th) + LN.fit_and_offset(size, (tw, th))
+
+
+def _clip_probe(S, shuffled):
+    """S x S RGB probe: every channel takes all 256 byte values (a ramp over the pixels in row-major order, or -- ``shuffled`` -- the
+    ramp in a fixed seeded order), each channel another byte at the same pixel."""
+    ramp = np.arange(S * S, dtype=np.int64)
+    if shuffled:
+        ramp = np.random.default_rng(0).permutation(ramp)
+    ramp = ramp.reshape(S, S)
+    return np.ascontiguousarray(np.stack([(ramp + 85 * c) % 256 for c in range(3)], axis=2).astype(np.uint8))
+
+
+def clip_lut(processor, dtype=_torch.float32):
+    """What ``processor.preprocess`` does to a byte of an S x S RGB image, MEASURED: a host ``[3, 256]`` table of ``dtype`` read off
+    the processor's own result on a probe image (so it holds whatever the installed transformers computes: rescale in fp32 or fp64,
+    either backend), ``table[c][byte]``; 16-bit tables are the fp32 table rounded, as the host route's ``.to(dtype)`` rounds the views.
+    Raises ``RsvldError`` where the processor is not such a table at S x S (it resizes, crops or flips there, or returns another
+    shape), where its resize edge and crop differ, and for S * S < 256 (the probe cannot hold every byte)."""
+    from PIL import Image
+    from . import llava_next as LN
+    edge, crop = LN._proc_sizes(processor)
+    if edge != crop:
+        raise L.RsvldError(f"clip_lut: the processor resizes to {edge} and crops to {crop}: its tiles are not taken pixel for pixel")
+    S = edge
+    if S * S < 256:
+        raise L.RsvldError(f"clip_lut: a {S} x {S} probe cannot hold all 256 byte values")
+
+    def run(probe):
+        out = processor.preprocess(Image.fromarray(probe), return_tensors="pt")["pixel_values"]
+        if tuple(out.shape) != (1, 3, S, S) or out.dtype != _torch.float32:
+            raise L.RsvldError(f"clip_lut: preprocess of a {S} x {S} image gave {tuple(out.shape)} {out.dtype}, expected (1, 3, {S}, {S}) fp32")
+        return out[0].numpy().view(np.int32).reshape(3, -1)          # compared as bits
+
+    probe = _clip_probe(S, False)
+    bits = run(probe)
+    table = np.zeros((3, 256), np.int32)
+    for c in range(3):
+        table[c, probe[..., c].reshape(-1)] = bits[c]
+    # one value per byte, wherever the byte stands: on the probe itself, and on the shuffled probe (where S * S = 256 leaves a
+    # single pixel per byte, only the second image shows a processor that moves pixels)
+    for p, got in ((probe, bits), (_clip_probe(S, True), None)):
+        got = run(p) if got is None else got
+        for c in range(3):
+            if not np.array_equal(table[c, p[..., c].reshape(-1)], got[c]):
+                raise L.RsvldError(f"clip_lut: preprocess is not a per-byte table at {S} x {S} (channel {c}: one byte, two values): "
+                                   "it resizes, crops or flips there")
+    return _torch.from_numpy(table.view(np.float32)).to(dtype)
+
+
+def assemble_views_numpy(whole, fit, lut, layout):
+    """``rsvld_clip_views_u8`` in numpy: ``whole`` [S, S, 3] and ``fit`` [nh, nw, 3] uint8, ``lut`` [3, 256], ``layout`` of
+    ``anyres_layout`` -> [1 + tiles, 3, S, S] of the table's type (view 0 the squashed image, then the canvas's tiles row by row)."""
+    tw, th, nw, nh, ox, oy = layout
+    S = whole.shape[0]
+    canvas = np.zeros((th, tw, 3), np.uint8)
+    canvas[oy:oy + nh, ox:ox + nw] = fit
+    views = [whole] + [canvas[y:y + S, x:x + S] for y in range(0, th, S) for x in range(0, tw, S)]
+    lut = np.asarray(lut)
+    return np.stack([np.stack([lut[c][v[..., c]] for c in range(3)], axis=0) for v in views], axis=0)
+
+
+def caption_views_numpy(u8, processor, grid_pinpoints):
+    """``llava_next.process_anyres_image`` of the HWC uint8 RGB array ``u8``, restated (CPU tests and documentation): Pillow's resize
+    to the fitted size and to S x S (``pillow_resize_numpy``), the fitted image on a black canvas, the canvas's S x S tiles row by
+    row, every byte through ``clip_lut`` -> fp32 [1 + tiles, 3, S, S], equal to the host function bit for bit."""
+    from . import llava_next as LN
+    u8 = np.asarray(u8)
+    S = LN._proc_sizes(processor)[0]
+    layout = anyres_layout((u8.shape[1], u8.shape[0]), S, grid_pinpoints)
+    fit = pillow_resize_numpy(u8, layout[2:4])
+    return assemble_views_numpy(pillow_resize_numpy(u8, (S, S)), fit, clip_lut(processor).numpy(), layout)
+
+
 # ----------------------------------------------------------------------------- device tables
 class ImagePlan:
     """The device tables of one user (a pipeline, a benchmark), cached per ``(kind, in, out, device)``.  Building a table is host
@@ -191,6 +274,15 @@ class ImagePlan:
         device = _torch.device(device)
         build = {"stage2": stage2_lut, "loader": loader_lut}[kind]
         return self._get(("lut", kind, device), lambda: _torch.from_numpy(build()).to(device))
+
+    def clip_lut(self, processor, dtype, device):
+        """``clip_lut(processor, dtype)`` on ``device``, measured once per processor setting (not per processor object)."""
+        from . import llava_next as LN
+        device = _torch.device(device)
+        flags = tuple(getattr(processor, f, None) for f in ("do_resize", "do_center_crop", "do_rescale", "do_normalize", "do_convert_rgb"))
+        mean, std = (None if v is None else tuple(float(x) for x in v) for v in (processor.image_mean, processor.image_std))
+        key = ("clip", mean, std, getattr(processor, "rescale_factor", None), flags, LN._proc_sizes(processor), dtype, device)
+        return self._get(key, lambda: clip_lut(processor, dtype).to(device))
 
 
 # ----------------------------------------------------------------------------- launching wrappers
@@ -283,6 +375,38 @@ def bicubic_f32_to_u8(x, table_y, table_x):
     return out
 
 
+_VIEW_DT = {_torch.float16: L.F16, _torch.bfloat16: L.BF16, _torch.float32: L.F32}
+
+
+def clip_views(whole, fit, lut, layout, dtype=_torch.float16):
+    """The caption's views from its two resized images: ``whole`` uint8 [S, S, 3] (the image squashed to S x S), ``fit`` uint8
+    [nh, nw, 3] (the aspect-preserving resize), ``lut`` [3, 256] of ``dtype`` (``ImagePlan.clip_lut``), ``layout`` = (tw, th, nw, nh,
+    ox, oy) of ``anyres_layout`` -> ``dtype`` [1 + tiles, 3, S, S]: view 0 is ``whole``, the others the S x S tiles, row by row, of the
+    black tw x th canvas that holds ``fit`` at (ox, oy); every byte through its channel's table."""
+    fn = "clip_views"
+    _image_u8(fn, "whole", whole)
+    _image_u8(fn, "fit", fit)
+    if dtype not in _VIEW_DT:
+        raise L.RsvldOperandError(f"{fn}: dtype must be one of {tuple(_VIEW_DT)}, got {dtype!r}")
+    S = whole.shape[0]
+    O._arg(fn, "whole", whole, _torch.uint8, shape=(S, S, 3))
+    O._arg(fn, "lut", lut, dtype, shape=(3, 256))
+    try:
+        tw, th, nw, nh, ox, oy = (int(v) for v in layout)
+    except (TypeError, ValueError):
+        raise L.RsvldOperandError(f"{fn}: layout must be the (tw, th, nw, nh, ox, oy) of anyres_layout, got {layout!r}") from None
+    O._arg(fn, "fit", fit, _torch.uint8, shape=(nh, nw, 3))
+    if tw <= 0 or th <= 0 or tw % S or th % S or ox < 0 or oy < 0 or ox + nw > tw or oy + nh > th:
+        raise L.RsvldOperandError(f"{fn}: layout {(tw, th, nw, nh, ox, oy)}: the canvas must be whole tiles of {S} and hold the image")
+    O._need_gpu(whole, fit, lut)
+    gx, gy = tw // S, th // S
+    out = O.torch.empty((1 + gx * gy, 3, S, S), device=whole.device, dtype=dtype)
+    O._launch("clip_views_u8", 0.0, whole.numel() + fit.numel() + out.numel() * out.element_size(), lambda: L.check(
+        L.load().rsvld_clip_views_u8(O._ptr(whole), O._ptr(fit), O._ptr(lut), O._ptr(out), S, nw, nh, ox, oy, gx, gy, _VIEW_DT[dtype],
+                                     O._stream()), "rsvld_clip_views_u8"))
+    return out
+
+
 # ----------------------------------------------------------------------------- the host functions' device mirrors
 def resize_u8(src, size, plan=None, box=None):
     """``Image.resize(size, BICUBIC)`` of HWC uint8 ``src`` on the device: Pillow's horizontal pass, then its vertical pass, each with a
@@ -345,6 +469,28 @@ def pil2tensor(u8, upscale=1, min_size=1024, fix_resize=None, plan=None):
     plan = ImagePlan() if plan is None else plan
     w, h, h0, w0 = pil2tensor_size(u8.shape[1], u8.shape[0], upscale, min_size, fix_resize)
     return u8_to_nchw_f32(resize_u8(u8, (w, h), plan), plan.lut("stage2", u8.device)), h0, w0
+
+
+def caption_views(u8, processor, grid_pinpoints, dtype=_torch.float16, plan=None):
+    """``llava_next.process_anyres_image`` of a device HWC uint8 RGB image -> ``dtype`` [1 + tiles, 3, S, S] on its device, equal bit for
+    bit to the host function's result ``.to(dtype)``: Pillow's resize to the fitted size and to S x S (``resize_u8``; a pass that
+    changes no size is skipped), then ``clip_views``.  Five launches at most, on the current stream; with the tables of ``plan``
+    warm the host neither waits for the device nor copies from it."""
+    from . import llava_next as LN
+    fn = "caption_views"
+    _image_u8(fn, "u8", u8)
+    O._arg(fn, "u8", u8, _torch.uint8, shape=(None, None, 3))
+    if dtype not in _VIEW_DT:
+        raise L.RsvldOperandError(f"{fn}: dtype must be one of {tuple(_VIEW_DT)}, got {dtype!r}")
+    if not u8.is_cuda:
+        O._bad(fn, "u8", "must live on the GPU (the views are made where the image is; the host route is llava_next.process_images)")
+    plan = ImagePlan() if plan is None else plan
+    S = LN._proc_sizes(processor)[0]
+    layout = anyres_layout((u8.shape[1], u8.shape[0]), S, grid_pinpoints)
+    lut = plan.clip_lut(processor, dtype, u8.device)
+    fit = resize_u8(u8, layout[2:4], plan) if tuple(layout[2:4]) != (u8.shape[1], u8.shape[0]) else u8
+    whole = resize_u8(u8, (S, S), plan) if (S, S) != (u8.shape[1], u8.shape[0]) else u8
+    return clip_views(whole, fit, lut, layout, dtype)
 
 
 def tensor2pil_u8(x, h0, w0, plan=None):

@@ -151,6 +151,22 @@ class SuperResolutionPipeline:
         sr_pil.save(self.cfg.output_dir / f"sr3_{self.cfg.filename}.png")
         return sr_pil
 
+    def _caption_views(self, sr_image):
+        """The views the captioner sees of one Stage-1 image: a one-element list of fp16 [1 + tiles, 3, S, S] on ``base_model_device``."""
+        from . import llava_next as LN
+        dev = self.cfg.base_model_device
+        if self.cfg.device_io:
+            # resized, tiled and normalised where the image already is (Stage 1's device copy of its hand-off image; any other image
+            # is uploaded as uint8), on the current stream -- the stream ``tensor2img`` wrote it on and the caption runs on
+            held = self._handoff is not None and self._handoff[0] is sr_image
+            if not held and sr_image.mode != "RGB":
+                raise imageops.L.RsvldError(f"device_io: the caption pass takes an RGB image, got mode {sr_image.mode!r}")
+            u8 = self._handoff[1] if held else imageops.upload_u8(sr_image, dev)
+            return list(LN.process_images_device([u8.to(dev)], self.llava_image_processor, self.llava_model.config, torch.float16,
+                                                 self._plan()))
+        views = LN.process_images([sr_image], self.llava_image_processor, self.llava_model.config)
+        return [v.to(dtype=torch.float16, device=dev) for v in views]
+
     def run_stage2_captioning(self, sr_image) -> str:
         """infer.py:145-166: caption of the Stage-1 image.  Returns the caption STRING handed to just_sampling as p[0]
         (the reference passes get_img_describe's one-element list straight through as ``[caption]``; the text is the same)."""
@@ -163,8 +179,7 @@ class SuperResolutionPipeline:
         with open(self.cfg.prompt_yaml, "r", encoding="utf-8") as f:
             img_prompt = yaml.safe_load(f)["img_prompt"].format(DEFAULT_IMAGE_TOKEN=LN.DEFAULT_IMAGE_TOKEN)
         dev = self.cfg.base_model_device
-        views = LN.process_images([sr_image], self.llava_image_processor, self.llava_model.config)
-        views = [v.to(dtype=torch.float16, device=dev) for v in views]
+        views = self._caption_views(sr_image)
         # a fixed --seed makes the caption reproducible too (sampled inside a forked generator: Stage 2's noise draws do not
         # depend on how many tokens were sampled); --seed < 0 means "random run": the caption samples from the current state
         seed = None if self.cfg.seed < 0 else self.cfg.seed
@@ -186,10 +201,7 @@ class SuperResolutionPipeline:
         with open(self.cfg.prompt_yaml, "r", encoding="utf-8") as f:
             img_prompt = yaml.safe_load(f)["img_prompt"].format(DEFAULT_IMAGE_TOKEN=LN.DEFAULT_IMAGE_TOKEN)
         dev = self.cfg.base_model_device
-        views = []
-        for im in sr_images:
-            v = LN.process_images([im], self.llava_image_processor, self.llava_model.config)
-            views.append([t.to(dtype=torch.float16, device=dev) for t in v])
+        views = [self._caption_views(im) for im in sr_images]
         seeds = None if self.cfg.seed < 0 else [self.cfg.seed] * len(sr_images)
         return LN.get_img_describe_batch(image_tensors=views, images=list(sr_images), model=self.llava_model, tokenizer=self.llava_tokenizer,
                                          prompt=img_prompt, max_new_tokens=256, device=dev, seeds=seeds,

@@ -159,18 +159,25 @@ def select_best_resolution(original_size, possible_resolutions):
     return best
 
 
-def resize_and_pad_image(image, target_resolution):
-    """Aspect-preserving resize (PIL default filter, like the reference) centred on a black canvas (mm_utils.py:154-190)."""
-    from PIL import Image
-    ow, oh = image.size
+def fit_and_offset(original_size, target_resolution):
+    """The geometry of ``resize_and_pad_image`` -> ``(nw, nh, ox, oy)``: the aspect-preserving size of an image of ``original_size``
+    = (width, height) inside ``target_resolution`` and where its top-left corner lands on the canvas (mm_utils.py:154-190)."""
+    ow, oh = original_size
     tw, th = target_resolution
     sw, sh = tw / ow, th / oh
     if sw < sh:
         nw, nh = tw, min(math.ceil(oh * sw), th)
     else:
         nw, nh = min(math.ceil(ow * sh), tw), th
-    canvas = Image.new("RGB", (tw, th), (0, 0, 0))
-    canvas.paste(image.resize((nw, nh)), ((tw - nw) // 2, (th - nh) // 2))
+    return nw, nh, (tw - nw) // 2, (th - nh) // 2
+
+
+def resize_and_pad_image(image, target_resolution):
+    """Aspect-preserving resize (PIL default filter, like the reference) centred on a black canvas (mm_utils.py:154-190)."""
+    from PIL import Image
+    nw, nh, ox, oy = fit_and_offset(image.size, target_resolution)
+    canvas = Image.new("RGB", tuple(target_resolution), (0, 0, 0))
+    canvas.paste(image.resize((nw, nh)), (ox, oy))
     return canvas
 
 
@@ -209,6 +216,17 @@ def process_images(images, image_processor, model_cfg):
     if mode in ("highres", "crop_split", "pad"):
         raise NotImplementedError(f"image_aspect_ratio={mode!r}: the LLaVA-NeXT checkpoints of the pipeline use 'anyres'")
     return image_processor.preprocess(images, return_tensors="pt")["pixel_values"]
+
+
+def process_images_device(u8_images, image_processor, model_cfg, dtype=torch.float16, plan=None):
+    """``process_images`` of device uint8 HWC RGB images, on their device (``imageops.caption_views``: Pillow's resizes and the view
+    assembly as kernels) -> the same views ``.to(dtype)``, bit for bit.  The anyres modes only: any other mode raises."""
+    mode = getattr(model_cfg, "image_aspect_ratio", None)
+    if not (mode == "anyres" or (mode is not None and "anyres_max" in mode)):
+        raise NotImplementedError(f"image_aspect_ratio={mode!r}: the device route makes 'anyres' views only (and has no host fallback)")
+    from . import imageops
+    out = [imageops.caption_views(u8, image_processor, model_cfg.image_grid_pinpoints, dtype, plan) for u8 in u8_images]
+    return torch.stack(out, dim=0) if all(o.shape == out[0].shape for o in out) else out
 
 
 def anyres_grid_shape(image_size, grid_pinpoints, patch_size):

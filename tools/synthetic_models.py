@@ -39,11 +39,19 @@ def _seed_on_device(module, device, dtype, seed):
     return module
 
 
+def clip_l_336_processor():
+    """A CLIP image processor with the ViT-L/14-336 settings (what the 8 B checkpoint's preprocessor_config.json holds)."""
+    from transformers import CLIPImageProcessor
+    return CLIPImageProcessor(do_resize=True, size={"shortest_edge": 336}, do_center_crop=True, crop_size={"height": 336, "width": 336},
+                              do_rescale=True, rescale_factor=1 / 255, do_normalize=True, do_convert_rgb=True, resample=3,
+                              image_mean=[0.48145466, 0.4578275, 0.40821073], image_std=[0.26862954, 0.26130258, 0.27577711])
+
+
 def llava_full(device, seed=5, dtype=torch.float16):
     """-> (model, image_processor, prompt_ids): the 8 B LLaVA-NeXT architecture on ``device`` with seeded random weights,
     a CLIP image processor with the ViT-L/14-336 settings, and a synthetic prompt of PROMPT_TEXT_TOKENS ids around one
     image placeholder."""
-    from transformers import CLIPImageProcessor, CLIPVisionConfig, CLIPVisionModel
+    from transformers import CLIPVisionConfig, CLIPVisionModel
     from rsvld_amd import llava_next as LN
     cfg = LN._llama_config_cls()(**LLAMA3_8B, **LLAVA_MM)
     cfg._attn_implementation = "sdpa"
@@ -52,9 +60,7 @@ def llava_full(device, seed=5, dtype=torch.float16):
     _seed_on_device(model, device, dtype, seed)
     LN._materialise_derived_buffers(model, force=True)     # to_empty left inv_freq / position_ids uninitialised
     model.to(device).eval()
-    proc = CLIPImageProcessor(do_resize=True, size={"shortest_edge": 336}, do_center_crop=True, crop_size={"height": 336, "width": 336},
-                              do_rescale=True, rescale_factor=1 / 255, do_normalize=True, do_convert_rgb=True, resample=3,
-                              image_mean=[0.48145466, 0.4578275, 0.40821073], image_std=[0.26862954, 0.26130258, 0.27577711])
+    proc = clip_l_336_processor()
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(1000, 100000, (PROMPT_TEXT_TOKENS,), generator=g)
     ids[0] = LLAMA3_8B["bos_token_id"]
